@@ -6,7 +6,7 @@ LM_S2GP.forward(sat, grd, mode='test') = two VGG16-U-Nets (MFMA convolutions) + 
 projection/Jacobian/normal-equation/solve steps.  Workload at N=1: BASELINE configs[1]
 (KITTI shapes, batch 32 per GPU, VGG-16 two-branch, 5 LM iters, 3-DoF, bf16).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,12 @@ Multi-GPU: one process per GPU; the batch shards over ranks with no data-path co
 (every sample's solve is independent); a barrier + synchronize brackets the timed
 region and the reported time is the MAX over ranks.  Prints ONE JSON line on rank 0.
 
-Besides the headline (`value`, the precision BASELINE configs[1] names) the line carries, at N=1:
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the headline (`value`, `ms_per_step`).
+--dump-outputs DIR writes what the last timed step returned -- the final pose of every pair, (shift_lat, shift_lon, theta)
+or Ford's (shift_u, shift_v, theta) -- as DIR/<name>.npy (float32; N > 1: all ranks' shards in rank order).  The inputs and
+weights are seeded, so two builds given the same arguments can be compared output for output.
+
+With --full the line also carries the telemetry, per-kernel and roofline figures of the headline and, at N=1:
   by_precision   the same workload in each arithmetic mode -- fp32 (exact-fp32 MFMA), fp16x3 (split fp16, fp32-class
                  results) and bf16 -- with pairs/s, the dominant conv kernel's fraction of ITS roofline, and the measured
                  final-pose deviation from the reference's fp64 run on the committed golden inputs (tests/golden/), in
@@ -23,6 +28,7 @@ Besides the headline (`value`, the precision BASELINE configs[1] names) the line
   train          forward(train) + HIP backward + gradient all-reduce + Adam; train.by_precision: the same step in fp32 / fp16x3 / bf16
                  with the worst per-tensor relative L2 error and cosine of its gradients against the reference autograd
   cpu_baseline   the CPU oracle on this host's cores (bounded sample)
+(--no-cpu-baseline, --no-kernel-timing, --no-extra-legs and --train-steps 0 trim a --full run.)
 """
 import argparse
 import glob
@@ -199,6 +205,25 @@ def timed_infer(net, sat, grd, extra, steps, warmup, dist, tele=None):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     return dt, out
+
+
+OUTPUT_NAMES = {'kitti': ('shift_lat', 'shift_lon', 'theta'), 'g2sp': ('shift_lat', 'shift_lon', 'theta'),
+                'ford': ('shift_u', 'shift_v', 'theta')}      # forward(mode='test')'s tuple, in order
+
+
+def dump_outputs(path, model, out, dist):
+    """--dump-outputs: `out` (one forward(mode='test') return value: B poses per rank, a few hundred bytes) as <path>/<name>.npy in
+    float32 (float64 stays float64).  N > 1: every rank takes part in the gather, rank 0 writes the global batch in rank order."""
+    arrs = [o.detach().to(torch.float64 if o.dtype == torch.float64 else torch.float32).cpu().numpy() for o in out]
+    if dist:
+        shards = [None] * dist.get_world_size()
+        dist.all_gather_object(shards, arrs)
+        if dist.get_rank() != 0:
+            return
+        arrs = [np.concatenate([s[i] for s in shards]) for i in range(len(arrs))]
+    os.makedirs(path, exist_ok=True)
+    for name, x in zip(OUTPUT_NAMES[model], arrs, strict=True):
+        np.save(os.path.join(path, name + '.npy'), x)
 
 
 def kernel_pass(net, sat, grd, extra, n):
@@ -761,6 +786,12 @@ def main(argv=None):
     ap.add_argument('--sat-a', type=int, default=512, help='satellite image side (BASELINE configs[4]: 1024)')
     ap.add_argument('--model', default='kitti', choices=['kitti', 'ford', 'g2sp'],
                     help='kitti = LM_S2GP (the headline, BASELINE configs[1]); ford = LM_S2GP_Ford; g2sp = LM_G2SP')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run every other measurement and check of the line (telemetry, per-kernel timing and '
+                         'rooflines, training step, other precisions and configs, accuracy against the goldens, CPU baseline); '
+                         'the --no-* / --train-* options below apply to such a run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-timing', action='store_true')
     ap.add_argument('--no-extra-legs', action='store_true', help='skip by_precision and the secondary configs (N=1 extras)')
@@ -769,6 +800,8 @@ def main(argv=None):
                     help="arithmetic mode of the `train` object (default fp16x3: the fastest mode whose gradients match the reference's "
                          "autograd inside the fp32 gates; bf16 / fp16 steps are reported under train.by_precision as non-parity extras)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if a.n_iters is None:
         a.n_iters = 10 if a.model == 'ford' else 5
 
@@ -816,16 +849,19 @@ def main(argv=None):
     B = a.batch
     net = build_net(a.model, a.precision, a.n_iters, dev)
     sat, grd, extra = make_inputs(a.model, B, a.grd_hw, a.sat_a, dev, rank)
-    want_kt = (rank == 0) and not a.no_kernel_timing
+    want_kt = (rank == 0) and a.full and not a.no_kernel_timing
 
     # ---- the timed region: exactly K steps, no instrumentation
-    tele = Telemetry(local) if rank == 0 else None
+    tele = Telemetry(local) if rank == 0 and a.full else None
     dt, out = timed_infer(net, sat, grd, extra, a.steps, a.warmup, dist, None)
-    # clock / power of the headline: sampled over a SEPARATE block of the same steps that lasts >= 1 s (>= 100 samples at 100 Hz) and
-    # is not part of `value` -- the timed region itself is 0.1-0.3 s, 13 samples, not a steady-state reading (VERDICT r05 #8a).
-    # N > 1: every rank runs the block (timed_infer has barriers), rank 0 samples.
-    n_tele = max(a.steps, int(1.2 / max(dt / a.steps, 1e-4)) + 1)
-    dt_tele, _ = timed_infer(net, sat, grd, extra, n_tele, 0, dist, tele)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, a.model, out, dist)
+    if a.full:
+        # clock / power of the headline: sampled over a SEPARATE block of the same steps that lasts >= 1 s (>= 100 samples at 100 Hz)
+        # and is not part of `value` -- the timed region itself is 0.1-0.3 s, 13 samples, not a steady-state reading (VERDICT r05 #8a).
+        # N > 1: every rank runs the block (timed_infer has barriers), rank 0 samples.
+        n_tele = max(a.steps, int(1.2 / max(dt / a.steps, 1e-4)) + 1)
+        dt_tele, _ = timed_infer(net, sat, grd, extra, n_tele, 0, dist, tele)
     # ---- the same steps once more on rank 0 with a HIP-event pair around every kernel launch: per-kernel durations for the
     # rooflines.  Kept out of `value` (measured: 8.73 vs 7.97 ms/step), and it would make rank 0 the slowest rank of every multi-GPU run.
     recs, dt_ev = [], None
@@ -838,11 +874,11 @@ def main(argv=None):
         assert all(torch.isfinite(o).all() for o in out)
 
     headline_cfg = (a.model == 'kitti' and B == 32 and a.sat_a == 512 and tuple(a.grd_hw) == (256, 1024) and a.n_iters == 5)
-    pmc, pmc_src = load_pmc() if rank == 0 else (None, None)
+    pmc, pmc_src = load_pmc() if rank == 0 and a.full else (None, None)
 
     # ---- extra: the training step (forward(train) + HIP backward + gradient all-reduce + Adam), same shapes
     train = None
-    if a.train_steps > 0:
+    if a.full and a.train_steps > 0:
         # train.value is measured in the mode whose GRADIENTS are the reference's (the bf16 step's gradients differ
         # from the reference autograd by 0.24 relative L2, the fp16 step's by 0.077 -- the 16-bit dgrad / wgrad products' own
         # rounding, amplified by the cancellation in these gradient sums; the same figures come out behind an exact forward, and
@@ -894,7 +930,7 @@ def main(argv=None):
 
     # ---- N=1 extras: the other arithmetic modes on the same workload, and BASELINE configs[3] / [4]
     by_precision, secondary = None, None
-    if world == 1 and headline_cfg and not a.no_extra_legs:
+    if a.full and world == 1 and headline_cfg and not a.no_extra_legs:
         by_precision = {}
         for p in ('fp32', 'fp16x3', 'bf16', 'fp16'):     # (fp16: the dtype configs[4] names, on configs[1]'s workload)
             try:
@@ -1027,7 +1063,7 @@ def main(argv=None):
             res['secondary'] = secondary
         if train:
             res['train'] = train
-        if not a.no_cpu_baseline and world == 1:        # rank 0 at N = 1 only (the task's contract)
+        if a.full and not a.no_cpu_baseline and world == 1:        # rank 0 at N = 1 only (the task's contract)
             try:
                 res['cpu_baseline'] = cpu_baseline()
             except Exception as ex:     # the headline line must still be printed

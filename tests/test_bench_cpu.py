@@ -162,3 +162,23 @@ def test_step_breakdown_arithmetic_on_fake_events(monkeypatch):
     assert out['steps'] == 3 and out['fwd_sat'] == 4.125 and out['fwd_grd'] == 3.0 and out['glue'] == 0.25 and out['vgg_bwd'] == 9.0
     assert out['optimizer'] == 0.5 and out['inter_step_idle'] == 0.0 and abs(out['sum'] - 20.375) < 1e-9
     assert _s2gp.PHASE_HOOK is None
+
+
+def test_dump_outputs_writes_one_float_array_per_returned_tensor(tmp_path):
+    """--dump-outputs: the forward's (shift_lat, shift_lon, theta) tuple as <name>.npy, float32 (float64 kept), values unchanged."""
+    import numpy as np
+    import torch
+    import bench
+    out = (torch.tensor([0.25, -0.5], dtype=torch.bfloat16), torch.tensor([1.0, 2.0]), torch.tensor([3.0, 4.0], dtype=torch.float64))
+    bench.dump_outputs(str(tmp_path / 'd'), 'kitti', out, None)
+    got = {n: np.load(str(tmp_path / 'd' / (n + '.npy'))) for n in ('shift_lat', 'shift_lon', 'theta')}
+    assert sorted(os.listdir(tmp_path / 'd')) == ['shift_lat.npy', 'shift_lon.npy', 'theta.npy']
+    assert got['shift_lat'].dtype == np.float32 and got['shift_lon'].dtype == np.float32 and got['theta'].dtype == np.float64
+    assert got['shift_lat'].tolist() == [0.25, -0.5] and got['shift_lon'].tolist() == [1.0, 2.0] and got['theta'].tolist() == [3.0, 4.0]
+    bench.dump_outputs(str(tmp_path / 'f'), 'ford', out, None)
+    assert sorted(os.listdir(tmp_path / 'f')) == ['shift_u.npy', 'shift_v.npy', 'theta.npy']
+
+
+def test_steps_must_be_positive_before_touching_the_gpu():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True)
+    assert r.returncode == 2 and '--steps must be >= 1' in r.stderr

@@ -2051,7 +2051,7 @@ def test_bench_gpus_flag_spawns_its_ranks_and_reports_them():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT',
                                                             'HLA_BENCH_REHEARSE')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--train-steps', '2', '--batch', '8', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--train-steps', '2', '--batch', '8', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout[-2000:]                      # ONE line, from rank 0
@@ -2079,7 +2079,7 @@ def test_bench_eight_rank_rehearsal_of_configs2_shard_arithmetic():
                                                             'HLA_BENCH_REHEARSE')}
     env['OMP_NUM_THREADS'] = '4'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1',
-                        '--train-steps', '1', '--train-precision', 'bf16', '--batch', '4', '--no-cpu-baseline', '--no-kernel-timing'],
+                        '--full', '--train-steps', '1', '--train-precision', 'bf16', '--batch', '4', '--no-cpu-baseline', '--no-kernel-timing'],
                        env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -2109,7 +2109,7 @@ def test_bench_single_rank_through_rccl():
                                                             'HLA_BENCH_REHEARSE')}
     env['HLA_BENCH_FORCE_DIST'] = '1'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-                        '--train-steps', '2', '--batch', '8', '--no-cpu-baseline', '--no-extra-legs'],
+                        '--full', '--train-steps', '2', '--batch', '8', '--no-cpu-baseline', '--no-extra-legs'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -2130,6 +2130,27 @@ def test_bench_single_rank_through_rccl():
     assert 0.0 <= sb['allreduce_exposed_ms'] < 5.0 and len(sb['allreduce_buckets']) == 2, sb
     assert all(abs(b['bytes'] - 9.89e6) < 0.02e6 for b in sb['allreduce_buckets']), sb['allreduce_buckets']
     assert sb['allreduce_buckets'][0]['issued_ms_before_backward_end'] > sb['allreduce_buckets'][1]['issued_ms_before_backward_end'] >= 0.0, sb
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and prints only the headline fields (no extra legs: those are --full's);
+    --dump-outputs writes the last timed step's (shift_lat, shift_lon, theta) for every pair of the batch, float32 and finite."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'HLA_BENCH_FORCE_DIST', 'HLA_BENCH_REHEARSE')}
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+                        '--dump-outputs', str(tmp_path / 'out')], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j['steps'] == 3 and j['warmup'] == 1 and j['unit'] == 'pairs/s' and j['higher_is_better'] is True and j['dtype'] == 'bf16'
+    assert j['value'] > 0 and abs(j['value'] - 4 * 1e3 / j['ms_per_step']) < 0.01 * j['value'], j
+    assert not {'roofline', 'kernels', 'train', 'by_precision', 'secondary', 'cpu_baseline'} & set(j), sorted(j)
+    assert sorted(os.listdir(tmp_path / 'out')) == ['shift_lat.npy', 'shift_lon.npy', 'theta.npy']
+    for n in ('shift_lat', 'shift_lon', 'theta'):
+        x = np.load(str(tmp_path / 'out' / (n + '.npy')))
+        assert x.shape == (4,) and x.dtype == np.float32 and np.isfinite(x).all(), (n, x)
 
 
 def test_grad_sync_over_rccl_leaves_one_rank_gradients_unchanged():

@@ -2,10 +2,11 @@
 # Run ON the GPU box: round-6 first look -- the default bench line, which host op launches what in a training step, and the
 # training timeline (with the inter-step gap) in both training modes.
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-timeout 900 python bench.py > gpurun_out/r6_bench.json 2> gpurun_out/r6_bench.err; echo bench rc $?
-python - <<'PY'
-import json
-r = json.load(open('gpurun_out/r6_bench.json'))
+OUT=${OUT:-results}; mkdir -p $OUT     # where this script writes its results
+timeout 900 python bench.py --full > $OUT/r6_bench.json 2> $OUT/r6_bench.err; echo bench rc $?
+python - "$OUT/r6_bench.json" <<'PY'
+import json, sys
+r = json.load(open(sys.argv[1]))
 print('value', r['value'], r['ms_per_step'], 'frac', r['roofline']['frac'])
 print('matched', r.get('matched_accuracy'))
 t = r['train']; print('train', t.get('value'), t.get('ms_per_step'), t.get('blocks_ms_per_step'), t.get('roofline', {}).get('frac'))

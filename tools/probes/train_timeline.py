@@ -1,7 +1,7 @@
 """Timeline of ONE training step from a rocprofv3 kernel trace: which kernel ran when, on which stream (queue).
 
     cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $REPO/gpurun_out/tl -- python $REPO/bench.py --steps 1 --warmup 0 \
-        --no-cpu-baseline --no-kernel-timing --no-extra-legs --precision fp16x3 --train-precision fp16x3 --train-steps 2
+        --full --no-cpu-baseline --no-kernel-timing --no-extra-legs --precision fp16x3 --train-precision fp16x3 --train-steps 2
     cd $REPO && python tools/probes/train_timeline.py gpurun_out/tl > gpurun_out/timeline.txt
 
 Prints the LAST complete step (from the last conv02 pair's first launch back to the previous one): per launch the start offset,
