@@ -119,18 +119,29 @@ def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True,
         if not (defer_norm and not save_for_backward and L == 3 and dt in (_lib.HLA_BF16, _lib.HLA_F16)):
             raise ValueError("feat16 needs precision 'bf16' / 'fp16', defer_norm=True, level 3 and no save_for_backward")
         fdt = torch.float16         # (also in bf16 mode: the raw maps are written as fp16, saturating)
+    fold = bool(getattr(module, 'folded', False))
+    if fold:
+        if feat16 or first_row8:
+            raise ValueError('VGGUnet_G2S: feat16 / first_row8 do not apply to the folded maps')
+        if W % 16:
+            raise ValueError(f'VGGUnet_G2S folds [h,w] -> [2h,w/2] down to the W/8-wide map: W must be a multiple of 16, got {W}')
+
+    def hw(l, folded):      # map l: [H/2^(3-l), W/2^(3-l)], or the fold of it (VGG.py:278-310; the same memory in NHWC)
+        h, w = H >> (3 - l), W >> (3 - l)
+        return (2 * h, w // 2) if folded else (h, w)
+
     # level 4: x24 is stored with 64 channels, the 16 real ones first, zeros behind them (see include/hla.h)
-    feats = [torch.empty(B, H >> (3 - l), W >> (3 - l), 64 if l == 3 else _CH[l], device=x.device, dtype=fdt)
-             for l in range(L)]
-    confs = [torch.empty(B, H >> (3 - l), W >> (3 - l), device=x.device, dtype=torch.float32) if want_conf else None
+    feats = [torch.empty(B, *hw(l, fold), 64 if l == 3 else _CH[l], device=x.device, dtype=fdt) for l in range(L)]
+    # (the folded extractor's conf0 reads the unfolded x15, VGG.py:322)
+    confs = [torch.empty(B, *hw(l, fold and l > 0), device=x.device, dtype=torch.float32) if want_conf else None
              for l in range(L)]
     inv_norm = torch.empty(L, B, device=x.device, dtype=torch.float64)
     fp = (C.c_void_p * 4)(*([f.data_ptr() for f in feats] + [0] * (4 - L)))
     cp = (C.c_void_p * 4)(*([(c.data_ptr() if c is not None else 0) for c in confs] + [0] * (4 - L)))
-    nbytes = lib.hla_vgg_workspace_bytes(B, H, W, L, dt)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     flags = (_lib.HLA_VGG_WANT_CONF if want_conf else 0) | (_lib.HLA_VGG_DEFER_NORM if defer_norm else 0) | \
-            (_lib.HLA_VGG_FEAT16 if feat16 else 0)
+            (_lib.HLA_VGG_FEAT16 if feat16 else 0) | (_lib.HLA_VGG_FOLD_DECODER if fold else 0)
+    nbytes = lib.hla_vgg_workspace_bytes_flags(B, H, W, L, dt, flags) if fold else lib.hla_vgg_workspace_bytes(B, H, W, L, dt)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     if save_for_backward:
         if not defer_norm:
             raise ValueError('save_for_backward needs defer_norm=True (the backward works on the raw maps)')
@@ -218,17 +229,22 @@ def vgg_backward_nhwc(module: 'VGGUnet', ctx: dict, d_feats, confs=None, d_confs
     dfs = [d.contiguous().float() for d in d_feats]
     fp = (C.c_void_p * 4)(*([f.data_ptr() for f in ctx['feats']] + [0] * (4 - L)))
     dp = (C.c_void_p * 4)(*([d.data_ptr() for d in dfs] + [0] * (4 - L)))
-    nbytes = lib.hla_vgg_bwd_workspace_bytes(B, H, W, L, dt)
+    fold = bool(getattr(module, 'folded', False))
+    nbytes = lib.hla_vgg_bwd_workspace_bytes_flags(B, H, W, L, dt, _lib.HLA_VGG_BWD_FOLD_DECODER) if fold \
+        else lib.hla_vgg_bwd_workspace_bytes(B, H, W, L, dt)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     rc = lib.hla_vgg_backward(_lib.ptr(x), ctx.get('x_plane', 0), C.byref(prm), _lib.ptr(cache['buf']), _lib.ptr(ctx['ws']), fp, _lib.ptr(ctx['inv_norm']),
                               dp, cp, dcp, C.byref(gs), _lib.ptr(ws), nbytes, B, H, W, L, dt,
                               (_lib.HLA_VGG_BWD_SCALE_INVARIANT if scale_invariant else 0)
                               | (_lib.HLA_VGG_BWD_DENSE if dense else 0)
                               | (_lib.HLA_VGG_BWD_WGRAD_TWO_PHASE if int(wgrad_two_phase) & 1 else 0)
-                              | (_lib.HLA_VGG_BWD_WGRAD0_UNFUSED if int(wgrad_two_phase) & 2 else 0),
+                              | (_lib.HLA_VGG_BWD_WGRAD0_UNFUSED if int(wgrad_two_phase) & 2 else 0)
+                              | (_lib.HLA_VGG_BWD_FOLD_DECODER if getattr(module, 'folded', False) else 0),
                               int(first_row8), _lib.stream_ptr())
     _lib.check(rc, 'hla_vgg_backward')
-    if stats is not None:
+    if stats is not None and fold:
+        stats['live_tiles'], stats['total_tiles'] = 0, 0      # the folded backward always takes the dense walk
+    elif stats is not None:
         torch.cuda.current_stream().synchronize()
         live, total = C.c_longlong(0), C.c_longlong(0)
         _lib.check(lib.hla_vgg_backward_live_tiles(_lib.ptr(ws), B, H, W, L, dt, C.byref(live), C.byref(total)),
@@ -278,6 +294,20 @@ class VGGUnet(nn.Module):
         # NCHW-shaped views over the NHWC storage
         view = lambda i: (feats[i][..., :_CH[i]] if i == 3 else feats[i]).permute(0, 3, 1, 2)   # x24: 16 real of 64 stored channels
         return [view(i) for i in sel], [confs[i].unsqueeze(1) for i in sel]
+
+
+class VGGUnet_G2S(VGGUnet):
+    """The ground extractor of ``LM_G2SP(proj='nn')`` (``VGG.py:206-345``): VGGUnet whose maps behind the encoder are FOLDED,
+    ``[H', W'] -> [2H', W'/2]`` (a 256 x 1024 image gives 64 x 64 / 128 x 128 / 256 x 256 maps, the satellite maps' sizes).  The
+    reference folds with an NCHW ``reshape``; on the channels-last storage used here that reshape is the identity on memory, so
+    the encoder is VGGUnet's and the decoder, ``conf1..3`` and the L2 norms run on the same buffers with the folded geometry
+    (HLA_VGG_FOLD_DECODER).  Same parameter names and state-dict order as the reference; ``forward(x)`` returns
+    ``[x15_, x18, x21(, x24)]`` folded and ``[c0, c1, c2(, c3)]`` with ``c0`` at ``[B,1,H/8,W/8]`` (it reads the unfolded x15,
+    ``VGG.py:322``) and the rest folded.  W must be a multiple of 16."""
+    folded = True
+
+    def __init__(self, level, precision: str = 'fp32'):
+        super().__init__(level, precision=precision)
 
 
 class _VggFn(torch.autograd.Function):

@@ -1,7 +1,9 @@
-"""``LM_G2SP`` -- the ground->satellite variant of the KITTI model (``models_kitti.py:22-499``, ``proj='geo'``): the
+"""``LM_G2SP`` -- the ground->satellite variant of the KITTI model (``models_kitti.py:22-499``).  ``proj='geo'``: the
 ground feature map is projected onto the satellite plane with the per-sample camera intrinsics and the LM update
-runs on the satellite grid.  Same module surface as the reference (ctor argument, ``forward(sat_map, grd_img_left,
-left_camera_k, gt_shift_u, gt_shift_v, gt_heading, mode, ...)``, state-dict keys).  Under autograd the forward runs
+runs on the satellite grid.  ``proj='nn'``: the ground branch is ``VGGUnet_G2S`` (folded maps of the satellite maps' sizes)
+and the projection is the in-plane similarity warp of ``inplane_grd_to_map`` (289-332); ``left_camera_k`` is accepted and not
+read.  Same module surface as the reference (ctor argument, ``forward(sat_map, grd_img_left, left_camera_k, gt_shift_u,
+gt_shift_v, gt_heading, mode, ...)``, state-dict keys).  Under autograd the forward runs
 inside one ``torch.autograd.Function`` whose backward is ``hla_g2s_lm_solve_bwd`` + ``hla_vgg_backward`` x 2."""
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ from torch import nn
 
 from . import _lib, utils
 from ._s2gp import loss_from_trace, loss_func, raise_like_reference  # noqa: F401
-from .VGG import VGGUnet, vgg_backward_nhwc, vgg_forward_nhwc
+from .VGG import VGGUnet, VGGUnet_G2S, vgg_backward_nhwc, vgg_forward_nhwc
 
 
 class LM_G2SP(nn.Module):
@@ -25,11 +27,16 @@ class LM_G2SP(nn.Module):
         self.loss_method = args.loss_method
         if args.level not in (3, 4):
             raise NotImplementedError('args.level must be 3 (x15, x18, x21) or 4 (+ x24)')
-        if getattr(args, 'proj', 'geo') != 'geo':
-            raise NotImplementedError("only proj='geo' is built (proj='nn' needs VGGUnet_G2S, VGG.py:206-350)")
+        self.proj = getattr(args, 'proj', 'geo')
+        if self.proj not in ('geo', 'nn'):
+            raise NotImplementedError(f"proj={self.proj!r}: 'geo' and 'nn' are built (the reference's LM_G2SP has no other projection; 'polar' is out of scope)")
+        if self.proj == 'nn' and args.using_weight:
+            # the reference samples the UNFOLDED c0 ([H/8,W/8]) with the folded level-0 grid (models_kitti.py:298): defined, but
+            # plainly unintended -- refused rather than reproduced or silently replaced
+            raise NotImplementedError('using_weight with proj=nn')
         precision = getattr(args, 'precision', 'fp32')
         self.SatFeatureNet = VGGUnet(self.level, precision=precision)
-        self.GrdFeatureNet = VGGUnet(self.level, precision=precision)
+        self.GrdFeatureNet = (VGGUnet_G2S if self.proj == 'nn' else VGGUnet)(self.level, precision=precision)         # 35-38
         self.damping = nn.Parameter(args.damping * torch.ones(size=(1, 3), dtype=torch.float32))   # models_kitti.py:41
         self.meters_per_pixel = [utils.get_meter_per_pixel() * (2 ** (3 - l)) for l in range(4)]
         self.last_trace = None
@@ -43,6 +50,7 @@ class LM_G2SP(nn.Module):
         cfg = _lib.S2GConfig()
         cfg.ford, cfg.n_levels, cfg.n_iters, cfg.level_first = 0, L, self.N_iters, 0
         cfg.using_weight, cfg.use_hessian, cfg.dof = (1 if self.using_weight else 0), 0, 3
+        cfg.proj = 1 if self.proj == 'nn' else 0
         cfg.shift_range_lat, cfg.shift_range_lon = float(a.shift_range_lat), float(a.shift_range_lon)
         cfg.rotation_range = float(a.rotation_range)
         lam = self.damping.detach().double().reshape(-1).tolist() if getattr(a, 'train_damping', 0) else [float(a.damping)] * 3
@@ -62,6 +70,8 @@ class LM_G2SP(nn.Module):
             lv[l].A, lv[l].h, lv[l].w, lv[l].C, lv[l].row0, lv[l].grd_row_skip = A, g.shape[1], g.shape[2], Cn, 0, 0
             lv[l].meter_per_pixel = utils.get_meter_per_pixel() * utils.get_process_satmap_sidelength() / A   # 71-72
             lv[l].centre = float(A // 2)
+        if self.proj == 'nn':            # the in-plane warp has no camera in it
+            return cfg, lv, None
         K = camera_k.to(dev).float().contiguous()
         if tuple(K.shape) != (B, 3, 3):
             raise ValueError(f'left_camera_k must be [B,3,3], got {tuple(K.shape)}')
@@ -82,7 +92,8 @@ class LM_G2SP(nn.Module):
         nbytes = lib.hla_g2s_workspace_bytes(C.byref(cfg), lv, B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         p0 = init_pose.to(dev).float().contiguous() if init_pose is not None else None
-        rc = lib.hla_g2s_lm_solve(C.byref(cfg), lv, _lib.ptr(K), int(ori_hw[0]), int(ori_hw[1]), _lib.ptr(p0), _lib.ptr(trace),
+        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))      # (the in-plane warp reads neither)
+        rc = lib.hla_g2s_lm_solve(C.byref(cfg), lv, _lib.ptr(K), oh, ow, _lib.ptr(p0), _lib.ptr(trace),
                                   _lib.ptr(neq), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
         _lib.check(rc, 'hla_g2s_lm_solve')
         # the reference's run-time errors (see _s2gp.raise_like_reference).  This direction has no norms among its sums: a
@@ -115,7 +126,8 @@ class LM_G2SP(nn.Module):
         nbytes = lib.hla_g2s_bwd_workspace_bytes(C.byref(cfg), lv, B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         p0 = init_pose.to(dev).float().contiguous() if init_pose is not None else None
-        rc = lib.hla_g2s_lm_solve_bwd(C.byref(cfg), lv, gr, _lib.ptr(K), int(ori_hw[0]), int(ori_hw[1]), _lib.ptr(p0),
+        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))
+        rc = lib.hla_g2s_lm_solve_bwd(C.byref(cfg), lv, gr, _lib.ptr(K), oh, ow, _lib.ptr(p0),
                                       _lib.ptr(trace), _lib.ptr(normal_eq), _lib.ptr(dtr), _lib.ptr(d_lambda), _lib.ptr(ws),
                                       nbytes, B, _lib.stream_ptr())
         _lib.check(rc, 'hla_g2s_lm_solve_bwd')
@@ -130,6 +142,12 @@ class LM_G2SP(nn.Module):
                 or sat_map.shape[2] != sat_map.shape[3]:
             raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W], got {tuple(sat_map.shape)} and '
                              f'{tuple(grd_img_left.shape)}')
+        if self.proj == 'nn':
+            A, (H, W) = sat_map.shape[-1], grd_img_left.shape[-2:]
+            if 2 * H != A or W != 2 * A:
+                raise ValueError(f"proj='nn' warps the FOLDED ground maps ([H,W] -> [2H,W/2]) in the satellite maps' plane, so they must "
+                                 f'be the satellite maps\' size: grd_img must be [B,3,A/2,2A] = [B,3,{A // 2},{2 * A}] for sat_map '
+                                 f'[B,3,{A},{A}], got {tuple(grd_img_left.shape)}')
         want_conf = bool(self.using_weight) or mode == 'train'
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             names = [n for n, _ in self.named_parameters()]

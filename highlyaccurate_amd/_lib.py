@@ -15,11 +15,13 @@ LIB_PATH = os.environ.get('HLA_LIB') or os.path.join(HERE, 'libhla.so')   # HLA_
 
 HLA_F32, HLA_BF16, HLA_F16, HLA_F16X3 = 0, 1, 2, 3
 HLA_VGG_WANT_CONF, HLA_VGG_DEFER_NORM, HLA_VGG_SAVE_FOR_BACKWARD, HLA_VGG_FEAT16 = 1, 2, 4, 8
+HLA_VGG_FOLD_DECODER = 16
 HLA_VGG_BWD_SCALE_INVARIANT = 1
 HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
-ABI_VERSION = 21
+HLA_VGG_BWD_FOLD_DECODER = 16
+ABI_VERSION = 22
 
 
 class HlaError(RuntimeError):
@@ -43,7 +45,7 @@ class S2GConfig(C.Structure):
                 ('shift_range_lat', C.c_double), ('shift_range_lon', C.c_double), ('rotation_range', C.c_double),
                 ('damping', C.c_double * 3), ('keep', C.c_void_p), ('keep_stride', C.c_size_t),
                 ('optimizer', C.c_int), ('beta1', C.c_double), ('beta2', C.c_double), ('count_in_view', C.c_int),
-                ('grd_grad_overwrite', C.c_int), ('deterministic', C.c_int)]
+                ('grd_grad_overwrite', C.c_int), ('deterministic', C.c_int), ('proj', C.c_int)]
 
 
 class FillRegion(C.Structure):
@@ -122,6 +124,8 @@ def load() -> C.CDLL:
     lib.hla_source_hash.restype = C.c_char_p
     lib.hla_vgg_workspace_bytes.restype = sz
     lib.hla_vgg_workspace_bytes.argtypes = [i, i, i, i, i]
+    lib.hla_vgg_workspace_bytes_flags.restype = sz
+    lib.hla_vgg_workspace_bytes_flags.argtypes = [i, i, i, i, i, i]
     lib.hla_vgg_forward.restype = i
     lib.hla_vgg_forward.argtypes = [vp, sz, C.POINTER(VggParams), vp, C.POINTER(vp), C.POINTER(vp), vp, vp, sz,
                                     i, i, i, i, i, i, i, vp]
@@ -135,6 +139,8 @@ def load() -> C.CDLL:
     lib.hla_vgg_pack_weights_T.argtypes = [C.POINTER(VggParams), vp, i, vp]
     lib.hla_vgg_bwd_workspace_bytes.restype = sz
     lib.hla_vgg_bwd_workspace_bytes.argtypes = [i, i, i, i, i]
+    lib.hla_vgg_bwd_workspace_bytes_flags.restype = sz
+    lib.hla_vgg_bwd_workspace_bytes_flags.argtypes = [i, i, i, i, i, i]
     lib.hla_vgg_backward_live_tiles.restype = i
     lib.hla_vgg_backward_live_tiles.argtypes = [vp, i, i, i, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.hla_vgg_backward.restype = i

@@ -6,6 +6,10 @@
 // always 3-DoF, optional weight = the PROJECTED ground confidence.
 //   g2s_accum<C>  grid (tiles x samples), lanes spread over channels: 12 sums  H(6), J'W f (3), J'W s (3)
 //   g2s_solve     one wave per sample: fixed-order fp64 reduction, damped 3x3 solve, next step's 21 coefficients
+// cfg->proj == 1 (proj == 'nn', inplane_grd_to_map 289-332): the projection is a rotation about the map centre plus a shift,
+// so a pixel costs four FMAs, two Jacobian columns are constants of the step and EVERY pixel of every level takes part:
+//   g2s_ip_accum<C>  its own accumulate kernel (smaller pixel record, constants folded in after the reduction)
+// The solve kernels and the backward's element loop are shared; they branch on the projection outside the hot loops.
 #include "lm_common.h"
 
 #define G2S_COEF_N 24   // a[3] b[3] c[3]  (uv1_k = a_k*v_c + b_k*u_c + c_k)   dx[3] dy[3]   dth_a[3] dth_b[3]   pad[3]
@@ -27,8 +31,61 @@ struct G2sAccumArgs {
   int A, h, w, ctr, npix, TP, nt, B, xcd_affine;
 };
 
-template <int C, bool USE_W>
+// in-plane coefficients (proj == 1): cos, sin, T_u + A/2, T_v + A/2, d(u)/d(shift_u), d(v)/d(shift_v), k = rot*pi/180, A/2
+enum { IP_C = 0, IP_S, IP_TU, IP_TV, IP_JU, IP_JV, IP_K, IP_HALF };
+
+struct __attribute__((aligned(16))) G2sIpPix {
+  int off, dxo, dyo;
+  float wx0, wx1, wy0, wy1;
+  float j2u, j2v;               // d(uv)/d(heading) = k dR/dtheta (p - A/2)
+  float pad0, pad1, pad2;
+};
+
+// (u, v) of satellite pixel (row, col) under the in-plane warp and its heading column (models_kitti.py:303-324)
+__device__ __forceinline__ void g2s_ip_uv(const double* cf, int row, int col, double& u, double& v, double& j2u, double& j2v) {
+  const double uc = (double)col - cf[IP_HALF], vc = (double)row - cf[IP_HALF];
+  const double ru = cf[IP_C] * uc - cf[IP_S] * vc, rv = cf[IP_S] * uc + cf[IP_C] * vc;
+  u = ru + cf[IP_TU]; v = rv + cf[IP_TV];
+  j2u = -cf[IP_K] * rv; j2v = cf[IP_K] * ru;       // dR/dtheta (uc, vc) = (-s uc - c vc, c uc - s vc) = (-rv, ru)
+}
+
+template <int C>
+__device__ __forceinline__ G2sIpPix g2s_ip_pixel(const double* cf, int row, int col, int h, int w) {
+  double u, v, j2u, j2v;
+  g2s_ip_uv(cf, row, col, u, v, j2u, j2v);
+  const double limx = (double)(w - 1), limy = (double)(h - 1);
+  const bool inb = (u >= 0.0) && (u <= limx) && (v >= 0.0) && (v <= limy);  // jacobian.py:168-170
+  G2sIpPix o;
+  o.pad0 = o.pad1 = o.pad2 = 0.f;
+  if (inb) {
+    const double x0 = floor(u), y0 = floor(v);
+    const double x1 = fmin(x0 + 1.0, limx), y1 = fmin(y0 + 1.0, limy);
+    o.wx0 = (float)(x1 - u); o.wx1 = (float)(u - x0);
+    o.wy0 = (float)(y1 - v); o.wy1 = (float)(v - y0);
+    const int ix0 = (int)x0, iy0 = (int)y0;
+    o.off = (iy0 * w + ix0) * C;
+    o.dxo = ((int)x1 - ix0) * C;
+    o.dyo = ((int)y1 - iy0) * w * C;
+    o.j2u = (float)j2u; o.j2v = (float)j2v;
+  } else {
+    o.wx0 = o.wx1 = o.wy0 = o.wy1 = 0.f;
+    o.off = o.dxo = o.dyo = 0;
+    o.j2u = o.j2v = 0.f;
+  }
+  return o;
+}
+
+template <int C, bool USE_W, int PROJ = 0>
 __device__ __forceinline__ G2sPix g2s_pixel(const double* cf, int row, int col, int ctr, int h, int w, const float* conf) {
+  if constexpr (PROJ == 1) {      // the backward's element loop is shared: the in-plane pixel in the general record
+    const G2sIpPix q = g2s_ip_pixel<C>(cf, row, col, h, w);
+    const bool inb = (q.wx0 + q.wx1 + q.wy0 + q.wy1) != 0.f;
+    G2sPix o;
+    o.off = q.off; o.dxo = q.dxo; o.dyo = q.dyo; o.wx0 = q.wx0; o.wx1 = q.wx1; o.wy0 = q.wy0; o.wy1 = q.wy1;
+    o.j0u = inb ? (float)cf[IP_JU] : 0.f; o.j0v = 0.f; o.j1u = 0.f; o.j1v = inb ? (float)cf[IP_JV] : 0.f;
+    o.j2u = q.j2u; o.j2v = q.j2v; o.wt = 1.f; o.pad0 = o.pad1 = 0.f;
+    return o;
+  }
   const double vc = (double)(row - ctr), uc = (double)(col - ctr);
   const double q0 = cf[0] * vc + cf[3] * uc + cf[6];
   const double q1 = cf[1] * vc + cf[4] * uc + cf[7];
@@ -136,8 +193,91 @@ __global__ __launch_bounds__(256) void g2s_accum(G2sAccumArgs a) {
   }
 }
 
+// The in-plane specialisation.  d(uv)/d(shift_u) = (ju, 0) and d(uv)/d(shift_v) = (0, jv) are constants of the step, so the
+// loop accumulates the products of (dsx, dsy, J2) and the constants are applied once per block, after the reduction:
+//   H00 = ju^2 S(dsx dsx)  H01 = ju jv S(dsx dsy)  H02 = ju S(dsx J2)  H11 = jv^2 S(dsy dsy)  H12 = jv S(dsy J2)  H22 = S(J2 J2)
+// A tile is a run of consecutive satellite pixels; under the (small) rotation their taps are neighbouring texels of the ground
+// map, lanes run over channels, so every tap is one contiguous 16 B x (C/4 lanes) read and the four taps of neighbouring pixels
+// overlap in L1 / L2.  Out-of-map pixels carry zero weights and offset 0 (reads stay inside the sample's map).
+template <int C>
+__global__ __launch_bounds__(256) void g2s_ip_accum(G2sAccumArgs a) {
+  __shared__ G2sIpPix pp[MAX_TP];
+  __shared__ float red[4][12];
+  int b, tile;
+  if (!lm_block_map(a.xcd_affine, a.nt, a.B, b, tile)) return;
+  const int t = threadIdx.x;
+  const int p0 = tile * a.TP;
+  const int np = min(a.TP, a.npix - p0);
+  const double* cf = a.coef + (size_t)b * G2S_COEF_N;
+  if (t < np) {
+    const int p = p0 + t;
+    pp[t] = g2s_ip_pixel<C>(cf, p / a.A, p % a.A, a.h, a.w);
+  }
+  __syncthreads();
+
+  constexpr int LPP = C / 4, PPW = 64 / LPP;
+  const int lane = t & 63, wave = t >> 6;
+  const int sub = lane / LPP, cl = (lane % LPP) * 4;
+  const float* srcb = a.src + (size_t)b * a.h * a.w * C + cl;
+  const float* fixb = a.fix + ((size_t)b * a.npix + p0) * C + cl;
+  float sxx = 0, sxy = 0, sx2 = 0, syy = 0, sy2 = 0, s22 = 0, xf = 0, yf = 0, tf = 0, xg = 0, yg = 0, tg = 0;
+#pragma unroll 2
+  for (int i = wave * PPW + sub; i < np; i += 4 * PPW) {
+    const G2sIpPix P = pp[i];
+    const float4 t00 = *(const float4*)(srcb + P.off);
+    const float4 t01 = *(const float4*)(srcb + P.off + P.dxo);
+    const float4 t10 = *(const float4*)(srcb + P.off + P.dyo);
+    const float4 t11 = *(const float4*)(srcb + P.off + P.dyo + P.dxo);
+    const float4 gg = *(const float4*)(fixb + (size_t)i * C);
+    const float a00[4] = {t00.x, t00.y, t00.z, t00.w}, a01[4] = {t01.x, t01.y, t01.z, t01.w};
+    const float a10[4] = {t10.x, t10.y, t10.z, t10.w}, a11[4] = {t11.x, t11.y, t11.z, t11.w};
+    const float ag[4] = {gg.x, gg.y, gg.z, gg.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float top = P.wx0 * a00[e] + P.wx1 * a01[e];
+      const float bot = P.wx0 * a10[e] + P.wx1 * a11[e];
+      const float f = P.wy0 * top + P.wy1 * bot;                       // warped ground feature
+      const float dsy = bot - top;
+      const float dsx = P.wy0 * (a01[e] - a00[e]) + P.wy1 * (a11[e] - a10[e]);
+      const float J2 = dsx * P.j2u + dsy * P.j2v;
+      sxx += dsx * dsx; sxy += dsx * dsy; sx2 += dsx * J2; syy += dsy * dsy; sy2 += dsy * J2; s22 += J2 * J2;
+      xf += dsx * f; yf += dsy * f; tf += J2 * f;
+      xg += dsx * ag[e]; yg += dsy * ag[e]; tg += J2 * ag[e];
+    }
+  }
+  float acc[12] = {sxx, sxy, sx2, syy, sy2, s22, xf, yf, tf, xg, yg, tg};
+#pragma unroll
+  for (int k = 0; k < 12; ++k) acc[k] = wave_sum_f32(acc[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) red[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (t < PART_N) {
+    double v = 0.0;
+    if (t < 12) {
+      const double ju = cf[IP_JU], jv = cf[IP_JV];
+      const double sc = (t == 0) ? ju * ju : (t == 1) ? ju * jv : (t == 3) ? jv * jv
+                        : (t == 2 || t == 6 || t == 9) ? ju : (t == 4 || t == 7 || t == 10) ? jv : 1.0;
+      v = sc * (((double)red[0][t] + (double)red[1][t]) + ((double)red[2][t] + (double)red[3][t]));
+    }
+    a.part[((size_t)b * a.nt + tile) * PART_N + t] = v;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
-struct G2sGeom { double lat, lon, rot, mpp, sx, sy; };   // sx, sy: intrinsics scale to the level's ground map (111-113)
+struct G2sGeom { double lat, lon, rot, mpp, sx, sy, half; int proj; };   // sx, sy: intrinsics scale to the level's ground map (111-113)
+
+// proj == 1: pose -> the in-plane coefficients of the level the next step runs on (models_kitti.py:291-302)
+__device__ static inline void g2s_ip_coefficients(const G2sGeom& G, double su, double sv, double th, double* cf) {
+  const double k = G.rot / 180.0 * 3.14159265358979323846;
+  const double ang = th * k;
+  cf[IP_C] = cos(ang); cf[IP_S] = sin(ang);
+  cf[IP_JU] = -G.lon / G.mpp; cf[IP_JV] = G.lat / G.mpp;
+  cf[IP_TU] = cf[IP_JU] * su + G.half; cf[IP_TV] = cf[IP_JV] * sv + G.half;
+  cf[IP_K] = k; cf[IP_HALF] = G.half;
+  for (int i = IP_HALF + 1; i < G2S_COEF_N; ++i) cf[i] = 0.0;
+}
 
 // pose -> the 21 coefficients of the level the next step runs on (models_kitti.py:91-141)
 __device__ static inline void g2s_coefficients(const G2sGeom& G, double su, double sv, double th, const float* K9, double* cf) {
@@ -202,7 +342,10 @@ __global__ __launch_bounds__(64) void g2s_solve(G2sSolveArgs a) {
       tr[0] = su; tr[1] = sv; tr[2] = th;
     }
   }
-  if (a.coef && lane == 0) g2s_coefficients(a.next, su, sv, th, a.camera_k + (size_t)b * 9, a.coef + (size_t)b * G2S_COEF_N);
+  if (a.coef && lane == 0) {
+    if (a.next.proj) g2s_ip_coefficients(a.next, su, sv, th, a.coef + (size_t)b * G2S_COEF_N);
+    else g2s_coefficients(a.next, su, sv, th, a.camera_k + (size_t)b * 9, a.coef + (size_t)b * G2S_COEF_N);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -233,22 +376,44 @@ static void launch_g2s(int C, dim3 grid, hipStream_t st, const G2sAccumArgs& a) 
   }
 }
 
+static void launch_g2s_ip(int C, dim3 grid, hipStream_t st, const G2sAccumArgs& a) {
+  switch (C) {
+    case 256: hipLaunchKernelGGL((g2s_ip_accum<256>), grid, dim3(256), 0, st, a); break;
+    case 128: hipLaunchKernelGGL((g2s_ip_accum<128>), grid, dim3(256), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((g2s_ip_accum<64>), grid, dim3(256), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((g2s_ip_accum<16>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
+// what both entry points require of cfg->proj and of the maps it selects
+static int g2s_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_level* lv, const float* camera_k, int ori_h,
+                        int ori_w) {
+  HLA_REQUIRE(cfg->proj == 0 || cfg->proj == 1, "%s: cfg->proj must be 0 (geo) or 1 (in-plane), got %d", who, cfg->proj);
+  if (cfg->proj == 0) HLA_REQUIRE(camera_k && ori_h > 0 && ori_w > 0, "%s: proj 0 needs camera_k and the ground image size", who);
+  else HLA_REQUIRE(!cfg->using_weight, "%s: proj 1 has no weighted variant (using_weight must be 0)", who);
+  for (int l = 0; l < cfg->n_levels; ++l) {
+    const int C = lv[l].C;
+    HLA_REQUIRE(C == 256 || C == 128 || C == 64 || (cfg->proj == 1 && C == 16), "%s: unsupported channel count %d", who, C);
+    HLA_REQUIRE(lv[l].A > 0 && lv[l].h > 0 && lv[l].w > 0 && lv[l].meter_per_pixel > 0.0, "%s: level %d: bad geometry", who, l);
+    HLA_REQUIRE((size_t)lv[l].h * lv[l].w * C < (1u << 31), "%s: ground map too large", who);
+    HLA_REQUIRE((size_t)lv[l].A * lv[l].A < (1u << 30), "%s: satellite map too large", who);
+  }
+  return HLA_OK;
+}
+
 extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* lv, const float* camera_k, int ori_h,
                                 int ori_w, const float* pose0, float* trace, double* normal_eq, void* workspace,
                                 size_t workspace_bytes, int B, hla_stream_t stream) {
-  HLA_REQUIRE(cfg && lv && camera_k && trace && workspace, "hla_g2s_lm_solve: null argument");
-  HLA_REQUIRE(B > 0 && cfg->n_levels >= 1 && cfg->n_levels <= 4 && cfg->n_iters >= 1 && ori_h > 0 && ori_w > 0,
-              "hla_g2s_lm_solve: bad sizes");
+  HLA_REQUIRE(cfg && lv && trace && workspace, "hla_g2s_lm_solve: null argument");
+  HLA_REQUIRE(B > 0 && cfg->n_levels >= 1 && cfg->n_levels <= 4 && cfg->n_iters >= 1, "hla_g2s_lm_solve: bad sizes");
   HLA_REQUIRE(!cfg->ford && cfg->dof == 3 && !cfg->level_first && !cfg->use_hessian,
               "hla_g2s_lm_solve: LM_G2SP is KITTI-only, 3-DoF, iteration-first, identity damping (models_kitti.py:333-379)");
+  if (const int rc = g2s_validate("hla_g2s_lm_solve", cfg, lv, camera_k, ori_h, ori_w)) return rc;
   for (int l = 0; l < cfg->n_levels; ++l) {
-    const int C = lv[l].C;
-    HLA_REQUIRE(C == 256 || C == 128 || C == 64, "hla_g2s_lm_solve: unsupported channel count %d", C);
     HLA_REQUIRE(lv[l].sat_feat && lv[l].grd_feat, "hla_g2s_lm_solve: level %d has null maps", l);
     HLA_REQUIRE(lv[l].feat_dtype == HLA_F32, "hla_g2s_lm_solve: level %d: fp32 feature maps only", l);
     HLA_REQUIRE(!cfg->using_weight || lv[l].grd_conf, "hla_g2s_lm_solve: using_weight needs grd_conf");
     HLA_REQUIRE(lv[l].grd_row_skip == 0, "hla_g2s_lm_solve: the whole ground map is sampled (grd_row_skip must be 0)");
-    HLA_REQUIRE((size_t)lv[l].h * lv[l].w * C < (1u << 31), "hla_g2s_lm_solve: ground map too large");
   }
   size_t oc, op, opart;
   const size_t need = g2s_layout(cfg, lv, B, &oc, &op, &opart);
@@ -268,7 +433,8 @@ extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   auto geom = [&](int l) {
     G2sGeom g{};
     g.lat = cfg->shift_range_lat; g.lon = cfg->shift_range_lon; g.rot = cfg->rotation_range;
-    g.mpp = lv[l].meter_per_pixel; g.sx = (double)lv[l].w / ori_w; g.sy = (double)lv[l].h / ori_h;
+    g.mpp = lv[l].meter_per_pixel; g.proj = cfg->proj; g.half = 0.5 * lv[l].A;      // satmap_sidelength / 2 (304, 309)
+    if (!cfg->proj) { g.sx = (double)lv[l].w / ori_w; g.sy = (double)lv[l].h / ori_h; }
     return g;
   };
   G2sSolveArgs sa{};
@@ -285,9 +451,10 @@ extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
     aa.TP = lm_pick_tile(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.B = B;
     aa.xcd_affine = (B >= 8) ? 1 : 0;
     const int nblk = aa.xcd_affine ? 8 * ((B + 7) / 8) * aa.nt : B * aa.nt;
-    hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : K_LM64, 0,
+    hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
                    (double)B * ((double)v.h * v.w + (double)aa.npix) * v.C * 4.0, st);
-    if (cfg->using_weight) launch_g2s<true>(v.C, dim3(nblk), st, aa);
+    if (cfg->proj) launch_g2s_ip(v.C, dim3(nblk), st, aa);
+    else if (cfg->using_weight) launch_g2s<true>(v.C, dim3(nblk), st, aa);
     else launch_g2s<false>(v.C, dim3(nblk), st, aa);
     hla_prof_end(st);
     sa.part = part; sa.nt = aa.nt; sa.src_inv = v.grd_inv_norm; sa.fix_inv = v.sat_inv_norm;
@@ -323,7 +490,7 @@ struct G2sBwdAccumArgs {
   int A, h, w, ctr, npix, TP, nt, B, xcd_affine;
 };
 
-template <int C, bool USE_W>
+template <int C, bool USE_W, int PROJ = 0>
 __global__ __launch_bounds__(256) void g2s_bwd_accum(G2sBwdAccumArgs a) {
   __shared__ G2sPix pp[MAX_TP];
   __shared__ float pixacc[MAX_TP][9];     // a_u a_v a_j0u a_j0v a_j1u a_j1v a_j2u a_j2v a_w
@@ -337,7 +504,7 @@ __global__ __launch_bounds__(256) void g2s_bwd_accum(G2sBwdAccumArgs a) {
   const float* confb = USE_W ? a.conf + (size_t)b * a.h * a.w : nullptr;
   if (t < np) {
     const int p = p0 + t;
-    pp[t] = g2s_pixel<C, USE_W>(cf, p / a.A, p % a.A, a.ctr, a.h, a.w, confb);
+    pp[t] = g2s_pixel<C, USE_W, PROJ>(cf, p / a.A, p % a.A, a.ctr, a.h, a.w, confb);
   }
   __syncthreads();
 
@@ -443,7 +610,22 @@ __global__ __launch_bounds__(256) void g2s_bwd_accum(G2sBwdAccumArgs a) {
   double c21[21];
 #pragma unroll
   for (int k = 0; k < 21; ++k) c21[k] = 0.0;
-  if (t < np) {
+  if (PROJ == 1) {
+    // in-plane: u = c uc - s vc + Tu, v = s uc + c vc + Tv, j2 = k (-s uc - c vc, c uc - s vc); the shift columns are constants.
+    // Adjoints of (cos, sin, Tu, Tv) in slots IP_C, IP_S, IP_TU, IP_TV -- the heading column's dependence on cos / sin is the
+    // d2R/dtheta2 term
+    if (t < np) {
+      const int p = p0 + t;
+      const G2sPix P = pp[t];
+      if ((P.wx0 + P.wx1 + P.wy0 + P.wy1) != 0.f) {
+        const double uc = (double)(p % a.A) - cf[IP_HALF], vc = (double)(p / a.A) - cf[IP_HALF], k = cf[IP_K];
+        const double au = pixacc[t][0], av = pixacc[t][1], a2u = pixacc[t][6], a2v = pixacc[t][7];
+        c21[IP_C] = au * uc + av * vc + k * (a2v * uc - a2u * vc);
+        c21[IP_S] = av * uc - au * vc - k * (a2u * uc + a2v * vc);
+        c21[IP_TU] = au; c21[IP_TV] = av;
+      }
+    }
+  } else if (t < np) {
     const int p = p0 + t;
     const G2sPix P = pp[t];
     const bool inb = (P.wx0 + P.wx1 + P.wy0 + P.wy1) != 0.f;
@@ -490,7 +672,10 @@ __global__ __launch_bounds__(256) void g2s_bwd_accum(G2sBwdAccumArgs a) {
     }
   }
 #pragma unroll
-  for (int k = 0; k < 21; ++k) c21[k] = wave_sum_f64(c21[k]);
+  for (int k = 0; k < 21; ++k) {
+    if (PROJ == 1 && k > IP_TV) continue;      // (only four adjoints live)
+    c21[k] = wave_sum_f64(c21[k]);
+  }
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 21; ++k) red[wave][k] = c21[k];
@@ -518,6 +703,15 @@ __device__ static inline void g2s_coefficients_bwd(const G2sGeom& G, double th, 
   g3[0] = -G.lon * gT2;                 // T2 = -su*lon
   g3[1] = G.lat * gT0;                  // T0 =  sv*lat
   g3[2] = k * (s * gc - c * gs);        // ang = -th*k
+}
+
+// adjoint of g2s_ip_coefficients: a[IP_C], a[IP_S], a[IP_TU], a[IP_TV] -> d(loss)/d(su, sv, th)
+__device__ static inline void g2s_ip_coefficients_bwd(const G2sGeom& G, double th, const double* a, double* g3) {
+  const double k = G.rot / 180.0 * 3.14159265358979323846;
+  const double ang = th * k, c = cos(ang), s = sin(ang);
+  g3[0] = -G.lon / G.mpp * a[IP_TU];
+  g3[1] = G.lat / G.mpp * a[IP_TV];
+  g3[2] = k * (c * a[IP_S] - s * a[IP_C]);
 }
 
 struct G2sBwdSolveArgs {
@@ -552,7 +746,10 @@ __global__ __launch_bounds__(64) void g2s_bwd_solve(G2sBwdSolveArgs a) {
   double gout[3] = {dt[0], dt[1], dt[2]};
   if (!a.first) {
     double g3[3] = {0, 0, 0};
-    if (a.part_next) g2s_coefficients_bwd(a.geom_next, po[2], K9, c21, g3);
+    if (a.part_next) {
+      if (a.geom_next.proj) g2s_ip_coefficients_bwd(a.geom_next, po[2], c21, g3);
+      else g2s_coefficients_bwd(a.geom_next, po[2], K9, c21, g3);
+    }
     for (int p = 0; p < 3; ++p) gout[p] += g3[p] + a.gid[(size_t)b * 3 + p];
   }
   float pin[3] = {0.f, 0.f, 0.f};
@@ -572,7 +769,8 @@ __global__ __launch_bounds__(64) void g2s_bwd_solve(G2sBwdSolveArgs a) {
   ad[5] = 2.0 * gH[1][1]; ad[6] = gH[1][2] + gH[2][1]; ad[7] = 2.0 * gH[2][2];
   for (int p = 0; p < 3; ++p) { ad[8 + p] = y[p]; ad[11 + p] = -y[p]; }
   ad[14] = ad[15] = 0.0;
-  g2s_coefficients(a.geom, pin[0], pin[1], pin[2], K9, a.coef + (size_t)b * G2S_COEF_N);
+  if (a.geom.proj) g2s_ip_coefficients(a.geom, pin[0], pin[1], pin[2], a.coef + (size_t)b * G2S_COEF_N);
+  else g2s_coefficients(a.geom, pin[0], pin[1], pin[2], K9, a.coef + (size_t)b * G2S_COEF_N);
 }
 
 static size_t g2s_bwd_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B, size_t off[5]) {
@@ -604,16 +802,25 @@ static void launch_g2s_bwd(int C, dim3 grid, hipStream_t st, const G2sBwdAccumAr
   }
 }
 
+static void launch_g2s_ip_bwd(int C, dim3 grid, hipStream_t st, const G2sBwdAccumArgs& a) {
+  switch (C) {
+    case 256: hipLaunchKernelGGL((g2s_bwd_accum<256, false, 1>), grid, dim3(256), 0, st, a); break;
+    case 128: hipLaunchKernelGGL((g2s_bwd_accum<128, false, 1>), grid, dim3(256), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((g2s_bwd_accum<64, false, 1>), grid, dim3(256), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((g2s_bwd_accum<16, false, 1>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
 extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_level* lv, const hla_s2g_level_grad* gr,
                                     const float* camera_k, int ori_h, int ori_w, const float* pose0, const float* trace,
                                     const double* normal_eq, const float* d_trace, double* d_damping, void* workspace,
                                     size_t workspace_bytes, int B, hla_stream_t stream) {
-  HLA_REQUIRE(cfg && lv && gr && camera_k && trace && normal_eq && d_trace && d_damping && workspace,
-              "hla_g2s_lm_solve_bwd: null argument");
-  HLA_REQUIRE(B > 0 && !cfg->ford && cfg->dof == 3 && !cfg->level_first && !cfg->use_hessian && ori_h > 0 && ori_w > 0,
-              "hla_g2s_lm_solve_bwd: bad configuration");
+  HLA_REQUIRE(cfg && lv && gr && trace && normal_eq && d_trace && d_damping && workspace, "hla_g2s_lm_solve_bwd: null argument");
+  HLA_REQUIRE(B > 0 && cfg->n_levels >= 1 && cfg->n_levels <= 4 && cfg->n_iters >= 1 && !cfg->ford && cfg->dof == 3 &&
+              !cfg->level_first && !cfg->use_hessian, "hla_g2s_lm_solve_bwd: bad configuration");
+  if (const int rc = g2s_validate("hla_g2s_lm_solve_bwd", cfg, lv, camera_k, ori_h, ori_w)) return rc;
   for (int l = 0; l < cfg->n_levels; ++l) {
-    HLA_REQUIRE(lv[l].C == 256 || lv[l].C == 128 || lv[l].C == 64, "hla_g2s_lm_solve_bwd: unsupported channel count");
+    HLA_REQUIRE(lv[l].feat_dtype == HLA_F32 && lv[l].grd_row_skip == 0, "hla_g2s_lm_solve_bwd: level %d: whole fp32 maps only", l);
     HLA_REQUIRE(lv[l].sat_feat && lv[l].grd_feat && gr[l].d_sat_feat && gr[l].d_grd_feat, "hla_g2s_lm_solve_bwd: level %d buffers missing", l);
     HLA_REQUIRE(!cfg->using_weight || lv[l].grd_conf, "hla_g2s_lm_solve_bwd: using_weight needs grd_conf");
   }
@@ -635,7 +842,8 @@ extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
   auto geom = [&](int l) {
     G2sGeom g{};
     g.lat = cfg->shift_range_lat; g.lon = cfg->shift_range_lon; g.rot = cfg->rotation_range;
-    g.mpp = lv[l].meter_per_pixel; g.sx = (double)lv[l].w / ori_w; g.sy = (double)lv[l].h / ori_h;
+    g.mpp = lv[l].meter_per_pixel; g.proj = cfg->proj; g.half = 0.5 * lv[l].A;      // satmap_sidelength / 2 (304, 309)
+    if (!cfg->proj) { g.sx = (double)lv[l].w / ori_w; g.sy = (double)lv[l].h / ori_h; }
     return g;
   };
   int nt_prev = 0;
@@ -666,7 +874,8 @@ extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
     aa.xcd_affine = (B >= 8) ? 1 : 0;
     const int nblk = aa.xcd_affine ? 8 * ((B + 7) / 8) * aa.nt : B * aa.nt;
     hla_prof_begin(K_LMBWD, 0, (double)B * (5.0 * (double)v.h * v.w + 3.0 * (double)aa.npix) * v.C * 4.0, st);
-    if (cfg->using_weight) launch_g2s_bwd<true>(v.C, dim3(nblk), st, aa);
+    if (cfg->proj) launch_g2s_ip_bwd(v.C, dim3(nblk), st, aa);
+    else if (cfg->using_weight) launch_g2s_bwd<true>(v.C, dim3(nblk), st, aa);
     else launch_g2s_bwd<false>(v.C, dim3(nblk), st, aa);
     hla_prof_end(st);
     nt_prev = aa.nt;

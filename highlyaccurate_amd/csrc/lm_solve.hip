@@ -354,6 +354,7 @@ int hla_s2g_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_l
   HLA_REQUIRE(cfg && lv, "%s: null argument", who);
   HLA_REQUIRE(B > 0 && cfg->n_levels >= 1 && cfg->n_levels <= 4 && cfg->n_iters >= 1, "%s: bad sizes", who);
   HLA_REQUIRE(cfg->dof >= 1 && cfg->dof <= 3, "%s: dof must be 1..3", who);
+  HLA_REQUIRE(cfg->proj == 0, "%s: cfg->proj selects the projection of hla_g2s_* only (must be 0 here)", who);
   HLA_REQUIRE(!cfg->ford || (R_FL && T_FL), "%s: Ford mode needs R_FL and T_FL", who);
   for (int l = 0; l < cfg->n_levels; ++l) {
     const int C = lv[l].C;

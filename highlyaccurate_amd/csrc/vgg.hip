@@ -70,6 +70,11 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
                          int flags, int first_row8, hipStream_t st) {
   const bool level4 = pl.x2r != 0;
   const int NL = level4 ? 4 : 3;
+  // HLA_VGG_FOLD_DECODER (VGGUnet_G2S, VGG.py:278-310): the maps behind the encoder are read as [2h, w/2].  On NHWC storage
+  // that is the same buffer, so only the geometry the decoder launches are given changes: dH(d), dW(d) for the 1/d maps.
+  const bool fold = (flags & HLA_VGG_FOLD_DECODER) != 0;
+  auto dH = [&](int d) { return fold ? 2 * (H / d) : H / d; };
+  auto dW = [&](int d) { return fold ? (W / d) / 2 : W / d; };
   auto W_ = [&](int l) { return (const uint4*)(packed + packed_offset(l, dtype)); };
   char* w = ws;
   constexpr bool SPLIT = Prec<T>::SPLIT;
@@ -187,28 +192,29 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   conv(6, w + pl.a12, 256, H / 4, W / 4, w + pl.x15r, 1, true, nullptr, 0, 0, feat[0],
        (double*)(w + pl.ss[0]), (unsigned char*)(w + pl.idx15), r_c14, 0);            // conv14 + pool -> x15
   // decoder (VGG.py:144-151): conv(relu(cat(up(a), skip))) with both inputs stored post-ReLU
-  conv(7, w + pl.x15r, 256, H / 4, W / 4, w + pl.d1a, 1, false, w + pl.x8, 128, 1, nullptr, nullptr, nullptr, r_d11);   // dec1.1
-  conv(8, w + pl.d1a, 128, H / 4, W / 4, w + pl.x18r, 1, false, nullptr, 0, 0, feat[1],
+  conv(7, w + pl.x15r, 256, dH(4), dW(4), w + pl.d1a, 1, false, w + pl.x8, 128, 1, nullptr, nullptr, nullptr, r_d11);   // dec1.1
+  conv(8, w + pl.d1a, 128, dH(4), dW(4), w + pl.x18r, 1, false, nullptr, 0, 0, feat[1],
        (double*)(w + pl.ss[1]), nullptr, r_d13, 1);                                   // dec1.3 -> x18
   // relu(x21) feeds conv_dec3 (level 4), the conf2 head and the training backward only: without them the 16-bit feature path
   // stores just the raw map
   const bool x21r_dead = !level4 && !wc && !train && (flags & HLA_VGG_FEAT16) && sizeof(T) == 2;
   for (int b0 = 0; b0 < B; b0 += chunk) {      // (the half-resolution decoder pair in the same chunks: d2a is read once, right away)
     const int nb = B - b0 < chunk ? B - b0 : chunk;
-    conv(9, w + pl.x18r, 128, H / 2, W / 2, w + pl.d2a, 1, false, w + pl.x3, 64, 1, nullptr, nullptr, nullptr, r_d21, -1, b0, nb);    // dec2.1
-    conv(10, w + pl.d2a, 64, H / 2, W / 2, x21r_dead ? (char*)nullptr : w + pl.x21r, 1, false, nullptr, 0, 0, feat[2],
+    conv(9, w + pl.x18r, 128, dH(2), dW(2), w + pl.d2a, 1, false, w + pl.x3, 64, 1, nullptr, nullptr, nullptr, r_d21, -1, b0, nb);    // dec2.1
+    conv(10, w + pl.d2a, 64, dH(2), dW(2), x21r_dead ? (char*)nullptr : w + pl.x21r, 1, false, nullptr, 0, 0, feat[2],
          (double*)(w + pl.ss[2]), nullptr, r_d23, 2, b0, nb);                           // dec2.3 -> x21
   }
   if (level4) {      // VGG.py:153-155: conv_dec3 on cat(up(x21), x2), zero-padded to 64 channels (vgg_layers.h)
-    conv(11, w + pl.x21r, 64, H, W, w + pl.d3a, 1, false, w + pl.x2r, 64, 1);          // dec3.1
-    conv(12, w + pl.d3a, 64, H, W, w + pl.x24r, 1, false, nullptr, 0, 0, feat[3],
+    conv(11, w + pl.x21r, 64, dH(1), dW(1), w + pl.d3a, 1, false, w + pl.x2r, 64, 1);          // dec3.1
+    conv(12, w + pl.d3a, 64, dH(1), dW(1), w + pl.x24r, 1, false, nullptr, 0, 0, feat[3],
          (double*)(w + pl.ss[3]), nullptr, 0, 3);                                      // dec3.3 -> x24 (16 real channels)
   }
   // confidence heads on the ReLU'd maps
   if ((flags & HLA_VGG_WANT_CONF) && conf) {
     using CT = std::conditional_t<SPLIT, float, T>;      // split mode stores fp32 activations: the heads run in plain fp32
     const CT* acts[4] = {(const CT*)(w + pl.x15r), (const CT*)(w + pl.x18r), (const CT*)(w + pl.x21r), (const CT*)(w + pl.x24r)};
-    const int Cs[4] = {256, 128, 64, 64}, hs[4] = {H / 8, H / 4, H / 2, H}, wsz[4] = {W / 8, W / 4, W / 2, W};
+    // (conf0 reads the UNFOLDED x15 also under HLA_VGG_FOLD_DECODER: VGG.py:322)
+    const int Cs[4] = {256, 128, 64, 64}, hs[4] = {H / 8, dH(4), dH(2), dH(1)}, wsz[4] = {W / 8, dW(4), dW(2), dW(1)};
     for (int l = 0; l < NL; ++l) {
       if (!conf[l]) continue;
       const size_t npix = (size_t)B * hs[l] * wsz[l];
@@ -280,6 +286,12 @@ extern "C" size_t hla_vgg_workspace_bytes(int B, int H, int W, int level, int dt
   return p.total;
 }
 
+extern "C" size_t hla_vgg_workspace_bytes_flags(int B, int H, int W, int level, int dtype, int flags) {
+  VggPlan p;
+  vgg_plan(B, H, W, dtype, /*train=*/true, &p, level == 4, (flags & HLA_VGG_FOLD_DECODER) != 0);
+  return p.total;
+}
+
 extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
                                void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
                                size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
@@ -300,8 +312,14 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
                                             !(flags & HLA_VGG_SAVE_FOR_BACKWARD) && level == 3),
               "hla_vgg_forward: HLA_VGG_FEAT16 needs dtype HLA_BF16 / HLA_F16, HLA_VGG_DEFER_NORM, level 3 and no HLA_VGG_SAVE_FOR_BACKWARD");
   HLA_REQUIRE(first_row8 == 0 || (first_row8 >= 4 && first_row8 < H / 8), "hla_vgg_forward: first_row8 must be 0 or in [4, H/8)");
+  // folded decoder: the narrowest folded map (x15, W/16 wide) is up-sampled 2x into the W/8-wide dec1 geometry, so W/8 must be
+  // even; the 32-px / 8-row conv tiles take partial tiles at the right / bottom edge as for any other width (the partial-sum
+  // slots of the folded tile counts are planned by hla_vgg_workspace_bytes_flags, vgg_layers.h); every row of every map is read
+  HLA_REQUIRE(!(flags & HLA_VGG_FOLD_DECODER) || (W % 16 == 0 && first_row8 == 0 && !(flags & HLA_VGG_FEAT16)),
+              "hla_vgg_forward: HLA_VGG_FOLD_DECODER needs W %% 16 == 0 (folded maps are W/16, W/8, W/4 wide), first_row8 == 0 and no "
+              "HLA_VGG_FEAT16 (got W = %d, first_row8 = %d)", W, first_row8);
   VggPlan pl;
-  vgg_plan(B, H, W, dtype, (flags & HLA_VGG_SAVE_FOR_BACKWARD) != 0, &pl, level == 4);
+  vgg_plan(B, H, W, dtype, (flags & HLA_VGG_SAVE_FOR_BACKWARD) != 0, &pl, level == 4, (flags & HLA_VGG_FOLD_DECODER) != 0);
   if (workspace_bytes < pl.total) {
     hla_set_error("hla_vgg_forward: workspace %zu < %zu", workspace_bytes, pl.total);
     return HLA_ERR_WORKSPACE;

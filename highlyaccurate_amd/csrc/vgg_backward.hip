@@ -1631,7 +1631,7 @@ static int wgrad_ksplit(int Cout, int Cin, int ntile, int resident = 512) {
   return ks;
 }
 
-static void bwd_plan(int B, int H, int W, int dtype, BwdPlan* p, bool level4 = false) {
+static void bwd_plan(int B, int H, int W, int dtype, BwdPlan* p, bool level4 = false, bool fold = false) {
   const size_t es = hla_elem_bytes(dtype);
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += hla_align_up(bytes, 256); return r; };
@@ -1650,7 +1650,8 @@ static void bwd_plan(int B, int H, int W, int dtype, BwdPlan* p, bool level4 = f
   for (int l = 1; l < (level4 ? kAllLayers : kPackedLayers); ++l) {
     const int div = l < 11 ? hs[l] : 1;
     const int h = H / div, w = W / div;
-    const int ntile = B * ((h + WG_TH - 1) / WG_TH) * ((w + 31) / 32);
+    int ntile = B * ((h + WG_TH - 1) / WG_TH) * ((w + 31) / 32);
+    if (fold && l >= 7) ntile = B * ((2 * h + WG_TH - 1) / WG_TH) * ((w / 2 + 31) / 32);      // the decoder on [2h, w/2]
     const size_t sz = (size_t)wgrad_ksplit(kLayers[l].cout, kLayers[l].cin, ntile) * kLayers[l].cout * kLayers[l].cin * 9 * 4;
     if (sz > maxpart) maxpart = sz;
   }
@@ -1710,7 +1711,7 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
   const bool fuse0 = !level4 && !(flags & (HLA_VGG_BWD_WGRAD_TWO_PHASE | HLA_VGG_BWD_WGRAD0_UNFUSED));
   const int NL = level4 ? 4 : 3;
   VggPlan fp;
-  vgg_plan(B, H, W, dtype, true, &fp, level4);
+  vgg_plan(B, H, W, dtype, true, &fp, level4, (flags & HLA_VGG_BWD_FOLD_DECODER) != 0);
   constexpr int KC = SB / (int)sizeof(T);
   constexpr bool SPLIT = Prec<T>::SPLIT;
   using ET = std::conditional_t<SPLIT, float, T>;      // element type of the stored maps (split mode: fp32): the elementwise kernels
@@ -1763,8 +1764,13 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
   // data-dependent trimming (see bwd_fan_kernel): needs exact zeros outside the support, i.e. the one-pass L2 backward, and no
   // confidence-head gradient (which is dense).  Not combined with the caller's static first rows (the ground branch: every
   // column of its bottom half carries gradient, so there is nothing to gain).
+  // HLA_VGG_BWD_FOLD_DECODER: the decoder's launches run on the folded geometry [2h, w/2] (dH, dW below; same buffers).  The
+  // trimming tables describe the unfolded layer graph, so that mode takes the dense walk.
+  const bool fold = (flags & HLA_VGG_BWD_FOLD_DECODER) != 0;
+  auto dH = [&](int d) { return fold ? 2 * (H / d) : H / d; };
+  auto dW = [&](int d) { return fold ? (W / d) / 2 : W / d; };
   const bool dynamic = !level4 && (flags & HLA_VGG_BWD_SCALE_INVARIANT) && !(flags & HLA_VGG_BWD_DENSE) && !(conf && d_conf) &&
-                       first_row8 == 0 && H <= 1024;
+                       first_row8 == 0 && H <= 1024 && !fold;
   const DynLayout dl = dyn_layout(H, W);
   int* dynp = (int*)(bw + bp.dyn);
   if (dynamic) HLA_CHECK_HIP(hipMemsetAsync(dynp, 0x80, (size_t)dl.seed_ints * sizeof(int), st));
@@ -1829,7 +1835,7 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
   // ---- confidence heads (only the ground branch with using_weight=1 ever has d_conf): adds into the raw-map gradients
   if (conf && d_conf) {
     const ET* acts[4] = {(const ET*)(fw + fp.x15r), (const ET*)(fw + fp.x18r), (const ET*)(fw + fp.x21r), (const ET*)(fw + fp.x24r)};
-    const int Cs[4] = {256, 128, 64, 64}, hs[4] = {H / 8, H / 4, H / 2, H}, wsz[4] = {W / 8, W / 4, W / 2, W};
+    const int Cs[4] = {256, 128, 64, 64}, hs[4] = {H / 8, dH(4), dH(2), dH(1)}, wsz[4] = {W / 8, dW(4), dW(2), dW(1)};
     for (int l = 0; l < NL; ++l) {
       if (!d_conf[l]) continue;
       constexpr int EPL = 16 / (int)sizeof(ET);
@@ -1936,27 +1942,28 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
   const unsigned char* idx8 = (const unsigned char*)(fw + fp.idx8);
   const unsigned char* idx15 = (const unsigned char*)(fw + fp.idx15);
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+  const int Hd1 = dH(1), Wd1 = dW(1), Hd2 = dH(2), Wd2 = dW(2), Hd4 = dH(4), Wd4 = dW(4);      // the decoder's geometry
 
   // ---- decoder 3 (VGG.py:153-155, level 4 only; zero-padded to 64 channels, the host slices the weight gradients)
   if (level4) {
-    dgrad(12, 0, 64, G(bp.g_x24), nullptr, H, W, G(bp.g_d3a), F(fp.d3a), nullptr, false, 0, 0, 0, -1, GA_X24, GA_D3A);
-    wgrad(12, F(fp.d3a), 64, nullptr, 0, 0, G(bp.g_x24), nullptr, H, W, 0, -1, AM_D3A, -1, GA_X24);
-    dgrad(11, 0, 64, G(bp.g_d3a), nullptr, H, W, G(bp.g_x21), F(fp.x21r), G(bp.l2_21), true, 0, 0, 0, -1, GA_D3A, GA_X21);     // up(x21) branch
-    dgrad(11, 64, 64, G(bp.g_d3a), nullptr, H, W, G(bp.g_x2p), F(fp.x2r), nullptr, false, 0, 0, 0, -1, GA_D3A, GA_X2P);         // x2 skip branch
-    wgrad(11, F(fp.x21r), 64, F(fp.x2r), 64, 1, G(bp.g_d3a), nullptr, H, W, 0, -1, AM_X21, AM_X2, GA_D3A);
+    dgrad(12, 0, 64, G(bp.g_x24), nullptr, Hd1, Wd1, G(bp.g_d3a), F(fp.d3a), nullptr, false, 0, 0, 0, -1, GA_X24, GA_D3A);
+    wgrad(12, F(fp.d3a), 64, nullptr, 0, 0, G(bp.g_x24), nullptr, Hd1, Wd1, 0, -1, AM_D3A, -1, GA_X24);
+    dgrad(11, 0, 64, G(bp.g_d3a), nullptr, Hd1, Wd1, G(bp.g_x21), F(fp.x21r), G(bp.l2_21), true, 0, 0, 0, -1, GA_D3A, GA_X21);     // up(x21) branch
+    dgrad(11, 64, 64, G(bp.g_d3a), nullptr, Hd1, Wd1, G(bp.g_x2p), F(fp.x2r), nullptr, false, 0, 0, 0, -1, GA_D3A, GA_X2P);         // x2 skip branch
+    wgrad(11, F(fp.x21r), 64, F(fp.x2r), 64, 1, G(bp.g_d3a), nullptr, Hd1, Wd1, 0, -1, AM_X21, AM_X2, GA_D3A);
   }
   // ---- decoder 2 (VGG.py:148-151)
-  dgrad(10, 0, 64, G(bp.g_x21), nullptr, H2, W2, G(bp.g_d2a), F(fp.d2a), nullptr, false, n_d2a, n_x21, 0, DC_10, GA_X21, GA_D2A);   // (g_x21 is unwritten above n_x21)
-  wgrad(10, F(fp.d2a), 64, nullptr, 0, 0, G(bp.g_x21), nullptr, H2, W2, n_x21, DW_10, AM_D2A, -1, GA_X21);
-  dgrad(9, 0, 128, G(bp.g_d2a), nullptr, H2, W2, G(bp.g_x18), F(fp.x18r), G(bp.l2_18), true, rb_up18, n_d2a, 0, DC_9U, GA_D2A, GA_X18);   // up(x18) branch
-  dgrad(9, 128, 64, G(bp.g_d2a), nullptr, H2, W2, G(bp.g_x3p), F(fp.x3), nullptr, false, n_x3p, n_d2a, 0, DC_9S, GA_D2A, GA_X3P);          // x3 skip branch
-  wgrad(9, F(fp.x18r), 128, F(fp.x3), 64, 1, G(bp.g_d2a), nullptr, H2, W2, n_d2a, DW_9, AM_X18, AM_X3, GA_D2A);
+  dgrad(10, 0, 64, G(bp.g_x21), nullptr, Hd2, Wd2, G(bp.g_d2a), F(fp.d2a), nullptr, false, n_d2a, n_x21, 0, DC_10, GA_X21, GA_D2A);   // (g_x21 is unwritten above n_x21)
+  wgrad(10, F(fp.d2a), 64, nullptr, 0, 0, G(bp.g_x21), nullptr, Hd2, Wd2, n_x21, DW_10, AM_D2A, -1, GA_X21);
+  dgrad(9, 0, 128, G(bp.g_d2a), nullptr, Hd2, Wd2, G(bp.g_x18), F(fp.x18r), G(bp.l2_18), true, rb_up18, n_d2a, 0, DC_9U, GA_D2A, GA_X18);   // up(x18) branch
+  dgrad(9, 128, 64, G(bp.g_d2a), nullptr, Hd2, Wd2, G(bp.g_x3p), F(fp.x3), nullptr, false, n_x3p, n_d2a, 0, DC_9S, GA_D2A, GA_X3P);          // x3 skip branch
+  wgrad(9, F(fp.x18r), 128, F(fp.x3), 64, 1, G(bp.g_d2a), nullptr, Hd2, Wd2, n_d2a, DW_9, AM_X18, AM_X3, GA_D2A);
   // ---- decoder 1 (VGG.py:144-146)
-  dgrad(8, 0, 128, G(bp.g_x18), nullptr, H4, W4, G(bp.g_d1a), F(fp.d1a), nullptr, false, n_d1a, n_x18, 0, DC_8, GA_X18, GA_D1A);
-  wgrad(8, F(fp.d1a), 128, nullptr, 0, 0, G(bp.g_x18), nullptr, H4, W4, n_x18, DW_8, AM_D1A, -1, GA_X18);
-  dgrad(7, 0, 256, G(bp.g_d1a), nullptr, H4, W4, G(bp.g_x15), F(fp.x15r), G(bp.l2_15), true, rb_up15, n_d1a, 0, DC_7U, GA_D1A, GA_X15);   // up(x15) branch
-  dgrad(7, 256, 128, G(bp.g_d1a), nullptr, H4, W4, G(bp.g_x8p), F(fp.x8), nullptr, false, n_x8p, n_d1a, 0, DC_7S, GA_D1A, GA_X8P);        // x8 skip branch
-  wgrad(7, F(fp.x15r), 256, F(fp.x8), 128, 1, G(bp.g_d1a), nullptr, H4, W4, n_d1a, DW_7, AM_X15, AM_X8, GA_D1A);
+  dgrad(8, 0, 128, G(bp.g_x18), nullptr, Hd4, Wd4, G(bp.g_d1a), F(fp.d1a), nullptr, false, n_d1a, n_x18, 0, DC_8, GA_X18, GA_D1A);
+  wgrad(8, F(fp.d1a), 128, nullptr, 0, 0, G(bp.g_x18), nullptr, Hd4, Wd4, n_x18, DW_8, AM_D1A, -1, GA_X18);
+  dgrad(7, 0, 256, G(bp.g_d1a), nullptr, Hd4, Wd4, G(bp.g_x15), F(fp.x15r), G(bp.l2_15), true, rb_up15, n_d1a, 0, DC_7U, GA_D1A, GA_X15);   // up(x15) branch
+  dgrad(7, 256, 128, G(bp.g_d1a), nullptr, Hd4, Wd4, G(bp.g_x8p), F(fp.x8), nullptr, false, n_x8p, n_d1a, 0, DC_7S, GA_D1A, GA_X8P);        // x8 skip branch
+  wgrad(7, F(fp.x15r), 256, F(fp.x8), 128, 1, G(bp.g_d1a), nullptr, Hd4, Wd4, n_d1a, DW_7, AM_X15, AM_X8, GA_D1A);
   // ---- encoder block 2 (VGG.py:136-141); conv14 is followed by the pool (no ReLU in between)
   dgrad(6, 0, 256, G(bp.g_x15), idx15, H4, W4, G(bp.g_a12), F(fp.a12), nullptr, false, n_a12, 2 * n_x15, 0, DC_6, GA_X15, GA_A12);
   wgrad(6, F(fp.a12), 256, nullptr, 0, 0, G(bp.g_x15), idx15, H4, W4, 2 * n_x15, DW_6, AM_A12, -1, GA_X15);
@@ -2032,6 +2039,12 @@ extern "C" size_t hla_vgg_bwd_workspace_bytes(int B, int H, int W, int level, in
   return p.total;
 }
 
+extern "C" size_t hla_vgg_bwd_workspace_bytes_flags(int B, int H, int W, int level, int dtype, int flags) {
+  BwdPlan p;
+  bwd_plan(B, H, W, dtype, &p, level == 4, (flags & HLA_VGG_BWD_FOLD_DECODER) != 0);
+  return p.total;
+}
+
 // (HLA_F16X3: fp32 storage in the HLA_F32 workspace layout; data and weight gradients on split-fp16 kernels, conv0's weight
 // gradient and the elementwise passes on the fp32 ones)
 static inline int bwd_dtype(int dtype) { return dtype; }
@@ -2067,6 +2080,8 @@ extern "C" int hla_vgg_backward(const float* x, size_t x_plane, const hla_vgg_pa
   HLA_REQUIRE(first_row8 == 0 || (first_row8 >= 4 && first_row8 < H / 8), "hla_vgg_backward: first_row8 must be 0 or in [4, H/8)");
   const int NLc = level == 4 ? 4 : 3;
   HLA_REQUIRE(B > 0 && H % 8 == 0 && W % 8 == 0, "hla_vgg_backward: H and W must be multiples of 8");
+  HLA_REQUIRE(!(flags & HLA_VGG_BWD_FOLD_DECODER) || (W % 16 == 0 && first_row8 == 0),
+              "hla_vgg_backward: HLA_VGG_BWD_FOLD_DECODER needs W %% 16 == 0 and first_row8 == 0 (got W = %d, first_row8 = %d)", W, first_row8);
   for (int l = 0; l < kPackedLayers; ++l) HLA_REQUIRE(grads->dw[l], "hla_vgg_backward: dw[%d] missing", l);
   HLA_REQUIRE(!d_conf || conf, "hla_vgg_backward: d_conf given without conf");
   if (d_conf)
@@ -2076,7 +2091,7 @@ extern "C" int hla_vgg_backward(const float* x, size_t x_plane, const hla_vgg_pa
     HLA_REQUIRE(feat[3] && d_feat[3] && params->w[11] && params->w[12] && grads->dw[11] && grads->dw[12],
                 "hla_vgg_backward: level 4 needs feat[3], d_feat[3], the padded conv_dec3 weights and dw[11], dw[12] ([64,128,3,3], [64,64,3,3])");
   BwdPlan bp;
-  bwd_plan(B, H, W, dtype, &bp, level == 4);
+  bwd_plan(B, H, W, dtype, &bp, level == 4, (flags & HLA_VGG_BWD_FOLD_DECODER) != 0);
   if (workspace_bytes < bp.total) {
     hla_set_error("hla_vgg_backward: workspace %zu < %zu", workspace_bytes, bp.total);
     return HLA_ERR_WORKSPACE;

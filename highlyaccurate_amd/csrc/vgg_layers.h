@@ -42,7 +42,9 @@ struct VggPlan {
   size_t total;
 };
 
-static inline void vgg_plan(int B, int H, int W, int dtype, bool train, VggPlan* p, bool level4 = false) {
+// fold: the plan of a forward made with HLA_VGG_FOLD_DECODER (the decoder's tile counts are those of [2h, w/2]); every other
+// offset is the same
+static inline void vgg_plan(int B, int H, int W, int dtype, bool train, VggPlan* p, bool level4 = false, bool fold = false) {
   const size_t es = hla_elem_bytes(dtype);
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += hla_align_up(bytes, 256); return r; };
@@ -59,10 +61,11 @@ static inline void vgg_plan(int B, int H, int W, int dtype, bool train, VggPlan*
   p->x21r = take(P / 4 * 64 * es);
   // sum-of-squares partials: one per (image tile, cout block) of the producing layer
   auto tiles = [](int h, int w) { return ((h + 7) / 8) * ((w + 31) / 32); };
+  auto tiles_f = [&](int h, int w) { return fold ? tiles(2 * h, w / 2) : tiles(h, w); };      // the decoder layers
   p->np[0] = tiles(H / 4, W / 4) * 2;   // conv14: Cout 256 in blocks of 128
-  p->np[1] = tiles(H / 4, W / 4) * 1;   // dec1.3: Cout 128
-  p->np[2] = tiles(H / 2, W / 2) * 1;   // dec2.3: Cout 64
-  p->np[3] = tiles(H, W) * 1;           // dec3.3: Cout 16 (padded to 64)
+  p->np[1] = tiles_f(H / 4, W / 4) * 1; // dec1.3: Cout 128
+  p->np[2] = tiles_f(H / 2, W / 2) * 1; // dec2.3: Cout 64
+  p->np[3] = tiles_f(H, W) * 1;         // dec3.3: Cout 16 (padded to 64)
   for (int i = 0; i < 4; ++i) p->ss[i] = take((size_t)B * p->np[i] * sizeof(double));
   p->inv = take((size_t)4 * B * sizeof(double));
   p->amax = take((size_t)kAmaxSlots * B * sizeof(unsigned));

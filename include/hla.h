@@ -61,7 +61,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 21
+#define HLA_ABI_VERSION 22
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -90,6 +90,12 @@ enum {
                               scale into its normal equations: one full read+write pass less per map)  */
   HLA_VGG_SAVE_FOR_BACKWARD = 4, /* training: also keep relu(conv0) and the three max-pool argmax maps in the
                               workspace; the caller keeps the workspace alive until hla_vgg_backward   */
+  HLA_VGG_FOLD_DECODER = 16, /* VGGUnet_G2S (VGG.py:206-345): every map behind the encoder is FOLDED, [h,w] -> [2h,w/2]
+                              (an NCHW reshape in the reference; on NHWC storage the identity on memory).  The decoder
+                              layers conv_dec1.1 .. conv_dec3.3, their up-sampling / concatenation, the confidence heads
+                              1..3 and feat[0..3] take the folded geometry: feat[l] is [B,2h_l,w_l/2,C], conf[l >= 1] is
+                              [B,2h_l,w_l/2]; conf[0] stays on the unfolded x15 (VGG.py:322).  The encoder, its pooling
+                              and un-pooling are unchanged.  Needs W % 16 == 0 and first_row8 == 0 */
   HLA_VGG_FEAT16 = 8       /* dtype HLA_BF16 / HLA_F16 only, needs HLA_VGG_DEFER_NORM: feat[] are written as fp16 (saturating; also
                               in bf16 mode) instead of fp32 (inv_norm is that of the rounded maps); not with
                               HLA_VGG_SAVE_FOR_BACKWARD.  For hla_s2g_lm_solve with hla_s2g_level.feat_dtype set */
@@ -104,6 +110,9 @@ int hla_vgg_pack_weights(const hla_vgg_params* params, void* packed, int dtype, 
 
 /* Bytes of scratch hla_vgg_forward needs for this shape. */
 size_t hla_vgg_workspace_bytes(int B, int H, int W, int level, int dtype);
+/* The same for a forward made with `flags`: HLA_VGG_FOLD_DECODER plans the partial-sum slots of the folded decoder's tile counts
+ * (every other offset is unchanged; without that flag the result equals hla_vgg_workspace_bytes). */
+size_t hla_vgg_workspace_bytes_flags(int B, int H, int W, int level, int dtype, int flags);
 
 /* B, H, W  H and W multiples of 8, >= 8, and H*W < 2^23 pixels (8 388 608, e.g. below 2896 x 2896): the convolution kernels
  *          address a sample's activation map with signed 32-bit BYTE offsets and the largest map is H x W x 64 fp32.
@@ -148,6 +157,8 @@ size_t hla_vgg_packed_weight_T_bytes(int dtype);
 /* transposed + tap-flipped fragment packing used by the data-gradient convolutions */
 int hla_vgg_pack_weights_T(const hla_vgg_params* params, void* packed_T, int dtype, hla_stream_t stream);
 size_t hla_vgg_bwd_workspace_bytes(int B, int H, int W, int level, int dtype);
+/* The same for a backward made with `flags` (HLA_VGG_BWD_FOLD_DECODER: the weight-gradient partials of the folded tile counts). */
+size_t hla_vgg_bwd_workspace_bytes_flags(int B, int H, int W, int level, int dtype, int flags);
 
 /* x, x_plane, params  as in the forward call
  * fwd_workspace    the workspace of the forward call made with HLA_VGG_SAVE_FOR_BACKWARD | HLA_VGG_DEFER_NORM and the SAME dtype
@@ -176,6 +187,8 @@ size_t hla_vgg_bwd_workspace_bytes(int B, int H, int W, int level, int dtype);
 #define HLA_VGG_BWD_WGRAD_TWO_PHASE 4 /* weight gradients on the two-phase kernels (512 workgroups, what a device that refuses the
                                          wave-specialised kernels' 96-115 KB LDS request runs) instead of the wave-specialised
                                          ones: the same products in another split-K grouping (A/B and tests); implies the next */
+#define HLA_VGG_BWD_FOLD_DECODER 16    /* backward of a forward made with HLA_VGG_FOLD_DECODER (same geometry rules; the decoder's
+                                         launches take the dense walk, first_row8 must be 0) */
 #define HLA_VGG_BWD_WGRAD0_UNFUSED 8  /* conv2's data gradient stored as a map and conv0's weight gradient computed from it by a
                                          kernel of its own (rounds 1-5), instead of inside that data gradient's epilogue, where the
                                          map is never written (level 3; A/B and tests) */
@@ -282,6 +295,8 @@ typedef struct hla_s2g_config {
                              pairs whose bound outgrew the first one's by more than 2^(50 - P), i.e. put the 63-bit range at
                              risk (must be 0: repeat the call with a smaller P).  Costs 8 B per satellite-map element of
                              workspace, its memset and the closing pass */
+  int proj;               /* hla_g2s_lm_solve / hla_g2s_lm_solve_bwd only.  0: proj == 'geo', the camera chain.  1: proj == 'nn', the
+                             in-plane similarity warp of the (folded) ground map (models_kitti.py:289-332).  hla_s2g_* require 0 */
 } hla_s2g_config;
 
 size_t hla_s2g_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B);
@@ -313,7 +328,18 @@ int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* levels, con
  *            meter_per_pixel; xyz / row0 / centre are not read (the satellite grid is implicit, centre = A/2 integer)
  * camera_k   [B,3,3] fp32 intrinsics of the ori_h x ori_w ground IMAGE (left_camera_k, train_kitti.py:47)
  * trace      [B,N_iters,L,3] = (shift_u, shift_v, heading) after every step; no re-initialisation rule here.
- * normal_eq  [steps,B,16] or NULL: the 12 sums of every step in slots 2..13 (slots 0,1 = 1), needed by the backward */
+ * normal_eq  [steps,B,16] or NULL: the 12 sums of every step in slots 2..13 (slots 0,1 = 1), needed by the backward
+ *
+ * cfg->proj = 1: proj == 'nn' (inplane_grd_to_map 289-332 instead of 53-161).  Satellite pixel (row i, col j) of a level with
+ *            side A samples the ground map -- VGGUnet_G2S's folded one, [B,h,w,C] with any h, w -- at
+ *              (u, v) = R(theta) (j - A/2, i - A/2) + T + A/2,   R = [[cos, -sin], [sin, cos]],
+ *              T = (-shift_range_lon * shift_u, shift_range_lat * shift_v) / levels[l].meter_per_pixel   (291-312),
+ *              theta = heading * rotation_range * pi / 180,
+ *            with the Jacobian of 313-330: d(u,v)/d(shift_u) = (-shift_range_lon / mpp, 0), d(u,v)/d(shift_v) =
+ *            (0, shift_range_lat / mpp), d(u,v)/d(heading) = rotation_range * pi / 180 * dR/dtheta (j - A/2, i - A/2); the mask
+ *            is all ones and grid_sample's rules are the same (zero outside [0,w-1] x [0,h-1], clamped far corner).
+ *            using_weight must be 0; C may also be 16; camera_k (may be NULL), ori_h and ori_w are not read.  The backward
+ *            differentiates the pose through (u, v) and through d(u,v)/d(heading) (d2R/dtheta2 is not zero). */
 size_t hla_g2s_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B);
 int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* levels, const float* camera_k, int ori_h, int ori_w,
                      const float* pose0, float* trace, double* normal_eq, void* workspace, size_t workspace_bytes,
