@@ -183,16 +183,10 @@ class S2GPBase(nn.Module):
     #   train_ground_crop  0; 1: the same for training (changes the returned confidence maps above the crop)   DESIGN.md 3.5
     #   bwd_trim           1: the backward skips rows / tiles whose gradient is exactly zero; 0: dense walk     DESIGN.md 6
     #   bwd_two_streams    1: the two extractors' backward passes run on two streams (single-GPU training)       DESIGN.md 6
-    #   bwd_prefill        0: the LM backward's gradient buffers are cleared by one launch in front of it; 1: allocated and cleared
-    #                      during the forward, on a side stream; n > 1: as a background fill of n workgroups per buffer
-    #                      (an experiment kept as a switch: measured neutral, EXPERIMENTS.md round 6)
     #   wgrad_two_phase    0; 1: weight gradients on the two-phase kernels (A/B and tests: HLA_VGG_BWD_WGRAD_TWO_PHASE); 2: only conv0's
     #                      from a stored map of conv2's data gradient instead of inside that kernel's epilogue (..._WGRAD0_UNFUSED)
     #   strict_errors      0; 1: reproduce jacobian.py:172's AssertionError (costs a host sync per forward)     DESIGN.md 1
     #   small_batch_two_streams  4: inference batches up to this size run the two extractors on two streams        DESIGN.md 5
-    #   fwd_two_streams    unset / None / 0: off.  -1 or 1: inference at ANY batch with the satellite extractor on a side stream
-    #                      (-1: a high-priority one, 1: equal priority) -- an experiment kept as a switch: 0.3-0.6 % SLOWER at B = 32
-    #                      (EXPERIMENTS.md round 5)
     #   deterministic_backward  0; 1: lm_bwd_accum accumulates d(loss)/d(sat map) in a fixed order instead of with fp32 atomics:
     #                      the same batch twice gives bitwise equal parameter gradients
     def __init__(self, args):
@@ -378,8 +372,7 @@ class S2GPBase(nn.Module):
         self.last_trace, self.last_normal_eq = trace.detach(), neq
         return trace
 
-    def lm_grad_buffers(self, sat_feats, grd_feats, grd_confs, row0s, row_skips, grd_first_row8=0, overwrite=True, deterministic=False,
-                        max_blocks=0):
+    def lm_grad_buffers(self, sat_feats, grd_feats, grd_confs, row0s, row_skips, grd_first_row8=0, overwrite=True, deterministic=False):
         """The buffers ``hla_s2g_lm_solve_bwd`` accumulates into, cleared where they have to be by ONE launch (``hla_zero_fill``) on
         the current stream: (d_sat[l], d_grd[l], d_conf[l] or None, d_lambda[4]).
         * d_sat: zero-filled (the scatter adds); with ``deterministic`` not at all (the closing pass writes every element).
@@ -407,18 +400,17 @@ class S2GPBase(nn.Module):
         d_lambda = torch.empty(4, device=sat_feats[0].device, dtype=torch.float64)
         keep = d_sat + d_grd                      # (the regions of d_grd are raw pointers into tensors that are alive here)
         for k0 in range(0, len(regions), 16):
-            _lib.zero_fill(regions[k0:k0 + 16], max_blocks)
+            _lib.zero_fill(regions[k0:k0 + 16])
         del keep
         return d_sat, d_grd, d_conf, d_lambda
 
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def lm_backward(self, sat_feats, grd_feats, grd_confs, grd_hw, trace, normal_eq, d_trace, extra=None, level_first=0,
-                    init_pose=None, sat_inv_norm=None, grd_inv_norm=None, keep=None, grd_first_row8=0, overwrite=True, bufs=None):
+                    init_pose=None, sat_inv_norm=None, grd_inv_norm=None, keep=None, grd_first_row8=0, overwrite=True):
         """Backward of ``lm_solve``: d(loss)/d(trace) [B,N,L,3] -> (d_sat[l], d_grd[l], d_conf[l] or None, d_lambda[4]).
         ``keep``: the forward's dropout mask (``self.last_keep``), if args.dropout.
         Map gradients are NHWC fp32 and taken w.r.t. the L2-normalised maps (inv_norm * stored map).
-        ``bufs``: what ``lm_grad_buffers`` returned for the same maps and flags (training allocates and clears them while the
-        forward's convolutions run); None: made here.  ``args.deterministic_backward``: hla_s2g_config.deterministic."""
+        ``args.deterministic_backward``: hla_s2g_config.deterministic."""
         lib = _lib.load()
         dev = sat_feats[0].device
         B, L = sat_feats[0].shape[0], len(sat_feats)
@@ -429,10 +421,8 @@ class S2GPBase(nn.Module):
         det = bool(getattr(self.args, 'deterministic_backward', 0))
         cfg.deterministic = 1 if det else 0                  # (sizes the workspace: 8 B per satellite-map element)
         cfg.grd_grad_overwrite = 1 if overwrite else 0       # (0: zero-filled buffers, every step adds -- kept for callers of the C ABI)
-        if bufs is None:
-            bufs = self.lm_grad_buffers(sat_feats, grd_feats, grd_confs, [lv[l].row0 for l in range(L)],
-                                        [lv[l].grd_row_skip for l in range(L)], grd_first_row8, overwrite, det)
-        d_sat, d_grd, d_conf, d_lambda = bufs
+        d_sat, d_grd, d_conf, d_lambda = self.lm_grad_buffers(sat_feats, grd_feats, grd_confs, [lv[l].row0 for l in range(L)],
+                                                              [lv[l].grd_row_skip for l in range(L)], grd_first_row8, overwrite, det)
         gr = (_lib.S2GLevelGrad * L)()
         for l in range(L):
             gr[l].d_sat_feat, gr[l].d_grd_feat = d_sat[l].data_ptr(), d_grd[l].data_ptr()
@@ -479,15 +469,9 @@ class S2GPBase(nn.Module):
         # ground branch's (B <= args.small_batch_two_streams, default 4: B = 1 0.700 -> 0.615 ms, B = 4 1.195 -> 1.122; at B = 32, where both are dense, the same split measured
         # 2 % slower: DESIGN 3.1).
         small = sat_map.shape[0] <= int(getattr(self.args, 'small_batch_two_streams', 4))
-        # args.fwd_two_streams (round 5 experiment, default off = None / 0): the same split at ANY batch, the satellite branch on a side
-        # stream: -1 = a high-priority one (its chain owns the chip and the ground branch's launches fill the gaps its launch
-        # boundaries leave), 1 = equal priority
-        prio = getattr(self.args, 'fwd_two_streams', None)
-        prio = None if not prio else (-1 if int(prio) < 0 else 0)
-        small = small or prio is not None
         if small:
             cur = torch.cuda.current_stream()
-            side = _side_stream(sat_map.device, 0 if prio is None else int(prio))
+            side = _side_stream(sat_map.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16)
@@ -584,13 +568,12 @@ def raise_like_reference(trace, in_view, level_first, gn_norm2=None):
 _SIDE_STREAMS = {}
 
 
-def _side_stream(device, priority: int = 0) -> 'torch.cuda.Stream':
-    """One extra stream per device (and priority), kept OUTSIDE the modules (a Stream inside a module's __dict__ would break pickling / deepcopy)."""
+def _side_stream(device) -> 'torch.cuda.Stream':
+    """One extra stream per device, kept OUTSIDE the modules (a Stream inside a module's __dict__ would break pickling / deepcopy)."""
     idx = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-    key = (idx, priority)
-    st = _SIDE_STREAMS.get(key)
+    st = _SIDE_STREAMS.get(idx)
     if st is None:
-        st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=idx, priority=priority)
+        st = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=idx)
     return st
 
 
@@ -636,23 +619,6 @@ class _LocaliseFn(torch.autograd.Function):
         L = model._levels
         ctx.conf0 = grd_confs[0] if (model.level == 2 and grd_confs is not None) else None      # (the head's backward needs its own map)
         sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = L(sat_feats), L(sat_inv), L(grd_feats), L(grd_confs), L(grd_inv)
-        # args.bwd_prefill (round 6 experiment, default 0): allocate and clear the buffers the LM backward accumulates into NOW, on
-        # the side stream (1.4 GB of zero-fill at B = 32), so that it runs under the extractors' convolutions queued above instead
-        # of in front of the LM backward.  Measured neutral (same-box A/B, bf16 23.20 / 23.39 / 23.31 ms for off / on / a 16-workgroup
-        # background fill; fp16x3 53.51 / 53.53 / 53.65): the fill takes from the 2-stage layers it runs under what it saves
-        # (conv5 281 -> 439 us under a 204-us fill).  Default: ONE hla_zero_fill launch in front of the LM backward.
-        ctx.bufs = None
-        prefill = int(getattr(model.args, 'bwd_prefill', 0))
-        if prefill:
-            f8 = _bwd_first_row8(model, tuple(grd_img.shape[-2:]), grd_feats[-1].shape[1])
-            tabs = model.xyz_tables(grd_img.shape[-2], grd_img.shape[-1], sat_map.device)
-            row0s = [t.shape[0] // 2 for t in tabs]
-            skips = [t.shape[0] - g.shape[1] for t, g in zip(tabs, grd_feats)]
-            side = _side_stream(sat_map.device)
-            with torch.cuda.stream(side):
-                ctx.bufs = model.lm_grad_buffers(sat_feats, grd_feats, grd_confs, row0s, skips, f8, True,
-                                                 bool(getattr(model.args, 'deterministic_backward', 0)),
-                                                 max_blocks=prefill if prefill > 1 else 0)
         trace = model.lm_solve(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], extra, level_first, init_pose,
                                sat_inv, grd_inv, keep_normal_eq=True)
         _phase('lm_fwd')
@@ -685,14 +651,8 @@ class _LocaliseFn(torch.autograd.Function):
         trim = bool(getattr(model.args, 'bwd_trim', 1))
         # the ground maps' gradient lives in rows h_l/2.. (all the LM loop reads): the backward skips the rows above its support
         f8 = _bwd_first_row8(model, grd_hw, grd_feats[-1].shape[1])       # (grd_feats[-1]: the H/2 map)
-        bufs, ctx.bufs = ctx.bufs, None
-        if bufs is not None:          # cleared on the side stream during the forward: long done, but the order must be stated
-            cur = torch.cuda.current_stream()
-            cur.wait_stream(_side_stream(sat_feats[0].device))
-            for t in list(bufs[0]) + list(bufs[1]) + [c for c in bufs[2] if c is not None] + [bufs[3]]:
-                t.record_stream(cur)
         d_sat, d_grd, d_conf, d_lam = model.lm_backward(sat_feats, grd_feats, grd_confs, grd_hw, trace, neq, d_trace, ctx.extra,
-                                                   ctx.level_first, ctx.init_pose, sat_inv, grd_inv, keep, grd_first_row8=f8, bufs=bufs)
+                                                   ctx.level_first, ctx.init_pose, sat_inv, grd_inv, keep, grd_first_row8=f8)
         _phase('lm_bwd')
         if model.level == 2:        # x15 takes no part in the loop: its gradient (and its confidence map's) is zero
             zf = lambda cx: torch.zeros_like(cx['feats'][0], dtype=torch.float32)

@@ -1,4 +1,4 @@
-"""Build libhla.so (gfx950) in-tree with hipcc.  `python -m highlyaccurate_amd.build [--force] [--verbose] [--out=NAME.so] [-DX=1]`
+"""Build libhla.so (gfx950) in-tree with hipcc.  `python -m highlyaccurate_amd.build [--force] [--verbose] [--out=NAME.so] [-DNAME=1]`
 (A/B tooling: `-DX=<flag>` passes <flag> to hipcc verbatim, e.g. `-DX=-mllvm -DX=-amdgpu-sched-strategy=max-ilp --out=libhla_ilp.so`.)"""
 from __future__ import annotations
 

@@ -63,21 +63,6 @@ struct HlaPerDeviceOnce {
 
 static inline size_t hla_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// compute units of the current device (cached per device id < 64; 256 on MI355X)
-static inline int hla_num_cus() {
-  static std::atomic<int> cache[64];
-  int d = 0;
-  (void)hipGetDevice(&d);
-  if (d >= 0 && d < 64) {
-    const int c = cache[d].load(std::memory_order_relaxed);
-    if (c > 0) return c;
-  }
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
-  if (d >= 0 && d < 64) cache[d].store(n, std::memory_order_relaxed);
-  return n;
-}
-
 // 64-lane butterfly sum (all lanes end with the total)
 __device__ __forceinline__ float wave_sum_f32(float v) {
 #pragma unroll

@@ -62,14 +62,16 @@ __device__ __host__ __forceinline__ float split_scale(unsigned amax_bits) {
 // four fp32 values -> four (hi, lo) fp16 pairs of s x
 // Eight instructions: v_fma_mix{lo,hi}_f16 forms fp16(x * s + 0) (s is a power of two: the product is exact in fp32, one rounding to
 // nearest even) straight into one half of the destination, and fp16(x * s - hi) with the fp16 hi read as the addend (the fp32 FMA
-// result is exact before its one rounding).  Value for value what the plain C++ below computes -- hipcc needs 12-16 instructions
-// for it (packed multiplies, cvt_pk, converts back, packs) -- and the split is what the loaders of every split-mode kernel spend
-// their VALU time on.  -DHLA_SPLIT4_ASM=0 builds the C++ form (tools/probes/bitcmp_libs.py compares the two bit for bit).
-#ifndef HLA_SPLIT4_ASM
-#define HLA_SPLIT4_ASM 1
-#endif
+// result is exact before its one rounding).  Value for value (compared bit for bit) what this plain C++ computes -- hipcc needs
+// 12-16 instructions for it (packed multiplies, cvt_pk, converts back, packs) -- and the split is what the loaders of every
+// split-mode kernel spend their VALU time on:
+//   x0 *= s; x1 *= s; x2 *= s; x3 *= s;
+//   const f16 h0 = (f16)x0, h1 = (f16)x1, h2 = (f16)x2, h3 = (f16)x3;     // round to nearest even
+//   const f16x4 h = {h0, h1, h2, h3};
+//   const f16x4 l = {(f16)(x0 - (float)h0), (f16)(x1 - (float)h1), (f16)(x2 - (float)h2), (f16)(x3 - (float)h3)};
+//   hi = __builtin_bit_cast(uint2, h);
+//   lo = __builtin_bit_cast(uint2, l);
 __device__ __forceinline__ void split4(float x0, float x1, float x2, float x3, float s, uint2& hi, uint2& lo) {
-#if HLA_SPLIT4_ASM
   unsigned h01, h23, l01, l23;
   asm("v_fma_mixlo_f16 %0, %4, %8, 0\n\t"
       "v_fma_mixlo_f16 %1, %6, %8, 0\n\t"
@@ -82,14 +84,6 @@ __device__ __forceinline__ void split4(float x0, float x1, float x2, float x3, f
       : "=&v"(h01), "=&v"(h23), "=&v"(l01), "=&v"(l23) : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(s));
   hi = make_uint2(h01, h23);
   lo = make_uint2(l01, l23);
-#else
-  x0 *= s; x1 *= s; x2 *= s; x3 *= s;
-  const f16 h0 = (f16)x0, h1 = (f16)x1, h2 = (f16)x2, h3 = (f16)x3;     // round to nearest even
-  const f16x4 h = {h0, h1, h2, h3};
-  const f16x4 l = {(f16)(x0 - (float)h0), (f16)(x1 - (float)h1), (f16)(x2 - (float)h2), (f16)(x3 - (float)h3)};
-  hi = __builtin_bit_cast(uint2, h);
-  lo = __builtin_bit_cast(uint2, l);
-#endif
 }
 
 // Every dtype's kernels are compiled in their own translation unit (build.py passes -DHLA_TU_DTYPE=0|1|2); the
@@ -279,24 +273,9 @@ __device__ __forceinline__ int halo_off(int pix, int hx, int slot) { return pix 
 // (measured, same-box A/B of (TAP0, TAP1): (2, 6) beats (1, 5) by 3 % on the pooled 64-channel-wave-tile kernel and by 1 % on the
 // un-pooled one; (0, 4) the same; (3, 7) and (1, 6) lose 1-4 %; (3, 6) costs the 32-channel wave tile 20 %)
 constexpr int HALO_TAP0 = 2, HALO_TAP1 = 6;
-// The 16-bit plain kernels fetch a stage's halo tile HBM -> LDS directly (conv3x3_kernel, DMA): -DHLA_CONV_HALO_DMA=0 builds the
-// register-staged loader for them too (same-box A/B); the tap at whose weight loads the tile is requested (0 / 1 / 3 measure the same).
-#ifndef HLA_CONV_HALO_DMA
-#define HLA_CONV_HALO_DMA 1
-#endif
+// The 16-bit plain kernels fetch a stage's halo tile HBM -> LDS directly (conv3x3_kernel, DMA); the tap at whose weight loads the
+// tile is requested (0 / 1 / 3 measure the same).
 constexpr int HLA_CONV_DMA_TAP = 1;
-#ifndef HLA_CONV_DMA_EARLY1
-#define HLA_CONV_DMA_EARLY1 0
-#endif
-#ifndef HLA_A0_ABL
-#define HLA_A0_ABL 0
-#endif
-#ifndef HLA_UNPOOL_NT1_OCC
-#define HLA_UNPOOL_NT1_OCC 3         // workgroups per CU of conv2's data gradient (the one launch of the UNPOOL, 32-channel-wave-tile kernel)
-#endif
-#ifndef HLA_CONV_SMALL_GRID
-#define HLA_CONV_SMALL_GRID 320      // workgroups: below this a forward launch takes 4-row tiles (launch_conv)
-#endif
 // per-lane byte offsets of a wave's pixel fragments: [kx][kg] -> (x + kx) * PSTR + swizzled slot of (lane half g, k-group kg),
 // relative to the wave's first halo row
 struct FragOff { int o[3][2]; };
@@ -958,17 +937,17 @@ __device__ __forceinline__ void stage_mma(f32x16 (&acc)[MT][NT], const char* cur
 // of a piece next to the piece and applies them when the piece is WRITTEN to LDS -- masking right behind the load put an
 // s_waitcnt vmcnt(0) after every single piece, six full memory round trips per stage in the middle of the MFMA stream.
 template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false>
-__global__ __launch_bounds__(256, NT == 1 ? (UNPOOL ? HLA_UNPOOL_NT1_OCC : 3) : 2) void conv3x3_kernel(ConvArgs a) {
+__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs a) {
   static_assert(WM * WN == 4, "4 waves per block");
   constexpr int EPL = 16 / sizeof(T), KC = SB / sizeof(T);     // channels per stage: 32 (bf16) / 16 (fp32)
   constexpr int TH = WM * MT, HPIX = (TH + 2) * HWID;
   constexpr int NPIECE = (HPIX * 4 + 255) / 256;               // 16-B pieces per thread per stage ...
-  // DMA (HLA_CONV_HALO_DMA, 16-bit types, plain loader): the halo tile of a stage goes HBM -> LDS directly (buffer_load ... lds),
+  // DMA (16-bit types, plain loader): the halo tile of a stage goes HBM -> LDS directly (buffer_load ... lds),
   // no staging registers, no ds_write.  The LDS image of such a load is lane-linear (lane L's 16 B at M0 + 16 L), so the XOR
   // swizzle is applied to WHICH 16-B slot of its pixel a lane fetches; a pixel outside the image / the source's written part
   // gets an out-of-range offset and the buffer descriptor's range check writes zeros (tools/probes/lds_dma_probe.hip pins both).
   // A stage buffer is padded to whole 64-pixel pieces: the lanes past the tile's last pixel write zeros there.
-  constexpr bool DMA = HLA_CONV_HALO_DMA && sizeof(T) == 2 && !UNPOOL && !Prec<T>::SPLIT;
+  constexpr bool DMA = sizeof(T) == 2 && !UNPOOL && !Prec<T>::SPLIT;
   constexpr int BUF = (DMA ? NPIECE * 64 : HPIX) * PSTR;
   constexpr int NHALF = (NPIECE + 1) / 2;                      // ... fetched in two halves through NHALF staging registers
   // the epilogue reuses the halo buffers as four wave-private row stagers; the widest form stages a raw fp32 row and a 16-bit
@@ -1202,14 +1181,6 @@ __global__ __launch_bounds__(256, NT == 1 ? (UNPOOL ? HLA_UNPOOL_NT1_OCC : 3) : 
   ring.prime();              // the first weight fragments do not depend on the halo tile: request them ahead of it
   if constexpr (DMA) {
     dma_stage(0, 0);
-#if HLA_CONV_DMA_EARLY1
-    // the second stage's tile is requested right behind the first: both round trips overlap, and the first stage no longer
-    // ends on a tile that was requested one prologue later (per-wave cycle stamps, profiles/r06_conv_cycle_table_*.json)
-    if (nstage > 1) {
-      dma_stage(1, 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPIECE) : "memory");
-    } else
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     uint4 st1[NHALF];        // the prologue has registers to spare: both halves are requested back to back
@@ -1228,7 +1199,7 @@ __global__ __launch_bounds__(256, NT == 1 ? (UNPOOL ? HLA_UNPOOL_NT1_OCC : 3) : 
     char* nxt = lds + ((sg + 1) & 1) * BUF;
     stage_mma<T, MT, NT, WD, PF>(acc, lds + (sg & 1) * BUF, fo, ring, [&](int tap) __attribute__((always_inline)) {
       if constexpr (DMA) {
-        if (tap == HLA_CONV_DMA_TAP && more && !(HLA_CONV_DMA_EARLY1 && sg == 0)) dma_stage(sg + 1, (sg + 1) & 1);
+        if (tap == HLA_CONV_DMA_TAP && more) dma_stage(sg + 1, (sg + 1) & 1);
       } else {
         if (tap == HALO_TAP0 && more) load_stage(sg + 1, 0, st, ids);
         if (tap == HALO_TAP1 && more) { write_stage(nxt, sg + 1, 0, st, ids); load_stage(sg + 1, 1, st, ids); }
@@ -1586,13 +1557,7 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Con
         const float is = 1.f / s_a0;
         const float4 o4 = make_float4(((float)h[0] + (float)l[0]) * is, ((float)h[1] + (float)l[1]) * is,
                                       ((float)h[2] + (float)l[2]) * is, ((float)h[3] + (float)l[3]) * is);
-#if HLA_A0_ABL == 1       // timing-only ablations of the copy (tools/ab_libs.py): 1 = no store instruction, 2 = nt stores
-        if (o4.x == 12345.678f) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), ra, off, 0, 0);
-#elif HLA_A0_ABL == 2
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), ra, off, 0, 2);
-#else
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), ra, off, 0, 0);
-#endif
         if (ok) a0mx = fmaxf(fmaxf(a0mx, fmaxf(o4.x, o4.y)), fmaxf(o4.z, o4.w));        // (post-ReLU: non-negative)
       } else {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, *(const uint4*)(sb + halo_off(hpix, c + 1, part))), ra, off, 0, 0);
@@ -1893,6 +1858,7 @@ static __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x
 // BWD: the caller is the backward pass, whose conv2 / conv7 / conv14 data gradients read a virtually un-pooled source
 // (ConvArgs::unpool_idx): only then are the UNPOOL instantiations compiled into the translation unit.
 // Returns false (with the library's error string set, nothing launched) for a combination no kernel was compiled for.
+constexpr int CONV_SMALL_GRID = 320;      // workgroups: below this a forward launch takes 4-row tiles
 template <typename T, bool BWD = false>
 static bool launch_conv(hipStream_t st, ConvArgs a, bool pool) {
   if (a.unpool_idx && !(BWD && !pool)) {      // (cannot happen from this library's callers; the plain kernels ignore the field)
@@ -1923,7 +1889,7 @@ static bool launch_conv(hipStream_t st, ConvArgs a, bool pool) {
   // sum-of-squares partials are per tile, and a sample's L2 norm must not depend on its batch mates to the last bit.
   if constexpr (!BWD) {
     const int gy = big ? a.Cout / 128 : 1;
-    if (!a.dyn && !a.sumsq && !a.unpool_idx && a.tiles_x * a.tiles_y * a.B * gy < HLA_CONV_SMALL_GRID) {
+    if (!a.dyn && !a.sumsq && !a.unpool_idx && a.tiles_x * a.tiles_y * a.B * gy < CONV_SMALL_GRID) {
       a.tiles_y = (a.H - a.row_begin + 3) / 4;
       const dim3 g4(a.tiles_x * a.tiles_y * a.B, gy);
       if (big) {

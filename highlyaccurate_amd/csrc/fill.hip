@@ -35,7 +35,6 @@ extern "C" int hla_zero_fill(const hla_fill_region* regions, int n_regions, int 
     const size_t v = r.chunk_bytes / 16 * (size_t)r.n_chunks + 1;
     most = v > most ? v : most;
   }
-  if (most == 0) return HLA_OK;
   // (enough blocks for the largest region to keep every CU's store queue busy; small regions finish in their first blocks)
   size_t gx = (most + 256 * 16 - 1) / (256 * 16);
   gx = gx > 2048 ? 2048 : (gx < 1 ? 1 : gx);

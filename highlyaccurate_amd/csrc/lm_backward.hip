@@ -219,9 +219,6 @@ __global__ __launch_bounds__(64) void lm_bwd_solve(BwdSolveArgs a) {
 }
 
 
-#ifndef BWD_MAX_TP
-#define BWD_MAX_TP MAX_TP
-#endif
 struct BwdAccumArgs {
   const float* sat; const float* grd; const float* conf; const float* xyz;
   const double* coef;      // [B,COEF_N] forward coefficients of this step
@@ -244,8 +241,8 @@ struct BwdAccumArgs {
 
 template <int C, bool USE_W, bool DET = false>
 __global__ __launch_bounds__(256, USE_W ? 3 : 4) void lm_bwd_accum(BwdAccumArgs a, BwdSolveArgs sa) {
-  __shared__ PixParam pp[BWD_MAX_TP];
-  __shared__ float pxyz[BWD_MAX_TP][3];   // the pixel's ground-plane point (the coefficient adjoints weight by it)
+  __shared__ PixParam pp[MAX_TP];
+  __shared__ float pxyz[MAX_TP][3];   // the pixel's ground-plane point (the coefficient adjoints weight by it)
   __shared__ double red[4][12];
   __shared__ double c12s[12][256];
   int b, tile;
@@ -449,12 +446,8 @@ __global__ __launch_bounds__(256, USE_W ? 3 : 4) void lm_bwd_accum(BwdAccumArgs 
 //  smaller tiles merge fewer taps per texel cell, larger ones leave two blocks per CU)
 // (measured, same-box A/B twice: 256 / 128 / 64 -- the sizes LM_G2SP's kernels use -- 227.7 us per launch on average against
 // 218.3 for these; 128 / 128 / 64: 245)
-#ifndef HLA_LMB_TP0
-#define HLA_LMB_TP0 256     // npix >= 16384 (KITTI: the 64-channel level)
-#define HLA_LMB_TP1 256     // npix >= 4096  (the 128-channel level)
-#define HLA_LMB_TP2 128     // below         (the 256-channel level)
-#endif
-static inline int lm_pick_tile_bwd(int npix) { return npix >= 16384 ? HLA_LMB_TP0 : (npix >= 4096 ? HLA_LMB_TP1 : HLA_LMB_TP2); }
+// npix >= 16384 (KITTI: the 64-channel level) / >= 4096 (the 128-channel level) / below (the 256-channel level)
+static inline int lm_pick_tile_bwd(int npix) { return npix >= 16384 ? 256 : (npix >= 4096 ? 256 : 128); }
 
 // ---------------------------------------------------------------------------------------------
 // off[0..5]: coef, adj, gid, part, ADAM adjoints, tickets; off[6]: dlam [B,4]; off[7]: qexp [L,B]; off[8 + l]: level l's 64-bit

@@ -245,9 +245,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
 // of ds_read_b64_tr_b16 touches 4 consecutive pixels x 32 B, which the key spreads over 4 different 32-B segments of the two
 // 128-B bank halves.  Zero fill (outside the image / the written part of g) by the buffer descriptors' range check.
 // Plain launches only (no virtual unpool: that loader masks elements on the way into LDS).
-#ifndef HLA_WGRAD_DMA
-#define HLA_WGRAD_DMA 1
-#endif
 constexpr int WGD_XBLK = 28, WGD_GBLK = 16;             // 1-KiB blocks (8 pixels) per X buffer (204 pixels + pad) / G buffer
 constexpr int wgd_lds_bytes() { return (2 * WGD_XBLK + WGD_GBLK) * 1024; }
 
@@ -406,9 +403,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(WgradArgs a) {
 // write them into the idle one of two LDS buffers; waves 0-3 -- one per SIMD -- only read fragments and multiply, the next halo
 // row's fragments requested ahead of the current row's MFMAs.  One barrier per tile.  Plain AND un-pooling launches (wgrad_kernel
 // and wgrad_dma_kernel ran load -> barrier -> MFMA phases in every wave: 0.30 of the MFMA peak where the forward reaches 0.48).
-#ifndef HLA_WGRAD_WS
-#define HLA_WGRAD_WS 1
-#endif
 template <typename T> constexpr int wg_ws_buf_bytes() { return ((WG_TH + 2) * HWID + WG_TH * 32) * wg_stride<T>(); }
 template <typename T> constexpr int wg_ws_lds_bytes() { return 2 * wg_ws_buf_bytes<T>(); }
 
@@ -778,12 +772,6 @@ static __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs a,
 // share each SIMD, so the split's VALU work and the global-load latency run under the MFMAs instead of between them.  One
 // workgroup barrier per half tile; LDS: two buffers of {Xh, Xl, Gh, Gl} = 115 KB, one workgroup per CU, 256 registers per wave.
 // Same tile lists, same order of every partial sum's terms as wgrad_split_kernel (bit-identical partials for the same KS).
-#ifndef HLA_WGRAD_SPLIT_WS
-#define HLA_WGRAD_SPLIT_WS 1
-#endif
-#ifndef HLA_WS_ABL
-#define HLA_WS_ABL 0
-#endif
 constexpr int wgs_ws_buf_bytes() { return 2 * ((WGS_TH + 2) * HWID + WGS_TH * 32) * WGS_STR; }
 constexpr int wgs_ws_lds_bytes() { return 2 * wgs_ws_buf_bytes(); }
 
@@ -898,11 +886,7 @@ static __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WgradArgs
       for (int k = 0; k < NX; ++k) {
         const int pix = pix0 + k * PSTEP;
         uint2 hi, lw;
-#if HLA_WS_ABL == 2      // timing-only: no split arithmetic
-        hi = make_uint2(S.xr[k].x, S.xr[k].y); lw = make_uint2(S.xr[k].z, S.xr[k].w);
-#else
         split4(__uint_as_float(S.xr[k].x), __uint_as_float(S.xr[k].y), __uint_as_float(S.xr[k].z), __uint_as_float(S.xr[k].w), s_x, hi, lw);
-#endif
         if (pix < XPIX) { *(uint2*)(base + oXh + pix * STR + part * 8) = hi; *(uint2*)(base + oXl + pix * STR + part * 8) = lw; }
       }
 #pragma unroll
@@ -917,11 +901,7 @@ static __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WgradArgs
           if ((S.gid[k] >> 24) != pos) e3 = 0.f;
         }
         uint2 hi, lw;
-#if HLA_WS_ABL == 2
-        hi = make_uint2(__float_as_uint(e0), __float_as_uint(e1)); lw = make_uint2(__float_as_uint(e2), __float_as_uint(e3));
-#else
         split4(e0, e1, e2, e3, s_g, hi, lw);
-#endif
         *(uint2*)(base + oGh + pix * STR + part * 8) = hi; *(uint2*)(base + oGl + pix * STR + part * 8) = lw;
       }
     };
@@ -932,10 +912,6 @@ static __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WgradArgs
     commit(A, 0);
     __syncthreads();                                     // barrier 0: buffer 0 holds the first half tile
     int cur = 0;
-#if HLA_WS_ABL == 3      // timing only: the loaders do nothing but keep the barrier count
-    while (ta >= 0) { __syncthreads(); ta = next_t2(ta); }
-    return;
-#endif
     // at the top: the matrix waves work on half tile `ta` in buffer `cur`; Bq holds (in flight) the loads of `tb`; A is free
     while (ta >= 0) {
       int tc = tb >= 0 ? next_t2(tb) : -1;
@@ -983,7 +959,6 @@ static __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WgradArgs
     // ky that use it.  Term order per accumulator as in wgrad_split_kernel: (hi hi, lo hi, hi lo) per (kk, rho, kx, ky).
     constexpr int NSTEP = (32 / KPX) * (WGS_TH + 2);
     uint4 Ah[2][WGS_TH], Al[2][WGS_TH], Bh[2][3], Bl[2][3];
-#if HLA_WS_ABL != 1
 #pragma unroll
     for (int r = 0; r < WGS_TH; ++r) {
       Ah[0][r] = frag_kmajor<H>(Gh, STR, r * 32, ct * 32, lane);
@@ -1030,7 +1005,6 @@ static __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WgradArgs
         }
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
     __syncthreads();                                     // the loaders have filled the other buffer; this one is free
     cur ^= 1;
   }
@@ -1720,26 +1694,23 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
     if constexpr (SPLIT) {
       // (the wave-specialised form needs 115 KB of dynamic LDS: where the device refuses it, the launches below fall back to
       //  wgrad_split_kernel -- ws_ok, per device)
-      if (HLA_WGRAD_SPLIT_WS) {
-        int d = 0;
-        (void)hipGetDevice(&d);
-        const bool ok = hipFuncSetAttribute((const void*)wgrad_split_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_ws_lds_bytes()) == hipSuccess;
-        if (ok) g_wgrad_split_ws_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
-      }
+      int d = 0;
+      (void)hipGetDevice(&d);
+      const bool ok = hipFuncSetAttribute((const void*)wgrad_split_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_ws_lds_bytes()) == hipSuccess;
+      if (ok) g_wgrad_split_ws_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
       return hipFuncSetAttribute((const void*)wgrad_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_lds_bytes());
     }
     else {
-      if constexpr (sizeof(T) == 2 && HLA_WGRAD_DMA) {      // 72 KB: refused (a partition mode with a smaller per-workgroup limit) ->
-        int d = 0;                                          // the plain launches fall back to wgrad_kernel<T>
-        (void)hipGetDevice(&d);
-        const bool ok = hipFuncSetAttribute((const void*)wgrad_dma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wgd_lds_bytes()) == hipSuccess;
-        if (ok) g_wgrad_dma_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
-      }
-      if constexpr (sizeof(T) == 2 && HLA_WGRAD_WS) {      // 96 KB of dynamic LDS: refused -> the launches fall back (g_wgrad_ws_ok)
+      if constexpr (sizeof(T) == 2) {
         int d = 0;
         (void)hipGetDevice(&d);
-        const bool ok = hipFuncSetAttribute((const void*)wgrad_ws_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_ws_lds_bytes<T>()) == hipSuccess;
-        if (ok) g_wgrad_ws_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
+        // 72 KB: refused (a partition mode with a smaller per-workgroup limit) -> the plain launches fall back to wgrad_kernel<T>
+        // 
+        const bool dma = hipFuncSetAttribute((const void*)wgrad_dma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wgd_lds_bytes()) == hipSuccess;
+        if (dma) g_wgrad_dma_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
+        // 96 KB of dynamic LDS: refused -> the launches fall back (g_wgrad_ws_ok)
+        const bool ws = hipFuncSetAttribute((const void*)wgrad_ws_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_ws_lds_bytes<T>()) == hipSuccess;
+        if (ws) g_wgrad_ws_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
       }
       return hipFuncSetAttribute((const void*)wgrad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_lds_bytes<T>());
     }
@@ -1906,11 +1877,10 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
       (void)hipGetDevice(&d);
       dma_ok = (g_wgrad_dma_ok.load() & dev_bit(d)) != 0;
     }
-    if constexpr (SPLIT || (sizeof(T) == 2 && HLA_WGRAD_WS)) {      // wave-specialised kernels: one 8-wave workgroup per CU -> 256
-      int d = 0;                                                    // workgroups are one resident generation
+    if constexpr (SPLIT || sizeof(T) == 2) {                      // wave-specialised kernels: one 8-wave workgroup per CU -> 256
+      int d = 0;                                                  // workgroups are one resident generation
       (void)hipGetDevice(&d);
-      ws = (SPLIT ? HLA_WGRAD_SPLIT_WS : HLA_WGRAD_WS) && ((SPLIT ? g_wgrad_split_ws_ok : g_wgrad_ws_ok).load() & dev_bit(d)) != 0 &&
-           !(flags & HLA_VGG_BWD_WGRAD_TWO_PHASE);
+      ws = ((SPLIT ? g_wgrad_split_ws_ok : g_wgrad_ws_ok).load() & dev_bit(d)) != 0 && !(flags & HLA_VGG_BWD_WGRAD_TWO_PHASE);
       if (ws) a.KS = wgrad_ksplit(a.Cout, a.Cin, a.ntile, 256);
     }
     a.part = (float*)(bw + bp.part);
@@ -1922,7 +1892,7 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
       WgradSplitExtra ex{FA(fa1), FA(fa2), GA(ga)};
       if (ws) hipLaunchKernelGGL(wgrad_split_ws_kernel, dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(512), wgs_ws_lds_bytes(), st, a, ex);
       else hipLaunchKernelGGL(wgrad_split_kernel, dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wgs_lds_bytes(), st, a, ex);
-    } else if constexpr (sizeof(T) == 2 && HLA_WGRAD_DMA) {
+    } else if constexpr (sizeof(T) == 2) {
       if (ws) hipLaunchKernelGGL((wgrad_ws_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(512), wg_ws_lds_bytes<T>(), st, a);
       else if (!unpool && dma_ok) hipLaunchKernelGGL((wgrad_dma_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wgd_lds_bytes(), st, a);
       else hipLaunchKernelGGL((wgrad_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wg_lds_bytes<T>(), st, a);

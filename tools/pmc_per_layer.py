@@ -1,6 +1,5 @@
 """Per-LAYER HBM fetch bytes of one inference step from a rocprofv3 --pmc FETCH_SIZE pass (dispatch order), optionally for two
-runs side by side (e.g. HLA_VGG_CHUNK=0 against 8): does running the high-resolution chain in cache-sized chunks take its
-reads off the memory interface?   usage: pmc_per_layer.py <dir_a> [<dir_b>] > out.json"""
+runs side by side (two builds, or two settings of one).   usage: pmc_per_layer.py <dir_a> [<dir_b>] > out.json"""
 import csv, glob, json, sys
 
 
@@ -11,8 +10,7 @@ def last_step(d):
     rows.sort(key=lambda r: int(r['Dispatch_Id']))
     conv = [r for r in rows if 'conv' in r['Kernel_Name']]
     c02 = [i for i, r in enumerate(conv) if 'conv02' in r['Kernel_Name']]
-    # a step = from one "first conv02 of the satellite branch" to the next; with chunking there are several conv02 launches per
-    # branch, so cut at the launch count instead: the run is `steps` identical steps
+    # (the run is `steps` identical steps: the caller cuts at the launch count)
     return conv, c02
 
 

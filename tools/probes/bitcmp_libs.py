@@ -1,4 +1,4 @@
-"""Are two builds of libhla bit-identical on a split-mode forward + training step?  (e.g. -DHLA_SPLIT4_ASM=0 against the default)
+"""Are two builds of libhla bit-identical on a split-mode forward + training step?  (e.g. the previous commit's kernels against this one's)
     python tools/probes/bitcmp_libs.py libhla_a.so libhla_b.so      # each library runs in its own process; outputs compared with ==
 Inputs include exact zeros, denormal-range values and large magnitudes in the images and weights (the split's corner cases)."""
 import os, subprocess, sys, tempfile

@@ -1,8 +1,8 @@
 """Where the TRAINING variant of the fused conv0 + conv2 kernel spends its extra time: the extractor's forward with
-save_for_backward, timed per launch, under the library's timing-only switches.
-    for a in 0 1 2 3; do HLA_ABL_C02=$a python tools/probes/conv02_probe.py fp16x3; done    # bit 0: no relu(conv0) copy, bit 1: no argmax"""
+save_for_backward, timed per launch.
+    python tools/probes/conv02_probe.py fp16x3"""
 import os, sys, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from highlyaccurate_amd.VGG import VGGUnet, vgg_forward_nhwc
 from highlyaccurate_amd import _lib
 prec = sys.argv[1] if len(sys.argv) > 1 else 'fp16x3'
@@ -20,4 +20,4 @@ for train in (False, True):
     agg = {}
     for n, ms, fl, by in recs:
         a = agg.setdefault(n, [0, 0.0]); a[0] += 1; a[1] += ms
-    print(prec, 'abl', os.environ.get('HLA_ABL_C02', '0'), 'train' if train else 'infer', {n: round(v[1] / v[0] * 1e3, 1) for n, v in agg.items() if n.startswith('conv')})
+    print(prec, 'train' if train else 'infer', {n: round(v[1] / v[0] * 1e3, 1) for n, v in agg.items() if n.startswith('conv')})

@@ -1,5 +1,5 @@
 """Same-process, same-box A/B of a training step under different args settings, alternating, medians.
-    python tools/probes/train_ab.py bf16 bwd_prefill=0 bwd_prefill=1 bwd_prefill=24 [steps=8] [rounds=4]"""
+    python tools/probes/train_ab.py bf16 deterministic_backward=0 deterministic_backward=1 [steps=8] [rounds=4]"""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import bench
