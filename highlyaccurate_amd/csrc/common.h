@@ -14,6 +14,7 @@ enum { K_PACK = 0, K_CONV02, K_CONV_NT2, K_CONV_NT2_POOL, K_CONV_NT1, K_CONV_NT1
 void hla_prof_begin(int id, double flops, double bytes, hipStream_t st);
 void hla_prof_begin_dyn(int id, double flops, double bytes, hipStream_t st, const int* dev_live, int denom);
 void hla_prof_end(hipStream_t st);
+bool hla_prof_on();
 
 // per-wave cycle stamps of ONE conv3x3_kernel launch (tooling builds only: python -m highlyaccurate_amd.build --out=libhla_stamps.so
 // -DHLA_CONV_STAMPS=1; tools/probes/conv_stamps.py): launch_conv hands `buf` to the launch whose ordinal since the last

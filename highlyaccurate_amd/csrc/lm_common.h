@@ -48,14 +48,17 @@ __device__ __forceinline__ unsigned lm_draw_ticket(unsigned* ticket, int lane) {
 
 // block -> (sample, tile).  With >= 8 samples keep every tile of a sample on one XCD (blocks are dealt
 // round-robin to the 8 XCDs) so its satellite map stays in that XCD's L2.  Returns false for idle blocks.
-__device__ __forceinline__ bool lm_block_map(int xcd_affine, int nt, int B, int& b, int& tile) {
+// A launch may cover the sample range [b0, b0 + nb) of a larger batch (the forward loop's stream groups, lm_solve.hip): b is the
+// GLOBAL sample, and with b0 a multiple of 8 a sample sits on the XCD it has in a whole-batch launch.
+__device__ __forceinline__ bool lm_block_map(int xcd_affine, int nt, int nb, int& b, int& tile, int b0 = 0) {
   if (xcd_affine) {
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    b = (j / nt) * 8 + xcd;
+    const int local = (j / nt) * 8 + xcd;
+    b = b0 + local;
     tile = j % nt;
-    return b < B;
+    return local < nb;
   }
-  b = blockIdx.x / nt;
+  b = b0 + blockIdx.x / nt;
   tile = blockIdx.x % nt;
   return true;
 }

@@ -13,12 +13,13 @@
 //                deterministic), 3x3/2x2/1x1 damped solve, pose update + re-initialisation rule,
 //                and the projection coefficients of the NEXT step (so no extra launch for them).
 #include "lm_common.h"
+#include <mutex>
 
 struct SolveArgs {
-  const double* part;    // [B,nt,PART_N] of the step being closed, or null (init launch)
+  const double* part;    // [B,part_ld,PART_N] of the step being closed (nt tiles used), or null (init launch)
   const double* sat_inv; // [B] or null: feature maps are stored un-normalised, sums are rescaled here
   const double* grd_inv;
-  int nt;
+  int nt, part_ld;
   float* pose;           // [B,3] running pose (shift_u, shift_v, theta), fp32 like the reference
   float* trace_out;      // &trace[0][iter][level][0] of this step (sample stride = trace_stride)
   int trace_stride;
@@ -27,7 +28,7 @@ struct SolveArgs {
   double* coef;          // [B,COEF_N] out for the next step, or null
   const float* R_FL;     // [B,3,3]
   const float* T_FL;     // [B,3]
-  int B, reinit;
+  int B, reinit;         // B: the WHOLE batch (row stride of rand_uv and of the arrival counters), whatever range a launch covers
   int optimizer, t;      // 0 LM; 1 SGD; 2 ADAM (t = step index in execution order); 3 GN (cfg.gn)
   double beta1, beta2;
   double* adam;          // [B,6] first / second moment of the three pose components (ADAM only)
@@ -58,7 +59,7 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, int b, int lan
 #pragma unroll
     for (int k = 0; k < 14; ++k) s[k] = 0.0;
     for (int i = lane; i < a.nt; i += 64) {
-      const double* p = a.part + ((size_t)b * a.nt + i) * PART_N;
+      const double* p = a.part + ((size_t)b * a.part_ld + i) * PART_N;
 #pragma unroll
       for (int k = 0; k < 14; ++k)
         s[k] += COHERENT ? __hip_atomic_load(p + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : p[k];
@@ -120,8 +121,10 @@ struct AccumArgs {
   const float* conf;  // [B,h,w] or null
   const float* xyz;   // [h,w,3]
   const double* coef; // [B,COEF_N]
-  double* part;       // [B,nt,PART_N]
-  int A, h, w, row0, npix, TP, nt, B, xcd_affine;
+  double* part;       // [B,part_ld,PART_N]: a sample's rows do not move with the level, so that stream groups on different
+                      // steps (levels with different nt) never share a row
+  int A, h, w, row0, npix, TP, nt, part_ld, xcd_affine;
+  int b0, nb;         // this launch covers samples [b0, b0 + nb) of the batch; every per-sample array is indexed by the global b
   int hs, rskip;      // stored rows of grd/conf (h - grd_row_skip) and the skip itself
   const unsigned char* keep;   // dropout: [npix] of this step, 1 = pixel takes part; or null
   unsigned* ticket;   // [B] arrival counters of this step (zeroed before the loop): the LAST tile of a sample closes the step
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
   __shared__ float red[4][14];
   __shared__ double redd[14];
   int b, tile;
-  if (!lm_block_map(a.xcd_affine, a.nt, a.B, b, tile)) return;
+  if (!lm_block_map(a.xcd_affine, a.nt, a.nb, b, tile, a.b0)) return;
   const int t = threadIdx.x;
   const int p0 = tile * a.TP;
   const int np = min(a.TP, a.npix - p0);
@@ -283,7 +286,7 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
       case 13: v = redd[13]; break;
       default: break;
     }
-    __hip_atomic_store(a.part + ((size_t)b * a.nt + tile) * PART_N + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.part + ((size_t)b * a.part_ld + tile) * PART_N + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   const unsigned old = lm_draw_ticket(a.ticket + b, lane);      // (publication recipe: lm_common.h)
   if (old + 1 != (unsigned)a.nt) return;
@@ -294,8 +297,8 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
 // hla_s2g_config.count_in_view: the quantity jacobian.py:172 asserts on -- how many pixels of the WHOLE level map (all rows,
 // whatever their z > 0 mask) have satellite coordinates inside the map.  Geometry only; one thread per pixel.
 __global__ __launch_bounds__(256) void lm_inview_kernel(const double* __restrict__ coef, const float* __restrict__ xyz, int A,
-                                                        int npix, int* __restrict__ count) {
-  const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+                                                        int npix, int* __restrict__ count, int b0) {
+  const int b = b0 + blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
   const double* cf = coef + (size_t)b * COEF_N;
   int in = 0;
   if (p < npix) {
@@ -311,13 +314,14 @@ __global__ __launch_bounds__(256) void lm_inview_kernel(const double* __restrict
 
 // ---------------------------------------------------------------------------------------------
 static size_t ws_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B, size_t* off_coef, size_t* off_pose,
-                        size_t* off_part) {
+                        size_t* off_part, int* part_ld) {
   int max_nt = 1;
   for (int l = 0; l < cfg->n_levels; ++l) {
     const int npix = (lv[l].h - lv[l].row0) * lv[l].w;
     const int tp = lm_pick_tile_fwd(npix);
     max_nt = max(max_nt, (npix + tp - 1) / tp);
   }
+  *part_ld = max_nt;
   size_t o = 0;
   *off_coef = o; o += hla_align_up((size_t)B * COEF_N * sizeof(double), 256);
   *off_pose = o; o += hla_align_up((size_t)B * 3 * sizeof(float), 256);
@@ -330,7 +334,8 @@ static size_t ws_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int 
 
 extern "C" size_t hla_s2g_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B) {
   size_t a, b, c;
-  return ws_layout(cfg, levels, B, &a, &b, &c);
+  int ld;
+  return ws_layout(cfg, levels, B, &a, &b, &c, &ld);
 }
 
 template <bool W, typename F>
@@ -370,6 +375,53 @@ int hla_s2g_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_l
   return HLA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Stream groups.  Every launch of the loop ends in a tail during which the chip is nearly idle: one wave per sample reduces the
+// partials, solves in fp64 on one lane and writes the next coefficients, and a launch boundary follows.  Samples are independent
+// (and a sample's result does not depend on its batch mates, bit for bit), so the loop runs as LM_GROUPS sample ranges, each an
+// in-order chain of launches on its own stream: one group's gather fills the other's tail.  Group 0 runs on the caller's stream,
+// the others on streams the library owns (one set per device, created on first use); they fork from the caller's stream behind
+// the init launch and are joined on it before hla_s2g_lm_solve returns, so the caller sees one stream's worth of ordering.
+// Group boundaries are multiples of 8: the XCD-affine block map keeps every sample on the XCD it has in a whole-batch launch.
+// Both constants are reasoned, NOT measured (EXPERIMENTS.md, "LM loop on stream groups"): the tail to hide is shorter than one
+// group's gather, so a third group has nothing left to fill; 16 is the smallest batch whose two groups are whole XCD octets.
+constexpr int LM_GROUPS = 2;
+constexpr int LM_SPLIT_MIN = 16;    // smallest batch that is split
+static_assert(LM_GROUPS >= 2 && LM_GROUPS <= 4 && LM_SPLIT_MIN > 8, "a batch of up to 8 samples is one XCD octet and never splits");
+
+// One set per device, made on the first split call on it.  `mu` is held while a call enqueues its loop: the fork / join events
+// and the side streams are shared by every caller on the device (two callers interleaving record and wait would fork one
+// caller's side stream behind the other's init launch).
+struct LmSideStreams {
+  std::mutex mu;
+  bool ready = false, failed = false;
+  hipStream_t side[LM_GROUPS] = {};     // [0] unused: group 0 is the caller's stream
+  hipEvent_t fork = nullptr, join[LM_GROUPS] = {};
+};
+static LmSideStreams g_lm_side[64];
+
+// (mu held)  false: no stream to be had -- remembered, the loop stays on the caller's stream now and later
+static bool lm_side_create(LmSideStreams& S) {
+  if (S.ready || S.failed) return S.ready;
+  hipError_t r = hipEventCreateWithFlags(&S.fork, hipEventDisableTiming);
+  for (int g = 1; g < LM_GROUPS && r == hipSuccess; ++g) {
+    r = hipStreamCreateWithFlags(&S.side[g], hipStreamNonBlocking);
+    if (r == hipSuccess) r = hipEventCreateWithFlags(&S.join[g], hipEventDisableTiming);
+  }
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    if (S.fork) (void)hipEventDestroy(S.fork);
+    for (int g = 1; g < LM_GROUPS; ++g) {
+      if (S.join[g]) (void)hipEventDestroy(S.join[g]);
+      if (S.side[g]) (void)hipStreamDestroy(S.side[g]);
+    }
+    S.failed = true;
+    return false;
+  }
+  S.ready = true;
+  return true;
+}
+
 extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* lv, const float* R_FL,
                                 const float* T_FL, const float* pose0, const float* rand_uv, float* trace,
                                 double* normal_eq, void* workspace, size_t workspace_bytes, int B,
@@ -384,7 +436,8 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   const bool reinit = (cfg->ford || cfg->dof == 3) && newton;     // SGD_update / ADAM_update never re-initialise
   HLA_REQUIRE(!reinit || rand_uv, "hla_s2g_lm_solve: rand_uv required");
   size_t oc, op, opart;
-  const size_t need = ws_layout(cfg, lv, B, &oc, &op, &opart);
+  int part_ld;
+  const size_t need = ws_layout(cfg, lv, B, &oc, &op, &opart, &part_ld);
   if (workspace_bytes < need) {
     hla_set_error("hla_s2g_lm_solve: workspace %zu < %zu", workspace_bytes, need);
     return HLA_ERR_WORKSPACE;
@@ -416,7 +469,7 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   if (cfg->optimizer == 2) HLA_CHECK_HIP(hipMemsetAsync(adam, 0, (size_t)B * 6 * sizeof(double), st));
   SolveArgs sa{};
   sa.optimizer = cfg->optimizer; sa.beta1 = cfg->beta1; sa.beta2 = cfg->beta2; sa.adam = adam;
-  sa.pose = pose; sa.B = B; sa.reinit = reinit ? 1 : 0; sa.R_FL = R_FL; sa.T_FL = T_FL;
+  sa.pose = pose; sa.B = B; sa.part_ld = part_ld; sa.reinit = reinit ? 1 : 0; sa.R_FL = R_FL; sa.T_FL = T_FL;
   sa.cfg.gn = cfg->optimizer == 3 ? 1 : 0;
   sa.cfg.dof = cfg->dof; sa.cfg.use_hessian = sa.cfg.gn ? 0 : cfg->use_hessian;
   for (int i = 0; i < 3; ++i) sa.cfg.lam[i] = sa.cfg.gn ? 0.0 : cfg->damping[i];     // GN_update: delta = -H^-1 J^T W r
@@ -428,20 +481,52 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   hipLaunchKernelGGL(lm_solve, dim3(B), dim3(64), 0, st, sa);
   sa.zero_ticket = nullptr; sa.zero_steps = 0; sa.zero_pose = 0;
 
-  for (int k = 0; k < steps; ++k) {
+  // Sample ranges of the stream groups (comment above LM_GROUPS).  One group -- today's loop on the caller's stream -- for a
+  // small batch, under the event profiler (its event pairs sit on the launch stream, and a per-kernel time must stay the time
+  // of a kernel that has the chip to itself), while the caller's stream is being captured, and when no side stream can be had.
+  int ng = 1, gb0[LM_GROUPS + 1] = {0};
+  LmSideStreams* side = nullptr;
+  std::unique_lock<std::mutex> side_lock;
+  if (B >= LM_SPLIT_MIN && !hla_prof_on()) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    int d = -1;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = -1; }
+    if (cap == hipStreamCaptureStatusNone && d >= 0 && d < 64) {
+      side_lock = std::unique_lock<std::mutex>(g_lm_side[d].mu);
+      if (lm_side_create(g_lm_side[d])) side = &g_lm_side[d];
+      else side_lock.unlock();
+    }
+  }
+  if (side) {
+    const int oct = (B + 7) / 8;
+    ng = oct < LM_GROUPS ? oct : LM_GROUPS;
+    for (int g = 0; g < ng; ++g) gb0[g + 1] = gb0[g] + 8 * (oct / ng + (g < oct % ng ? 1 : 0));
+  }
+  gb0[ng] = B;
+  hipStream_t gst[LM_GROUPS];
+  gst[0] = st;
+  int forked = 0;                                        // side streams that wait on the fork event: they are joined whatever follows
+  hipError_t err = hipSuccess;
+  if (ng > 1) {
+    err = hipEventRecord(side->fork, st);                // behind the pose copy, the memsets and the init launch
+    for (int g = 1; g < ng && err == hipSuccess; ++g) {
+      gst[g] = side->side[g];
+      err = hipStreamWaitEvent(gst[g], side->fork, 0);
+      if (err == hipSuccess) forked = g;
+    }
+  }
+
+  // steps interleaved over the groups: each group's launches stay in order on its own stream
+  for (int k = 0; k < steps && err == hipSuccess; ++k) {
     const int l = step_level(k), it = step_iter(k);
     const hla_s2g_level& v = lv[l];
-    if (count)
-      hipLaunchKernelGGL(lm_inview_kernel, dim3((v.h * v.w + 255) / 256, B), dim3(256), 0, st, coef, v.xyz, v.A, v.h * v.w,
-                         in_view + (size_t)k * B);
     AccumArgs aa{};
     aa.sat = v.sat_feat; aa.grd = v.grd_feat; aa.conf = v.grd_conf; aa.xyz = v.xyz; aa.coef = coef; aa.part = part;
     aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.row0 = v.row0; aa.npix = (v.h - v.row0) * v.w;
     aa.hs = v.h - v.grd_row_skip; aa.rskip = v.grd_row_skip;
     aa.keep = cfg->keep ? cfg->keep + (size_t)k * cfg->keep_stride : nullptr;
-    aa.TP = lm_pick_tile_fwd(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.B = B;
+    aa.TP = lm_pick_tile_fwd(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.part_ld = part_ld;
     aa.xcd_affine = (B >= 8) ? 1 : 0;
-    const int nblk = aa.xcd_affine ? 8 * ((B + 7) / 8) * aa.nt : B * aa.nt;
     aa.ticket = ticket + (size_t)k * B;
     // the step's closing solve runs inside the same launch (last tile of each sample): its arguments
     sa.t = k;
@@ -453,12 +538,28 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
     if (k + 1 < steps) { sa.coef = coef; sa.next = geom(step_level(k + 1)); }
     else sa.coef = nullptr;
     const double esz = v.feat_dtype == HLA_F32 ? 4.0 : 2.0;
-    hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
-                   (double)B * ((double)v.A * v.A + (double)aa.npix) * v.C * esz, st);
-    if (cfg->using_weight && newton) launch_accum<true>(v.C, v.feat_dtype, dim3(nblk), st, aa, sa);   // SGD / ADAM ignore the confidence
-    else launch_accum<false>(v.C, v.feat_dtype, dim3(nblk), st, aa, sa);
-    hla_prof_end(st);
+    for (int g = 0; g < ng; ++g) {
+      hipStream_t gs = gst[g];
+      aa.b0 = gb0[g]; aa.nb = gb0[g + 1] - gb0[g];
+      if (count)
+        hipLaunchKernelGGL(lm_inview_kernel, dim3((v.h * v.w + 255) / 256, aa.nb), dim3(256), 0, gs, coef, v.xyz, v.A, v.h * v.w,
+                           in_view + (size_t)k * B, aa.b0);
+      const int nblk = aa.xcd_affine ? 8 * ((aa.nb + 7) / 8) * aa.nt : aa.nb * aa.nt;
+      hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
+                     (double)aa.nb * ((double)v.A * v.A + (double)aa.npix) * v.C * esz, gs);
+      if (cfg->using_weight && newton) launch_accum<true>(v.C, v.feat_dtype, dim3(nblk), gs, aa, sa);   // SGD / ADAM ignore the confidence
+      else launch_accum<false>(v.C, v.feat_dtype, dim3(nblk), gs, aa, sa);
+      hla_prof_end(gs);
+    }
   }
+  // join: behind this point the caller's stream orders every launch of the loop -- also after a failure above, so that work
+  // already on a side stream (it touches the workspace) is never left outside the caller's ordering
+  for (int g = 1; g <= forked; ++g) {
+    hipError_t e = hipEventRecord(side->join[g], gst[g]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join[g], 0);
+    if (err == hipSuccess) err = e;
+  }
+  HLA_CHECK_HIP(err);
   HLA_CHECK_HIP(hipGetLastError());
   return HLA_OK;
 }

@@ -11,10 +11,12 @@
  *     the library never allocates or frees device memory and keeps no global state
  *     except a thread-local last-error string, the opt-in timing log (hla_prof_*) and
  *     per-device "kernel attribute set / refused" bits (dynamic-LDS opt-in of the large-LDS kernels; a refused request
- *     makes hla_vgg_backward fall back to its smaller-footprint weight-gradient kernels)
+ *     makes hla_vgg_backward fall back to its smaller-footprint weight-gradient kernels), and one internal stream per device with
+ *     its fork / join events (hla_s2g_lm_solve)
  *   - kernels are launched on the CURRENT device: the caller makes the device that owns the
  *     buffers and the stream current before the call (highlyaccurate_amd/_lib.py on_device)
- *   - all work is enqueued on the given hipStream_t (passed as void*); no implicit
+ *   - all work is enqueued on the given hipStream_t (passed as void*) -- or, inside hla_s2g_lm_solve, on an internal
+ *     stream that is forked from it and joined on it before the call returns; no implicit
  *     synchronisation, no host<->device copies except the small [host] structs
  *     passed by value
  *   - return 0 on success, negative hla_status on error; hla_last_error() explains
@@ -306,7 +308,10 @@ size_t hla_s2g_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* l
  * rand_uv  [n_steps,2,B] fp32: the (rand_u, rand_v) re-initialisation draws of every step
  *          (models_kitti.py:1028-1033), drawn by the caller from torch's CPU generator
  * trace    [B,n_iters,n_levels,3] fp32 out: (shift_u, shift_v, theta) after every step
- * normal_eq[n_steps,B,16] fp64 out or NULL: ||s||^2, ||g||^2, H(6), J^T s (3), J^T g (3), pixels in view (count_in_view), pad */
+ * normal_eq[n_steps,B,16] fp64 out or NULL: ||s||^2, ||g||^2, H(6), J^T s (3), J^T g (3), pixels in view (count_in_view), pad
+ * stream   from B = 16 on the loop may run part of the batch on an internal stream of the library (one per device, created on
+ *          first use); it starts behind the work already on `stream` and is joined on `stream` before the call returns, so
+ *          `stream` orders the whole call as if every launch were on it.  Not while `stream` is being captured. */
 int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* levels, const float* R_FL,
                      const float* T_FL, const float* pose0, const float* rand_uv, float* trace,
                      double* normal_eq, void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
