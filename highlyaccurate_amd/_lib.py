@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class HlaError(RuntimeError):
@@ -152,6 +152,8 @@ def load() -> C.CDLL:
     lib.hla_sat_tile.argtypes = [vp, vp, vp, i, i, i, vp]
     lib.hla_grid_sample.restype = i
     lib.hla_grid_sample.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
+    lib.hla_grid_sample_bwd.restype = i
+    lib.hla_grid_sample_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
     lib.hla_s2g_workspace_bytes.restype = sz
     lib.hla_s2g_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i]
     lib.hla_g2s_workspace_bytes.restype = sz

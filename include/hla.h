@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 22
+#define HLA_ABI_VERSION 23
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -234,6 +234,30 @@ int hla_resize_bilinear(const unsigned char* src, const int* hbounds, const int*
  * jac     [M,N,H,W,2] or NULL;    out [N,H,W,C] NHWC;  jac_out [M,N,H,W,C] NHWC or NULL */
 int hla_grid_sample(const float* image, const float* optical, const float* jac, float* out, float* jac_out,
                     int N, int C, int IH, int IW, int H, int W, int M, hla_stream_t stream);
+
+/* Backward of hla_grid_sample: what autograd derives from the reference's chain of torch ops (jacobian.py:168-198, with
+ * the corner coordinates constants as under its no_grad block, jacobian.py:146-166), in one kernel.  Same layouts.
+ *   image, optical, jac   the forward's inputs (jac may be NULL: M is then ignored)
+ *   d_out     [N,H,W,C]   cotangent of out,      NULL = zeros
+ *   d_jac_out [M,N,H,W,C] cotangent of jac_out,  NULL = zeros;  needs jac and M > 0
+ *   d_image   [N,IH,IW,C] ACCUMULATED into (the caller zero-fills it), NULL = not wanted
+ *   d_optical [N,H,W,2]   WRITTEN,  NULL = not wanted
+ *   d_jac     [M,N,H,W,2] WRITTEN,  NULL = not wanted;  needs jac and M > 0
+ * A NULL output removes its work from the kernel, not only its store.  With both cotangents NULL, or all three outputs
+ * NULL, no kernel is launched (the wanted written outputs are zero-filled, d_image is left as it is).
+ * With the forward's rules  inb = 0<=ix<=IW-1 && 0<=iy<=IH-1,  x0 = floor(ix), x1 = min(x0+1, IW-1), y0, y1 alike,
+ * wx0 = x1-ix, wx1 = ix-x0, wy0 = y1-iy, wy1 = iy-y0,  the taps nw, ne, sw, se,  g = d_out[c],
+ * a[c] = sum_m d_jac_out[m][c] jac[m].x,  b[c] = sum_m d_jac_out[m][c] jac[m].y:
+ *   ddx = wy0 (ne-nw) + wy1 (se-sw)     ddy = wx0 (sw-nw) + wx1 (se-ne)     cross = nw-ne-sw+se
+ *   d_image[nw] += g wx0 wy0 - a wy0 - b wx0        d_image[ne] += g wx1 wy0 + a wy0 - b wx1
+ *   d_image[sw] += g wx0 wy1 - a wy1 + b wx0        d_image[se] += g wx1 wy1 + a wy1 + b wx1
+ *   d_optical = ( sum_c g ddx + b cross ,  sum_c g ddy + a cross )     (cross: jac_out through the bilinear weights)
+ *   d_jac[m]  = ( sum_c d_jac_out[m][c] ddx ,  sum_c d_jac_out[m][c] ddy )
+ * and everything is zero for a sample that is not in bounds.  Any C and any M.  d_image is summed with fp32 atomic adds,
+ * whose order varies: it is NOT bitwise reproducible from run to run (d_optical and d_jac are). */
+int hla_grid_sample_bwd(const float* image, const float* optical, const float* jac, const float* d_out,
+                        const float* d_jac_out, float* d_image, float* d_optical, float* d_jac,
+                        int N, int C, int IH, int IW, int H, int W, int M, hla_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * The LM pose loop: project_map_to_grd + LM_update, N_iters x levels steps
