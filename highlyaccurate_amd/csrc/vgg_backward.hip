@@ -3,1023 +3,11 @@
 //   * data gradients: every conv's dgrad is the SAME MFMA implicit-GEMM kernel as the forward pass, run on
 //     transposed + tap-flipped packed weights, with the ReLU mask / gradient fan-in / "sum 2x2" (nearest-upsample
 //     backward) fused into its epilogue and the max-pool routing (argmax) fused into its loader
-//   * weight gradients: wgrad_kernel, an MFMA GEMM that contracts over PIXELS.  Both operands are then "k-major"
-//     in NHWC (pixels are rows); for bf16 the fragments are fetched with gfx950's transpose read
-//     ds_read_b64_tr_b16 straight from the same [pixel][channel] LDS tiles the forward kernel uses
-//     (tools/probes/tr16_probe.hip documents the lane semantics), for fp32 a lane needs one element per MFMA
-//     so plain ds_read_b32 suffices.  Bias gradients ride along as one extra MFMA against an all-ones fragment.
+//   * weight gradients: MFMA GEMMs that contract over PIXELS (the kernels: wgrad_kernels.h; planned and launched here)
 #include <vector>
 #include <stdlib.h>
-#include "conv_kernels.h"
+#include "wgrad_kernels.h"
 #include "vgg_layers.h"
-
-// (frag_kmajor / frag_ones / KStep: conv_kernels.h -- the fused conv0 weight gradient in the data-gradient epilogue uses them too)
-
-// ---------------------------------------------------------------------------------------------
-constexpr int WG_TH = 4;                                  // pixel tile of the weight-gradient kernels: 4 rows x 32 px
-struct WgradArgs {
-  const void* x1; const void* x2;      // conv input (stored post-ReLU activations); virtual upsample+concat as forward
-  const void* g;                       // d(loss)/d(conv output) NHWC T [B,H,W,Cout], or the pooled map's gradient
-  const unsigned char* g_unpool;       //   [B,H/2,W/2,Cout] + forward argmax (virtual unpool) when non-null
-  float* part;                         // [KS][Cout][Cin][9] partial sums
-  float* bpart;                        // [KS][Cout] partial bias gradients, or null
-  int C1, C2, up1, B, H, W, Cout, Cin, tiles_x, tiles_y, ntile, KS;
-  int row_begin;                       // first pixel row that carries gradient (even with g_unpool); rows above are skipped
-  const int* dyn;                      // data-dependent launch (bwd_fan_kernel): base of the device-side tables, or null
-  int dyn_desc;                        //   int offset of {live tiles per sample, list offset, band table of g or -1}: only the
-                                       //   listed tiles are visited, and g reads as zero outside the part its producer wrote
-};
-
-// tile enumeration of the weight-gradient kernels
-struct WgTiles {
-  const int* dyn; int nl, list, gb, ntile, tiles_x, tiles_y, row_begin, H, W, gsh;
-  __device__ __forceinline__ WgTiles(const int* dyn_, int desc, int H_, int W_, int row_begin_, int tiles_x_, int tiles_y_,
-                                     int ntile_all, int B, int gsh_)
-      : dyn(dyn_), nl(0), list(0), gb(-1), ntile(ntile_all), tiles_x(tiles_x_), tiles_y(tiles_y_), row_begin(row_begin_),
-        H(H_), W(W_), gsh(gsh_) {
-    if (!dyn) return;
-    nl = dyn[desc]; list = dyn[desc + 1]; gb = dyn[desc + 2];
-    ntile = nl * B;
-  }
-  // origin of a tile and the column interval [gx0, gx1) of this launch's coordinates in which g may be read
-  __device__ __forceinline__ void origin(int tile, int& b, int& y0, int& x0, int& gx0, int& gx1) const {
-    gx0 = 0; gx1 = W;
-    if (dyn) {
-      b = tile / nl;
-      const int e = dyn[list + tile % nl];
-      y0 = (e >> 16) * WG_TH; x0 = (e & 0xffff) * 32;
-      if (gb >= 0) {
-        const int band = (y0 >> gsh) >> 3;
-        gx0 = dyn[gb + 2 * band] << gsh;
-        gx1 = min(dyn[gb + 2 * band + 1] << gsh, W);
-      }
-    } else {
-      int q = tile;
-      x0 = (q % tiles_x) * 32; q /= tiles_x;
-      y0 = row_begin + (q % tiles_y) * WG_TH;
-      b = q / tiles_y;
-    }
-  }
-};
-
-template <typename T> constexpr int wg_stride() { return 64 * (int)sizeof(T) + 16; }
-template <typename T> constexpr int wg_lds_bytes() { return ((WG_TH + 2) * HWID + WG_TH * 32) * wg_stride<T>(); }
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
-  constexpr int EPL = 16 / sizeof(T), STR = wg_stride<T>(), PPX = 64 * (int)sizeof(T) / 16;   // 16-B pieces per pixel
-  constexpr int XPIX = (WG_TH + 2) * HWID, GPIX = WG_TH * 32, KPX = KStep<T>::PX;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Xs = smem;
-  char* Gs = smem + XPIX * STR;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, ct = wv >> 1, it = wv & 1;
-  const int ks = blockIdx.x, ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
-  const bool first = ci0 < a.C1;
-  const T* xsrc = first ? (const T*)a.x1 : (const T*)a.x2;
-  const int Cs = first ? a.C1 : a.C2, coff = first ? ci0 : ci0 - a.C1, sh = (first && a.up1) ? 1 : 0;
-  const int Hs = a.H >> sh, Ws = a.W >> sh;
-  const int gsh = a.g_unpool ? 1 : 0, Hg = a.H >> gsh, Wg = a.W >> gsh;
-  const bool want_bias = a.bpart && blockIdx.y == 0 && it == 0;
-
-  f32x16 acc[9], accb;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accb[r] = 0.f;
-  const uint4 ones = frag_ones<T>();
-
-  // Register-staged tile loads: all of a tile's 16-B pieces are requested back to back (memory-level parallelism).  (Issuing
-  // the NEXT tile's requests before the current tile's MFMA phase needs the staging registers live across it: one workgroup
-  // per CU, measured slower.)
-  constexpr int NX = (XPIX * PPX + 255) / 256, NG = GPIX * PPX / 256, PSTEP = 256 / PPX;
-  const int part = t % PPX, pix0 = t / PPX;
-  uint4 xr[NX], gr[NG];
-  unsigned long long gid[NG];
-  const WgTiles tl(a.dyn, a.dyn_desc, a.H, a.W, a.row_begin, a.tiles_x, a.tiles_y, a.ntile, a.B, a.g_unpool ? 1 : 0);
-  int gx0, gx1;                         // (set by every tile_origin call: the interval of the tile being loaded)
-  auto tile_origin = [&](int tile, int& b, int& y0, int& x0) { tl.origin(tile, b, y0, x0, gx0, gx1); };
-  // raw buffer loads through one descriptor per operand and sample: a piece outside the image / the written part of g gets an
-  // offset beyond the range and reads zeros -- no branch around a load (hipcc ends every branch-guarded load's block with an
-  // s_waitcnt vmcnt(0): the exact-fp32 kernel's 29 loads per tile were 29 dependent round trips)
-  constexpr int OOB = (int)0x80000000;
-  const size_t xs_bytes = (size_t)Hs * Ws * Cs * sizeof(T), gs_bytes = (size_t)Hg * Wg * a.Cout * sizeof(T);
-  auto rsrc = [](const void* base, size_t bytes) __attribute__((always_inline)) {
-    const unsigned long long p = (unsigned long long)base;
-    const void* pu = (const void*)(((unsigned long long)__builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32)) << 32) |
-                                   (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)pu, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-  };
-  typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
-  auto load_x = [&](int tile, int lo, int hi) {
-    int b, y0, x0;
-    tile_origin(tile, b, y0, x0);
-    const __amdgpu_buffer_rsrc_t rx = rsrc((const char*)xsrc + (size_t)b * xs_bytes, xs_bytes);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {                     // input halo tile, zero outside the image
-      if (i < lo || i >= hi) continue;
-      const int pix = pix0 + i * PSTEP;
-      const int hy = pix / HWID, hx = pix - hy * HWID, y = y0 - 1 + hy, x = x0 - 1 + hx;
-      const bool ok = pix < XPIX && y >= 0 && y < a.H && x >= 0 && x < a.W;
-      const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? (((y >> sh) * Ws + (x >> sh)) * Cs + coff + part * EPL) * (int)sizeof(T) : OOB, 0, 0);
-      xr[i] = make_uint4(v.x, v.y, v.z, v.w);
-    }
-  };
-  auto load_g = [&](int tile, int lo, int hi) {
-    int b, y0, x0;
-    tile_origin(tile, b, y0, x0);
-    const __amdgpu_buffer_rsrc_t rg = rsrc((const char*)a.g + (size_t)b * gs_bytes, gs_bytes);
-    const __amdgpu_buffer_rsrc_t ri = rsrc(a.g_unpool ? a.g_unpool + (size_t)b * (gs_bytes / sizeof(T)) : (const unsigned char*)a.g,
-                                           a.g_unpool ? gs_bytes / sizeof(T) : 0);
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {                     // output-gradient tile (virtual unpool: + the forward argmax)
-      if (i < lo || i >= hi) continue;
-      const int pix = pix0 + i * PSTEP;
-      const int y = y0 + pix / 32, x = x0 + pix % 32;
-      const bool ok = y < a.H && x >= gx0 && x < gx1;
-      const int e0 = ok ? ((y >> gsh) * Wg + (x >> gsh)) * a.Cout + co0 + part * EPL : OOB;
-      const u32x4w v = __builtin_amdgcn_raw_buffer_load_b128(rg, ok ? e0 * (int)sizeof(T) : OOB, 0, 0);
-      gr[i] = make_uint4(v.x, v.y, v.z, v.w);
-      unsigned long long id = 0;                       // (no unpool: a zero-sized descriptor, reads 0)
-      if constexpr (EPL == 8) { const u32x2w w = __builtin_amdgcn_raw_buffer_load_b64(ri, e0, 0, 0); id = (unsigned long long)w.x | ((unsigned long long)w.y << 32); }
-      else id = __builtin_amdgcn_raw_buffer_load_b32(ri, e0, 0, 0);
-      gid[i] = id;
-    }
-  };
-  auto store_x = [&](int lo, int hi) {
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-      if (i < lo || i >= hi) continue;
-      const int pix = pix0 + i * PSTEP;
-      if (pix < XPIX) *(uint4*)(Xs + pix * STR + part * 16) = xr[i];
-    }
-  };
-  auto store_g = [&](int tile, int lo, int hi) {
-    int b, y0, x0;
-    tile_origin(tile, b, y0, x0);
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-      if (i < lo || i >= hi) continue;
-      const int pix = pix0 + i * PSTEP;
-      uint4 v = gr[i];
-      if (a.g_unpool) {                                // keep the elements whose forward argmax is this (y&1, x&1)
-        const unsigned pos = (((y0 + pix / 32) & 1) << 1) | ((x0 + pix % 32) & 1);
-        T ev[EPL];
-        unsigned char id[8];
-        __builtin_memcpy(ev, &v, 16);
-        __builtin_memcpy(id, &gid[i], 8);
-#pragma unroll
-        for (int k = 0; k < EPL; ++k) if (id[k] != pos) ev[k] = (T)0.f;
-        __builtin_memcpy(&v, ev, 16);
-      }
-      *(uint4*)(Gs + pix * STR + part * 16) = v;
-    }
-  };
-
-  for (int tile = ks; tile < tl.ntile; tile += a.KS) {
-    if (sizeof(T) == 2) {
-      load_x(tile, 0, NX); load_g(tile, 0, NG);
-      __syncthreads();                                 // previous tile fully consumed
-      store_x(0, NX);
-      store_g(tile, 0, NG);
-    } else {                                           // fp32 (parity mode): batches of 4 pieces = 16 staging registers
-      __syncthreads();
-#pragma unroll
-      for (int lo = 0; lo < NX; lo += 4) { load_x(tile, lo, lo + 4); store_x(lo, lo + 4); }
-#pragma unroll
-      for (int lo = 0; lo < NG; lo += 4) { load_g(tile, lo, lo + 4); store_g(tile, lo, lo + 4); }
-    }
-    __syncthreads();
-    // G fragments of the whole tile stay in registers; every X fragment (halo row rho, column shift kx, K-step kk) is
-    // fetched ONCE and feeds the up to three taps ky with r = rho - ky inside the tile  (halves the LDS reads per MFMA)
-    // (K-steps are taken two at a time so that the resident G fragments cost 32 VGPRs for every dtype)
-#pragma unroll 1
-    for (int kk0 = 0; kk0 < 32 / KPX; kk0 += 2) {
-      uint4 Af[WG_TH][2];
-#pragma unroll
-      for (int r = 0; r < WG_TH; ++r)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          Af[r][kk] = frag_kmajor<T>(Gs, STR, r * 32 + (kk0 + kk) * KPX, ct * 32, lane);
-          if (want_bias) mma16<T>(accb, Af[r][kk], ones);
-        }
-#pragma unroll
-      for (int rho = 0; rho < WG_TH + 2; ++rho) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            const uint4 Bf = frag_kmajor<T>(Xs, STR, rho * HWID + kx + (kk0 + kk) * KPX, it * 32, lane);
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-              const int r = rho - ky;
-              if (r >= 0 && r < WG_TH) mma16<T>(acc[ky * 3 + kx], Af[r][kk], Bf);
-            }
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-  // D[i = co][j = ci]: lane -> ci = ci0 + it*32 + (lane&31); reg r -> co = co0 + ct*32 + (r&3) + 8(r>>2) + 4(lane>>5)
-  const int ci = ci0 + it * 32 + (lane & 31), g5 = lane >> 5;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g5;
-    float* o = a.part + (((size_t)ks * a.Cout + co) * a.Cin + ci) * 9;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    if (want_bias && (lane & 31) == 0) a.bpart[(size_t)ks * a.Cout + co] = accb[r];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// wgrad_dma_kernel: the same contraction for the 16-bit types with the tiles fetched HBM -> LDS by LDS-DMA and the NEXT tile's
-// loads in flight under the current tile's MFMA phase.  wgrad_kernel stages a tile through 44 registers and runs
-// load -> barrier -> LDS write -> barrier -> MFMA with nothing but the co-resident workgroup to overlap the phases; here the X
-// halo tile is double-buffered, and the G tile -- whose fragments all sit in registers for the whole MFMA phase -- is refilled in
-// place as soon as every wave holds them: 2 x 28 KB + 16 KB = 72 KB, still two workgroups per CU, and no staging registers.
-// LDS image: 128-B pixels with NO pad (a DMA's image is lane-linear); the transposing reads stay conflict-free through an XOR of
-// the 16-B chunk index with 2 (pixel & 3), applied to the SOURCE chunk a lane fetches and to the read address: a 16-lane group
-// of ds_read_b64_tr_b16 touches 4 consecutive pixels x 32 B, which the key spreads over 4 different 32-B segments of the two
-// 128-B bank halves.  Zero fill (outside the image / the written part of g) by the buffer descriptors' range check.
-// Plain launches only (no virtual unpool: that loader masks elements on the way into LDS).
-constexpr int WGD_XBLK = 28, WGD_GBLK = 16;             // 1-KiB blocks (8 pixels) per X buffer (204 pixels + pad) / G buffer
-constexpr int wgd_lds_bytes() { return (2 * WGD_XBLK + WGD_GBLK) * 1024; }
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(WgradArgs a) {
-  static_assert(sizeof(T) == 2, "16-bit types");
-  constexpr int XPIX = (WG_TH + 2) * HWID, XB = WGD_XBLK * 1024, NXJ = WGD_XBLK / 4, NGJ = WGD_GBLK / 4;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Gs = smem + 2 * XB;
-  const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), ct = wv >> 1, it = wv & 1;
-  const int ks = blockIdx.x, ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
-  const bool first = ci0 < a.C1;
-  const char* xsrc = first ? (const char*)a.x1 : (const char*)a.x2;
-  const int Cs = first ? a.C1 : a.C2, coff = first ? ci0 : ci0 - a.C1, sh = (first && a.up1) ? 1 : 0;
-  const int Hs = a.H >> sh, Ws = a.W >> sh;
-  const bool want_bias = a.bpart && blockIdx.y == 0 && it == 0;
-
-  f32x16 acc[9], accb;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accb[r] = 0.f;
-  const uint4 ones = frag_ones<T>();
-
-  // what a lane fetches: block k = wv + 4 j of a buffer, pixel 8 k + (lane >> 3) of the tile, LDS chunk position lane & 7, which holds
-  // channel chunk (lane & 7) ^ 2 (pixel & 3)
-  const int q = lane >> 3, cp = lane & 7;
-  int xhy[NXJ], xhx[NXJ], xc[NXJ];
-#pragma unroll
-  for (int j = 0; j < NXJ; ++j) {
-    const int p = 8 * (wv + 4 * j) + q;
-    xhy[j] = p < XPIX ? p / HWID : 1 << 20;            // (past the tile: never inside the image -> zeros into the pad)
-    xhx[j] = p % HWID;
-    xc[j] = (cp ^ (2 * (p & 3))) * 16;
-  }
-  typedef int rsrc_t __attribute__((ext_vector_type(4)));
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)smem) + wv * 1024;
-  const WgTiles tl(a.dyn, a.dyn_desc, a.H, a.W, a.row_begin, a.tiles_x, a.tiles_y, a.ntile, a.B, 0);
-  auto dma_tile = [&](int tile, int xbuf) __attribute__((always_inline)) {
-    int b, y0, x0, gx0, gx1;
-    tl.origin(tile, b, y0, x0, gx0, gx1);
-    const unsigned long long px = (unsigned long long)xsrc + (size_t)b * Hs * Ws * Cs * 2;
-    const unsigned long long pg = (unsigned long long)a.g + (size_t)b * a.H * a.W * a.Cout * 2;
-    rsrc_t rx, rg;
-    rx[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)px); rx[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(px >> 32));
-    rx[2] = __builtin_amdgcn_readfirstlane(Hs * Ws * Cs * 2); rx[3] = 0x00020000;
-    rg[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)pg); rg[1] = __builtin_amdgcn_readfirstlane((int)(unsigned)(pg >> 32));
-    rg[2] = __builtin_amdgcn_readfirstlane(a.H * a.W * a.Cout * 2); rg[3] = 0x00020000;
-    int ox[NXJ], og[NGJ];
-#pragma unroll
-    for (int j = 0; j < NXJ; ++j) {
-      const int y = y0 - 1 + xhy[j], x = x0 - 1 + xhx[j];
-      const bool ok = y >= 0 && y < a.H && x >= 0 && x < a.W;
-      ox[j] = ok ? (((y >> sh) * Ws + (x >> sh)) * Cs + coff) * 2 + xc[j] : (int)0x80000000;
-    }
-#pragma unroll
-    for (int j = 0; j < NGJ; ++j) {
-      const int p = 8 * (wv + 4 * j) + q, y = y0 + p / 32, x = x0 + p % 32;
-      const bool ok = y < a.H && x >= gx0 && x < gx1;
-      og[j] = ok ? ((y * a.W + x) * a.Cout + co0) * 2 + (cp ^ (2 * (p & 3))) * 16 : (int)0x80000000;
-    }
-    const unsigned dx = lds0 + xbuf * XB, dg = lds0 + 2 * XB;
-    const int zero = 0;
-    unsigned keep;
-    static_assert(NXJ == 7 && NGJ == 4, "asm below");
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %10\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %8, %9 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %8, %9 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %8, %9 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %8, %9 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %8, %9 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %6, %8, %9 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %7, %8, %9 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(ox[0]), "v"(ox[1]), "v"(ox[2]), "v"(ox[3]), "v"(ox[4]), "v"(ox[5]), "v"(ox[6]), "s"(rx), "s"(zero), "s"(dx)
-                 : "memory", "scc");
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %5, %6 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %5, %6 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %5, %6 offen lds\n\t"
-                 "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %5, %6 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(og[0]), "v"(og[1]), "v"(og[2]), "v"(og[3]), "s"(rg), "s"(zero), "s"(dg)
-                 : "memory", "scc");
-  };
-  // read side: byte offset of this lane's 8 bytes inside a buffer for a fragment whose first pixel px0 has px0 & 3 == m, WITHOUT
-  // px0 * 128 (compile-time: it goes into the instruction's offset): row part + swizzled column part
-  const int tq = (lane & 15) >> 2, g5 = lane >> 5;
-  int scG[4], scX[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int key = (2 * ((m + tq) & 3)) << 4;
-    const int rowb = (tq + 8 * g5) * 128;
-    scG[m] = rowb + ((((ct * 32 + 16 * ((lane >> 4) & 1)) + 4 * (lane & 3)) * 2) ^ key);
-    scX[m] = rowb + ((((it * 32 + 16 * ((lane >> 4) & 1)) + 4 * (lane & 3)) * 2) ^ key);
-  }
-  auto frag = [&](const char* buf, int px0, const int (&sc)[4]) __attribute__((always_inline)) {
-    const char* p = buf + px0 * 128 + sc[px0 & 3];
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p + 4 * 128));
-    uint4 r;
-    __builtin_memcpy(&r.x, &lo, 8);
-    __builtin_memcpy(&r.z, &hi, 8);
-    return r;
-  };
-
-  int tile = ks, cur = 0;
-  if (tile < tl.ntile) dma_tile(tile, 0);
-  for (; tile < tl.ntile; tile += a.KS) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's share of X(tile) and G(tile) has landed ...
-    __syncthreads();                                       // ... and so has everyone's; the previous tile's MFMA phase is over
-    const char* Xs = smem + cur * XB;
-    uint4 Af[WG_TH][2];
-#pragma unroll
-    for (int r = 0; r < WG_TH; ++r)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) Af[r][kk] = frag(Gs, r * 32 + kk * 16, scG);
-    __syncthreads();                                       // every wave holds its G fragments: the G buffer can be refilled
-    if (tile + a.KS < tl.ntile) dma_tile(tile + a.KS, cur ^ 1);
-    if (want_bias) {
-#pragma unroll
-      for (int r = 0; r < WG_TH; ++r)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) mma16<T>(accb, Af[r][kk], ones);
-    }
-#pragma unroll
-    for (int rho = 0; rho < WG_TH + 2; ++rho) {
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const uint4 Bf = frag(Xs, rho * HWID + kx + kk * 16, scX);
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
-            const int r = rho - ky;
-            if (r >= 0 && r < WG_TH) mma16<T>(acc[ky * 3 + kx], Af[r][kk], Bf);
-          }
-        }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    cur ^= 1;
-  }
-  const int ci = ci0 + it * 32 + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g5;
-    float* o = a.part + (((size_t)ks * a.Cout + co) * a.Cin + ci) * 9;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    if (want_bias && (lane & 31) == 0) a.bpart[(size_t)ks * a.Cout + co] = accb[r];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// wgrad_ws_kernel: the 16-bit weight gradient, WAVE-SPECIALISED (round 5; the split-mode twin is wgrad_split_ws_kernel below, which
-// explains the scheme).  One 8-wave workgroup per CU: waves 4-7 fetch a 4-row tile's pieces two tiles ahead through registers
-// (raw buffer loads, zero fill by the descriptors' range check, the virtual unpool's argmax mask applied on the way into LDS) and
-// write them into the idle one of two LDS buffers; waves 0-3 -- one per SIMD -- only read fragments and multiply, the next halo
-// row's fragments requested ahead of the current row's MFMAs.  One barrier per tile.  Plain AND un-pooling launches (wgrad_kernel
-// and wgrad_dma_kernel ran load -> barrier -> MFMA phases in every wave: 0.30 of the MFMA peak where the forward reaches 0.48).
-template <typename T> constexpr int wg_ws_buf_bytes() { return ((WG_TH + 2) * HWID + WG_TH * 32) * wg_stride<T>(); }
-template <typename T> constexpr int wg_ws_lds_bytes() { return 2 * wg_ws_buf_bytes<T>(); }
-
-template <typename T>
-__global__ __launch_bounds__(512, 1) void wgrad_ws_kernel(WgradArgs a) {
-  static_assert(sizeof(T) == 2, "16-bit types");
-  constexpr int STR = wg_stride<T>(), PPX = 8, XPIX = (WG_TH + 2) * HWID, GPIX = WG_TH * 32, KPX = 16, BUFB = wg_ws_buf_bytes<T>();
-  constexpr int oX = 0, oG = XPIX * STR;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const bool loader = wv >= 4;
-  const int ks = blockIdx.x, ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
-  const bool first = ci0 < a.C1;
-  const T* xsrc = first ? (const T*)a.x1 : (const T*)a.x2;
-  const int Cs = first ? a.C1 : a.C2, coff = first ? ci0 : ci0 - a.C1, sh = (first && a.up1) ? 1 : 0;
-  const int Hs = a.H >> sh, Ws = a.W >> sh;
-  const int gsh = a.g_unpool ? 1 : 0, Hg = a.H >> gsh, Wg = a.W >> gsh;
-  const WgTiles tl(a.dyn, a.dyn_desc, a.H, a.W, a.row_begin, a.tiles_x, a.tiles_y, a.ntile, a.B, a.g_unpool ? 1 : 0);
-  const int ntile = tl.ntile;
-  const int t_first = ks < ntile ? ks : -1;
-  auto next_tile = [&](int tt) { tt += a.KS; return tt < ntile ? tt : -1; };
-
-  if (loader) {
-    const int tl_ = t - 256, part = tl_ % PPX, pix0 = tl_ / PPX;
-    constexpr int NX = (XPIX * PPX + 255) / 256, NG = GPIX * PPX / 256, PSTEP = 256 / PPX;
-    static_assert(GPIX * PPX % 256 == 0, "gradient tile pieces per thread");
-    constexpr int OOB = (int)0x80000000;
-    const size_t xs_bytes = (size_t)Hs * Ws * Cs * 2, gs_bytes = (size_t)Hg * Wg * a.Cout * 2;
-    auto rsrc = [](const void* base, size_t bytes) __attribute__((always_inline)) {
-      const unsigned long long p = (unsigned long long)base;
-      const void* pu = (const void*)(((unsigned long long)__builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32)) << 32) |
-                                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p));
-      return __builtin_amdgcn_make_buffer_rsrc((void*)pu, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    struct Stage { u32x4 xr[NX]; u32x4 gr[NG]; u32x2 gid[NG]; int ypar, xpar; };
-    int xrel[NX], xhyx[NX], grel[NG];
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      const int pix = pix0 + k * PSTEP, hy = pix / HWID, hx = pix - hy * HWID;
-      xhyx[k] = pix < XPIX ? (hy << 8) | hx : (200 << 8);
-      xrel[k] = (((hx - 1) >> sh) * Cs + coff + part * 8) * 2;      // column part (x0 is a multiple of 32); the row part per tile
-    }
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int pix = pix0 + k * PSTEP;
-      grel[k] = (((pix / 32) >> gsh) * Wg + ((pix % 32) >> gsh)) * a.Cout + co0 + part * 8;
-    }
-    auto issue = [&](int tile, Stage& S) __attribute__((always_inline)) {
-      int b = 0, x0 = 0, gx0 = 0, gx1 = 0, y0 = 0;
-      const bool live = tile >= 0;
-      if (live) tl.origin(tile, b, y0, x0, gx0, gx1);
-      S.ypar = y0; S.xpar = x0;
-      const __amdgpu_buffer_rsrc_t rx = rsrc((const char*)xsrc + (size_t)b * xs_bytes, xs_bytes);
-      const __amdgpu_buffer_rsrc_t rg = rsrc((const char*)a.g + (size_t)b * gs_bytes, gs_bytes);
-      const __amdgpu_buffer_rsrc_t ri = rsrc(a.g_unpool ? a.g_unpool + (size_t)b * (gs_bytes / 2) : (const unsigned char*)a.g, a.g_unpool ? gs_bytes / 2 : 0);
-      // source row of halo row hy: (y0 - 1 + hy) >> sh = ((y0 - 1) >> sh) + ((hy + ((y0 - 1) & sh)) >> sh) -- the static first row of a
-      // trimmed ground launch may be odd, so the tile origin's parity under the upsample shift is carried (ypar)
-      const int ylo = y0 - 1, ypar = ylo & sh, rowb = Ws * Cs * 2;
-      const int xbase = __builtin_amdgcn_readfirstlane(((ylo >> sh) * Ws + (x0 >> sh)) * Cs * 2);
-      const int gbase = __builtin_amdgcn_readfirstlane(((y0 >> gsh) * Wg + (x0 >> gsh)) * a.Cout);
-      const int hy_lo = live ? max(0, 1 - y0) : 255, hy_hi = a.H - y0 + 1, hx_lo = max(0, 1 - x0), hx_hi = a.W - x0 + 1;
-      const int gy_hi = live ? a.H - y0 : 0, gx_lo = gx0 - x0, gx_hi = gx1 - x0;
-#pragma unroll
-      for (int k = 0; k < NX; ++k) {
-        const int hy = xhyx[k] >> 8, hx = xhyx[k] & 255;
-        const bool ok = hy >= hy_lo && hy < hy_hi && hx >= hx_lo && hx < hx_hi;
-        S.xr[k] = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? xbase + ((hy + ypar) >> sh) * rowb + xrel[k] : OOB, 0, 0);
-      }
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        const int pix = pix0 + k * PSTEP, py = pix / 32, px = pix % 32;
-        const bool ok = py < gy_hi && px >= gx_lo && px < gx_hi;
-        const int e0 = ok ? gbase + grel[k] : OOB;
-        S.gr[k] = __builtin_amdgcn_raw_buffer_load_b128(rg, ok ? e0 * 2 : OOB, 0, 0);
-        S.gid[k] = __builtin_amdgcn_raw_buffer_load_b64(ri, e0, 0, 0);       // (no unpool: a zero-sized descriptor, reads 0)
-      }
-    };
-    auto commit = [&](const Stage& S, int buf) __attribute__((always_inline)) {
-      char* base = smem + buf * BUFB;
-#pragma unroll
-      for (int k = 0; k < NX; ++k) {
-        const int pix = pix0 + k * PSTEP;
-        if (pix < XPIX) *(u32x4*)(base + oX + pix * STR + part * 16) = S.xr[k];
-      }
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        const int pix = pix0 + k * PSTEP;
-        u32x4 v = S.gr[k];
-        if (a.g_unpool) {      // keep the elements whose forward argmax is this (y&1, x&1): (id ^ pos) - 1 is negative only for a match
-          typedef short s16x2 __attribute__((ext_vector_type(2)));
-          const unsigned pos = ((((S.ypar + pix / 32) & 1) << 1) | ((S.xpar + pix % 32) & 1)) * 0x01010101u;
-          const unsigned m0 = S.gid[k].x ^ pos, m1 = S.gid[k].y ^ pos;
-          auto keep = [](unsigned m, unsigned sel) {
-            s16x2 w2 = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(0u, m, sel));
-            w2 = (w2 - (short)1) >> 15;
-            return __builtin_bit_cast(unsigned, w2);
-          };
-          v.x &= keep(m0, 0x0c010c00u); v.y &= keep(m0, 0x0c030c02u);
-          v.z &= keep(m1, 0x0c010c00u); v.w &= keep(m1, 0x0c030c02u);
-        }
-        *(u32x4*)(base + oG + pix * STR + part * 16) = v;
-      }
-    };
-    Stage A, Bq;
-    int ta = t_first, tb = ta >= 0 ? next_tile(ta) : -1;
-    issue(ta, A);
-    issue(tb, Bq);
-    commit(A, 0);
-    __syncthreads();                                     // barrier 0: buffer 0 holds the first tile
-    int cur = 0;
-    while (ta >= 0) {
-      int tc = tb >= 0 ? next_tile(tb) : -1;
-      issue(tc, A);
-      commit(Bq, cur ^ 1);
-      __syncthreads();
-      ta = tb; tb = tc; cur ^= 1;
-      if (ta < 0) break;
-      tc = tb >= 0 ? next_tile(tb) : -1;
-      issue(tc, Bq);
-      commit(A, cur ^ 1);
-      __syncthreads();
-      ta = tb; tb = tc; cur ^= 1;
-    }
-    return;
-  }
-
-  // ---------------- matrix waves
-  const int ct = wv >> 1, it = wv & 1;
-  const bool want_bias = a.bpart && blockIdx.y == 0 && it == 0;
-  f32x16 acc[9], accb;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accb[r] = 0.f;
-  const uint4 ones = frag_ones<T>();
-  __syncthreads();                                       // barrier 0
-  int cur = 0;
-  for (int tile = t_first; tile >= 0; tile = next_tile(tile)) {
-    const char* Xs = smem + cur * BUFB + oX;
-    const char* Gs = smem + cur * BUFB + oG;
-    // the G fragments of the whole tile (4 rows x 2 K-steps) stay in registers; halo row rho's X fragments (3 column shifts x 2
-    // K-steps) are requested one row ahead of the MFMAs that consume them and feed the up to three taps ky with r = rho - ky
-    uint4 Af[WG_TH][2], Bf[2][3][2];
-#pragma unroll
-    for (int r = 0; r < WG_TH; ++r)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) Af[r][kk] = frag_kmajor<T>(Gs, STR, r * 32 + kk * KPX, ct * 32, lane);
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) Bf[0][kx][kk] = frag_kmajor<T>(Xs, STR, kx + kk * KPX, it * 32, lane);
-#pragma unroll
-    for (int rho = 0; rho < WG_TH + 2; ++rho) {
-      if (rho + 1 < WG_TH + 2) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) Bf[(rho + 1) & 1][kx][kk] = frag_kmajor<T>(Xs, STR, (rho + 1) * HWID + kx + kk * KPX, it * 32, lane);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (rho == 0 && want_bias) {
-#pragma unroll
-        for (int r = 0; r < WG_TH; ++r)
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) mma16<T>(accb, Af[r][kk], ones);
-      }
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
-            const int r = rho - ky;
-            if (r >= 0 && r < WG_TH) mma16<T>(acc[ky * 3 + kx], Af[r][kk], Bf[rho & 1][kx][kk]);
-          }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();                                     // the loaders have filled the other buffer; this one is free
-    cur ^= 1;
-  }
-  const int ci = ci0 + it * 32 + (lane & 31), g5 = lane >> 5;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g5;
-    float* o = a.part + (((size_t)ks * a.Cout + co) * a.Cin + ci) * 9;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r];
-    if (want_bias && (lane & 31) == 0) a.bpart[(size_t)ks * a.Cout + co] = accb[r];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Split-fp16 weight gradient (precision 'fp16x3'): the same contraction over pixels with both operands fed to the matrix cores
-// as hi + lo = fp16(s v) + fp16(s v - hi): G X ~= Ghi Xhi + Glo Xhi + Ghi Xlo, three v_mfma_f32_32x32x16_f16 per product, fp32
-// accumulate -- fp32-class gradients at a third of the fp16 MFMA rate instead of the exact-fp32 kernels' sixteenth.
-// Storage stays fp32 (the maps a split-mode forward / backward keep); a tile's 16-B pieces are split where they enter LDS, into
-// an fp16 hi plane and an fp16 lo plane per operand, each laid out like the f16 kernel's tile, so the k-major fragments come
-// from the same transpose reads.  Scales: ONE power of two per operand for the whole launch, from the maximum over the batch
-// of the per-sample maxima their producers recorded (the gradient is a sum over the batch, so a batch-wide scale costs no
-// accuracy where it matters: elements below 2^-17 of the batch maximum keep an absolute error of 2^-39 of it); exact to undo.
-struct WgradSplitExtra {
-  const unsigned* amax_x1; const unsigned* amax_x2; const unsigned* amax_g;   // [B] fp32 bit patterns of max |.| per sample
-};
-constexpr int WGS_STR = 64 * 2 + 16;                       // fp16 plane row stride (as wg_stride<f16>)
-// A tile of the (shared) tile lists is WG_TH = 4 rows x 32 pixels; with two fp16 planes per operand that is 96 KB of LDS and one
-// workgroup per CU, whose load and MFMA phases then run strictly one after the other (measured: 1.9 ms per launch, 6x the bf16
-// kernel for 3x its MFMAs).  The tile is therefore walked as two HALVES of WGS_TH = 2 rows: 58 KB, two workgroups per CU.
-constexpr int WGS_TH = 2;
-constexpr int wgs_lds_bytes() { return 2 * ((WGS_TH + 2) * HWID + WGS_TH * 32) * WGS_STR; }
-
-static __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs a, WgradSplitExtra sx) {
-  typedef f16 H;
-  constexpr int STR = WGS_STR, PPX = 16;                   // 16-B fp32 pieces per pixel (64 channels)
-  constexpr int XPIX = (WGS_TH + 2) * HWID, GPIX = WGS_TH * 32, KPX = 16;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Xh = smem;
-  char* Xl = Xh + XPIX * STR;
-  char* Gh = Xl + XPIX * STR;
-  char* Gl = Gh + GPIX * STR;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, ct = wv >> 1, it = wv & 1;
-  const int ks = blockIdx.x, ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
-  const bool first = ci0 < a.C1;
-  const float* xsrc = first ? (const float*)a.x1 : (const float*)a.x2;
-  const int Cs = first ? a.C1 : a.C2, coff = first ? ci0 : ci0 - a.C1, sh = (first && a.up1) ? 1 : 0;
-  const int Hs = a.H >> sh, Ws = a.W >> sh;
-  const int gsh = a.g_unpool ? 1 : 0, Hg = a.H >> gsh, Wg = a.W >> gsh;
-  const bool want_bias = a.bpart && blockIdx.y == 0 && it == 0;
-  // launch-wide scales (uniform)
-  unsigned mx = 0, mg = 0;
-  const unsigned* ax = first ? sx.amax_x1 : sx.amax_x2;
-  for (int b = 0; b < a.B; ++b) { mx = max(mx, ax[b]); mg = max(mg, sx.amax_g[b]); }
-  const float s_x = split_scale(mx), s_g = split_scale(mg);
-
-  f32x16 acc[9], accb;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accb[r] = 0.f;
-  const uint4 ones = frag_ones<f16>();
-
-  constexpr int NX = (XPIX * PPX + 255) / 256, NG = GPIX * PPX / 256, PSTEP = 256 / PPX;
-  static_assert(GPIX * PPX % 256 == 0, "gradient tile pieces per thread");
-  const int part = t % PPX, pix0 = t / PPX;
-  const WgTiles tl(a.dyn, a.dyn_desc, a.H, a.W, a.row_begin, a.tiles_x, a.tiles_y, a.ntile, a.B, a.g_unpool ? 1 : 0);
-  // Tile loads: raw buffer loads through one descriptor per operand and sample (base = the sample's map, range = its bytes).  A piece
-  // outside the image / the written part of g gets an offset beyond the range and reads as ZERO: no branch around a load, so all of a
-  // half tile's 13 (+ 4 argmax) loads are in flight together.  (With `if (inside) v = *p` hipcc put each load into its own exec-masked
-  // block with an s_waitcnt vmcnt(0) at its end: 13 dependent memory round trips per half tile -- the kernel ran at 0.37 of its
-  // MFMA ceiling where the forward kernels reach 0.55.)
-  constexpr int OOB = (int)0x80000000;
-  const size_t xs_bytes = (size_t)Hs * Ws * Cs * 4, gs_bytes = (size_t)Hg * Wg * a.Cout * 4;
-  auto rsrc = [](const void* base, size_t bytes) __attribute__((always_inline)) {
-    const unsigned long long p = (unsigned long long)base;
-    const void* pu = (const void*)(((unsigned long long)__builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32)) << 32) |
-                                   (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)pu, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-  };
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  for (int tile2 = 2 * ks; tile2 < 2 * tl.ntile; tile2 += (tile2 & 1) ? 2 * a.KS - 1 : 1) {      // (tile, half 0), (tile, half 1), next tile
-    int b, y0, x0, gx0, gx1;
-    tl.origin(tile2 >> 1, b, y0, x0, gx0, gx1);
-    y0 += (tile2 & 1) * WGS_TH;
-    if (y0 >= a.H) continue;                           // (uniform: the lower half of a tile at the image's last rows)
-    const __amdgpu_buffer_rsrc_t rx = rsrc((const char*)xsrc + (size_t)b * xs_bytes, xs_bytes);
-    const __amdgpu_buffer_rsrc_t rg = rsrc((const char*)a.g + (size_t)b * gs_bytes, gs_bytes);
-    const __amdgpu_buffer_rsrc_t ri = rsrc(a.g_unpool ? a.g_unpool + (size_t)b * (gs_bytes / 4) : (const unsigned char*)a.g, a.g_unpool ? gs_bytes / 4 : 0);
-    u32x4 xr[NX], gr[NG];
-    unsigned gid[NG];
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {                     // input halo tile, zero outside the image
-      const int pix = pix0 + k * PSTEP;
-      const int hy = pix / HWID, hx = pix - hy * HWID, y = y0 - 1 + hy, x = x0 - 1 + hx;
-      const bool ok = pix < XPIX && y >= 0 && y < a.H && x >= 0 && x < a.W;
-      const int off = ok ? (((y >> sh) * Ws + (x >> sh)) * Cs + coff + part * 4) * 4 : OOB;
-      xr[k] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {                     // output-gradient tile (virtual unpool: + the forward argmax)
-      const int pix = pix0 + k * PSTEP;
-      const int y = y0 + pix / 32, x = x0 + pix % 32;
-      const bool ok = y < a.H && x >= gx0 && x < gx1;
-      const int e0 = ok ? ((y >> gsh) * Wg + (x >> gsh)) * a.Cout + co0 + part * 4 : OOB;
-      gr[k] = __builtin_amdgcn_raw_buffer_load_b128(rg, ok ? e0 * 4 : OOB, 0, 0);
-      gid[k] = a.g_unpool ? __builtin_amdgcn_raw_buffer_load_b32(ri, e0, 0, 0) : 0u;
-    }
-    __syncthreads();                                   // previous half tile fully consumed (the loads above are in flight across it)
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      const int pix = pix0 + k * PSTEP;
-      uint2 hi, lw;
-      split4(__uint_as_float(xr[k].x), __uint_as_float(xr[k].y), __uint_as_float(xr[k].z), __uint_as_float(xr[k].w), s_x, hi, lw);
-      if (pix < XPIX) { *(uint2*)(Xh + pix * STR + part * 8) = hi; *(uint2*)(Xl + pix * STR + part * 8) = lw; }
-    }
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int pix = pix0 + k * PSTEP;
-      float e0 = __uint_as_float(gr[k].x), e1 = __uint_as_float(gr[k].y), e2 = __uint_as_float(gr[k].z), e3 = __uint_as_float(gr[k].w);
-      if (a.g_unpool) {                                // keep the elements whose forward argmax is this (y&1, x&1)
-        const unsigned pos = (((y0 + pix / 32) & 1) << 1) | ((x0 + pix % 32) & 1);
-        if ((gid[k] & 0xff) != pos) e0 = 0.f;
-        if (((gid[k] >> 8) & 0xff) != pos) e1 = 0.f;
-        if (((gid[k] >> 16) & 0xff) != pos) e2 = 0.f;
-        if ((gid[k] >> 24) != pos) e3 = 0.f;
-      }
-      uint2 hi, lw;
-      split4(e0, e1, e2, e3, s_g, hi, lw);
-      *(uint2*)(Gh + pix * STR + part * 8) = hi; *(uint2*)(Gl + pix * STR + part * 8) = lw;
-    }
-    __syncthreads();
-    // one K-step (16 pixels) at a time: the G fragments of the tile's four rows (hi and lo: 32 registers) stay resident while
-    // every X fragment (halo row rho, column shift kx) is fetched once and feeds the up to three taps ky that use it
-#pragma unroll 1
-    for (int kk = 0; kk < 32 / KPX; ++kk) {
-      uint4 Ah[WGS_TH], Al[WGS_TH];
-#pragma unroll
-      for (int r = 0; r < WGS_TH; ++r) {
-        Ah[r] = frag_kmajor<H>(Gh, STR, r * 32 + kk * KPX, ct * 32, lane);
-        Al[r] = frag_kmajor<H>(Gl, STR, r * 32 + kk * KPX, ct * 32, lane);
-        if (want_bias) { mma16<H>(accb, Ah[r], ones); mma16<H>(accb, Al[r], ones); }
-      }
-#pragma unroll
-      for (int rho = 0; rho < WGS_TH + 2; ++rho) {
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const uint4 Bh = frag_kmajor<H>(Xh, STR, rho * HWID + kx + kk * KPX, it * 32, lane);
-          const uint4 Bl = frag_kmajor<H>(Xl, STR, rho * HWID + kx + kk * KPX, it * 32, lane);
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
-            const int r = rho - ky;
-            if (r >= 0 && r < WGS_TH) {
-              mma16<H>(acc[ky * 3 + kx], Ah[r], Bh);
-              mma16<H>(acc[ky * 3 + kx], Al[r], Bh);
-              mma16<H>(acc[ky * 3 + kx], Ah[r], Bl);
-            }
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-  // D[i = co][j = ci]: lane -> ci = ci0 + it*32 + (lane&31); reg r -> co = co0 + ct*32 + (r&3) + 8(r>>2) + 4(lane>>5)
-  const float inv = 1.f / (s_x * s_g), invg = 1.f / s_g;
-  const int ci = ci0 + it * 32 + (lane & 31), g5 = lane >> 5;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g5;
-    float* o = a.part + (((size_t)ks * a.Cout + co) * a.Cin + ci) * 9;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r] * inv;
-    if (want_bias && (lane & 31) == 0) a.bpart[(size_t)ks * a.Cout + co] = accb[r] * invg;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// wgrad_split_ws_kernel: the same contraction, WAVE-SPECIALISED (round 5).  wgrad_split_kernel runs load -> split -> barrier ->
-// MFMA in every wave, with nothing but the second resident workgroup to overlap the phases: 0.47 of its MFMA ceiling where the
-// forward kernels reach 0.55.  Here a workgroup is EIGHT waves on one CU: waves 4-7 are LOADERS (they fetch a half tile's fp32
-// pieces two half tiles ahead, split them into the fp16 hi / lo planes and write them into the idle LDS buffer -- the ~400 VALU
-// instructions per half tile that used to sit between two MFMA phases), waves 0-3 are the MATRIX waves (one per SIMD: transposing
-// LDS reads and MFMAs only, fragments requested one halo row ahead of the MFMAs that consume them).  A matrix wave and a loader
-// share each SIMD, so the split's VALU work and the global-load latency run under the MFMAs instead of between them.  One
-// workgroup barrier per half tile; LDS: two buffers of {Xh, Xl, Gh, Gl} = 115 KB, one workgroup per CU, 256 registers per wave.
-// Same tile lists, same order of every partial sum's terms as wgrad_split_kernel (bit-identical partials for the same KS).
-constexpr int wgs_ws_buf_bytes() { return 2 * ((WGS_TH + 2) * HWID + WGS_TH * 32) * WGS_STR; }
-constexpr int wgs_ws_lds_bytes() { return 2 * wgs_ws_buf_bytes(); }
-
-static __global__ __launch_bounds__(512, 1) void wgrad_split_ws_kernel(WgradArgs a, WgradSplitExtra sx) {
-  typedef f16 H;
-  constexpr int STR = WGS_STR, PPX = 16;                   // 16-B fp32 pieces per pixel (64 channels)
-  constexpr int XPIX = (WGS_TH + 2) * HWID, GPIX = WGS_TH * 32, KPX = 16, BUFB = wgs_ws_buf_bytes();
-  constexpr int oXh = 0, oXl = XPIX * STR, oGh = 2 * XPIX * STR, oGl = 2 * XPIX * STR + GPIX * STR;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const bool loader = wv >= 4;                             // wave-uniform role
-  const int ks = blockIdx.x, ci0 = blockIdx.y * 64, co0 = blockIdx.z * 64;
-  const bool first = ci0 < a.C1;
-  const float* xsrc = first ? (const float*)a.x1 : (const float*)a.x2;
-  const int Cs = first ? a.C1 : a.C2, coff = first ? ci0 : ci0 - a.C1, sh = (first && a.up1) ? 1 : 0;
-  const int Hs = a.H >> sh, Ws = a.W >> sh;
-  const int gsh = a.g_unpool ? 1 : 0, Hg = a.H >> gsh, Wg = a.W >> gsh;
-  const WgTiles tl(a.dyn, a.dyn_desc, a.H, a.W, a.row_begin, a.tiles_x, a.tiles_y, a.ntile, a.B, a.g_unpool ? 1 : 0);
-  // the half-tile walk of this k-slice: (tile, half 0), (tile, half 1), next tile; the lower half of a tile at the image's last
-  // rows may be empty.  Both roles step through it identically (they meet at one barrier per half tile).
-  const int n2 = 2 * tl.ntile;
-  auto half_y0 = [&](int t2, int& b, int& x0, int& gx0, int& gx1) {
-    int y0;
-    tl.origin(t2 >> 1, b, y0, x0, gx0, gx1);
-    return y0 + (t2 & 1) * WGS_TH;
-  };
-  auto next_t2 = [&](int t2) {                             // the next non-empty half tile after t2, or -1
-    for (;;) {
-      t2 += (t2 & 1) ? 2 * a.KS - 1 : 1;
-      if (t2 >= n2) return -1;
-      int b, x0, g0, g1;
-      if (half_y0(t2, b, x0, g0, g1) < a.H) return t2;
-    }
-  };
-  int t_first = 2 * ks;
-  if (t_first >= n2) t_first = -1;                         // (the upper half of a listed tile is never empty)
-
-  if (loader) {
-    // ---------------- loader waves: global -> registers (two half tiles in flight) -> split -> LDS planes of the idle buffer
-    const int tl_ = t - 256, part = tl_ % PPX, pix0 = tl_ / PPX;
-    constexpr int NX = (XPIX * PPX + 255) / 256, NG = GPIX * PPX / 256, PSTEP = 256 / PPX;
-    static_assert(GPIX * PPX % 256 == 0, "gradient tile pieces per thread");
-    unsigned mx = 0, mg = 0;
-    const unsigned* ax = first ? sx.amax_x1 : sx.amax_x2;
-    for (int b = 0; b < a.B; ++b) { mx = max(mx, ax[b]); mg = max(mg, sx.amax_g[b]); }
-    const float s_x = split_scale(mx), s_g = split_scale(mg);
-    constexpr int OOB = (int)0x80000000;
-    const size_t xs_bytes = (size_t)Hs * Ws * Cs * 4, gs_bytes = (size_t)Hg * Wg * a.Cout * 4;
-    auto rsrc = [](const void* base, size_t bytes) __attribute__((always_inline)) {
-      const unsigned long long p = (unsigned long long)base;
-      const void* pu = (const void*)(((unsigned long long)__builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32)) << 32) |
-                                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p));
-      return __builtin_amdgcn_make_buffer_rsrc((void*)pu, 0, __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-    };
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    struct Stage { u32x4 xr[NX]; u32x4 gr[NG]; unsigned gid[NG]; int ypar, xpar; };
-    // A piece's place in the half tile is fixed for the thread's life: its halo row / column (hy, hx) and, relative to the tile's
-    // origin, the COLUMN part of its byte offset in the source map (the origin's column is a multiple of 32 and splits off exactly,
-    // also through the nearest-upsample shift; its row may be odd and does not).  Per half tile a piece then costs a shift-multiply-add,
-    // the bounds compares and a select.
-    int xrel[NX], xhyx[NX], grel[NG];
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      const int pix = pix0 + k * PSTEP, hy = pix / HWID, hx = pix - hy * HWID;
-      xhyx[k] = pix < XPIX ? (hy << 8) | hx : (200 << 8);                          // (a row no image has: never valid)
-      xrel[k] = (((hx - 1) >> sh) * Cs + coff + part * 4) * 4;      // column part (arithmetic shift: floor; x0 is a multiple of 32)
-    }
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int pix = pix0 + k * PSTEP;
-      grel[k] = (((pix / 32) >> gsh) * Wg + ((pix % 32) >> gsh)) * a.Cout + co0 + part * 4;
-    }
-    // every load is issued unconditionally (a half tile that does not exist gets out-of-range offsets everywhere and reads
-    // zeros): straight-line code, so the compiler can COUNT the loads in flight and wait for one stage while the next one's are
-    // still outstanding.  (A branch around the loads makes the wait a vmcnt(0).)
-    auto issue = [&](int t2, Stage& S) __attribute__((always_inline)) {
-      int b = 0, x0 = 0, gx0 = 0, gx1 = 0, y0 = 0;
-      const bool live = t2 >= 0;
-      if (live) y0 = half_y0(t2, b, x0, gx0, gx1);
-      S.ypar = y0; S.xpar = x0;
-      const __amdgpu_buffer_rsrc_t rx = rsrc((const char*)xsrc + (size_t)b * xs_bytes, xs_bytes);
-      const __amdgpu_buffer_rsrc_t rg = rsrc((const char*)a.g + (size_t)b * gs_bytes, gs_bytes);
-      const __amdgpu_buffer_rsrc_t ri = rsrc(a.g_unpool ? a.g_unpool + (size_t)b * (gs_bytes / 4) : (const unsigned char*)a.g, a.g_unpool ? gs_bytes / 4 : 0);
-      // uniform: the tile origin's offset (y0 is even and x0 a multiple of 32, so the upsample / unpool shifts split off), and the
-      // valid ranges of hy / hx (input halo) and of the gradient tile's rows / columns
-      // source row of halo row hy: (y0 - 1 + hy) >> sh = ((y0 - 1) >> sh) + ((hy + ((y0 - 1) & sh)) >> sh) -- the static first row of a
-      // trimmed ground launch may be odd, so the origin's parity under the upsample shift is carried (ypar); columns split off
-      // exactly (x0 is a multiple of 32)
-      const int ylo = y0 - 1, ypar = ylo & sh, rowb = Ws * Cs * 4;
-      const int xbase = __builtin_amdgcn_readfirstlane(((ylo >> sh) * Ws + (x0 >> sh)) * Cs * 4);
-      const int gbase = __builtin_amdgcn_readfirstlane(((y0 >> gsh) * Wg + (x0 >> gsh)) * a.Cout);
-      const int hy_lo = live ? max(0, 1 - y0) : 255, hy_hi = a.H - y0 + 1, hx_lo = max(0, 1 - x0), hx_hi = a.W - x0 + 1;
-      const int gy_hi = live ? a.H - y0 : 0, gx_lo = gx0 - x0, gx_hi = gx1 - x0;
-#pragma unroll
-      for (int k = 0; k < NX; ++k) {                   // input halo tile, zero outside the image
-        const int hy = xhyx[k] >> 8, hx = xhyx[k] & 255;
-        const bool ok = hy >= hy_lo && hy < hy_hi && hx >= hx_lo && hx < hx_hi;
-        S.xr[k] = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? xbase + ((hy + ypar) >> sh) * rowb + xrel[k] : OOB, 0, 0);
-      }
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {                   // output-gradient tile (virtual unpool: + the forward argmax)
-        const int pix = pix0 + k * PSTEP, py = pix / 32, px = pix % 32;
-        const bool ok = py < gy_hi && px >= gx_lo && px < gx_hi;
-        const int e0 = ok ? gbase + grel[k] : OOB;
-        S.gr[k] = __builtin_amdgcn_raw_buffer_load_b128(rg, ok ? e0 * 4 : OOB, 0, 0);
-        S.gid[k] = __builtin_amdgcn_raw_buffer_load_b32(ri, e0, 0, 0);      // (no unpool: a zero-sized descriptor, reads 0)
-      }
-    };
-    auto commit = [&](const Stage& S, int buf) __attribute__((always_inline)) {
-      char* base = smem + buf * BUFB;
-#pragma unroll
-      for (int k = 0; k < NX; ++k) {
-        const int pix = pix0 + k * PSTEP;
-        uint2 hi, lw;
-        split4(__uint_as_float(S.xr[k].x), __uint_as_float(S.xr[k].y), __uint_as_float(S.xr[k].z), __uint_as_float(S.xr[k].w), s_x, hi, lw);
-        if (pix < XPIX) { *(uint2*)(base + oXh + pix * STR + part * 8) = hi; *(uint2*)(base + oXl + pix * STR + part * 8) = lw; }
-      }
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        const int pix = pix0 + k * PSTEP;
-        float e0 = __uint_as_float(S.gr[k].x), e1 = __uint_as_float(S.gr[k].y), e2 = __uint_as_float(S.gr[k].z), e3 = __uint_as_float(S.gr[k].w);
-        if (a.g_unpool) {                              // keep the elements whose forward argmax is this (y&1, x&1)
-          const unsigned pos = (((S.ypar + pix / 32) & 1) << 1) | ((S.xpar + pix % 32) & 1);
-          if ((S.gid[k] & 0xff) != pos) e0 = 0.f;
-          if (((S.gid[k] >> 8) & 0xff) != pos) e1 = 0.f;
-          if (((S.gid[k] >> 16) & 0xff) != pos) e2 = 0.f;
-          if ((S.gid[k] >> 24) != pos) e3 = 0.f;
-        }
-        uint2 hi, lw;
-        split4(e0, e1, e2, e3, s_g, hi, lw);
-        *(uint2*)(base + oGh + pix * STR + part * 8) = hi; *(uint2*)(base + oGl + pix * STR + part * 8) = lw;
-      }
-    };
-    Stage A, Bq;
-    int ta = t_first, tb = ta >= 0 ? next_t2(ta) : -1;
-    issue(ta, A);
-    issue(tb, Bq);
-    commit(A, 0);
-    __syncthreads();                                     // barrier 0: buffer 0 holds the first half tile
-    int cur = 0;
-    // at the top: the matrix waves work on half tile `ta` in buffer `cur`; Bq holds (in flight) the loads of `tb`; A is free
-    while (ta >= 0) {
-      int tc = tb >= 0 ? next_t2(tb) : -1;
-      issue(tc, A);
-      commit(Bq, cur ^ 1);
-      __syncthreads();
-      ta = tb; tb = tc; cur ^= 1;
-      if (ta < 0) break;
-      tc = tb >= 0 ? next_t2(tb) : -1;
-      issue(tc, Bq);
-      commit(A, cur ^ 1);
-      __syncthreads();
-      ta = tb; tb = tc; cur ^= 1;
-    }
-    return;
-  }
-
-  // ---------------- matrix waves
-  const int ct = wv >> 1, it = wv & 1;
-  const bool want_bias = a.bpart && blockIdx.y == 0 && it == 0;
-  unsigned mx = 0, mg = 0;
-  {
-    const unsigned* ax = first ? sx.amax_x1 : sx.amax_x2;
-    for (int b = 0; b < a.B; ++b) { mx = max(mx, ax[b]); mg = max(mg, sx.amax_g[b]); }
-  }
-  const float s_x = split_scale(mx), s_g = split_scale(mg);
-  f32x16 acc[9], accb;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) accb[r] = 0.f;
-  const uint4 ones = frag_ones<f16>();
-  __syncthreads();                                       // barrier 0
-  int cur = 0;
-  for (int t2 = t_first; t2 >= 0; t2 = next_t2(t2)) {
-    const char* base = smem + cur * BUFB;
-    const char *Xh = base + oXh, *Xl = base + oXl, *Gh = base + oGh, *Gl = base + oGl;
-    // A flat walk over the half tile's 8 steps (K-step kk = 16 pixels, halo row rho): the G fragments of a K-step (two rows, hi and
-    // lo) stay resident while its four halo rows pass; the X fragments of step s + 1 -- and, in a K-step's last row, the G
-    // fragments of the next one -- are REQUESTED AT THE TOP of step s, ahead of its 9-18 MFMAs (this wave has the SIMD's matrix pipe
-    // to itself: nothing else covers the LDS latency; left to the scheduler the requests sank to just before the step's last MFMA
-    // and every step started with an LDS round trip: 0.77 of the pipe with the loaders idle).  A fragment feeds the up to two taps
-    // ky that use it.  Term order per accumulator as in wgrad_split_kernel: (hi hi, lo hi, hi lo) per (kk, rho, kx, ky).
-    constexpr int NSTEP = (32 / KPX) * (WGS_TH + 2);
-    uint4 Ah[2][WGS_TH], Al[2][WGS_TH], Bh[2][3], Bl[2][3];
-#pragma unroll
-    for (int r = 0; r < WGS_TH; ++r) {
-      Ah[0][r] = frag_kmajor<H>(Gh, STR, r * 32, ct * 32, lane);
-      Al[0][r] = frag_kmajor<H>(Gl, STR, r * 32, ct * 32, lane);
-    }
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      Bh[0][kx] = frag_kmajor<H>(Xh, STR, kx, it * 32, lane);
-      Bl[0][kx] = frag_kmajor<H>(Xl, STR, kx, it * 32, lane);
-    }
-#pragma unroll
-    for (int st = 0; st < NSTEP; ++st) {
-      const int kk = st / (WGS_TH + 2), rho = st % (WGS_TH + 2);
-      if (st + 1 < NSTEP) {
-        const int kn = (st + 1) / (WGS_TH + 2), rn = (st + 1) % (WGS_TH + 2);
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          Bh[(st + 1) & 1][kx] = frag_kmajor<H>(Xh, STR, rn * HWID + kx + kn * KPX, it * 32, lane);
-          Bl[(st + 1) & 1][kx] = frag_kmajor<H>(Xl, STR, rn * HWID + kx + kn * KPX, it * 32, lane);
-        }
-        if (rn == 0) {
-#pragma unroll
-          for (int r = 0; r < WGS_TH; ++r) {
-            Ah[kn & 1][r] = frag_kmajor<H>(Gh, STR, r * 32 + kn * KPX, ct * 32, lane);
-            Al[kn & 1][r] = frag_kmajor<H>(Gl, STR, r * 32 + kn * KPX, ct * 32, lane);
-          }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (rho == 0 && want_bias) {
-#pragma unroll
-        for (int r = 0; r < WGS_TH; ++r) { mma16<H>(accb, Ah[kk & 1][r], ones); mma16<H>(accb, Al[kk & 1][r], ones); }
-      }
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const int r = rho - ky;
-          if (r >= 0 && r < WGS_TH) {
-            mma16<H>(acc[ky * 3 + kx], Ah[kk & 1][r], Bh[st & 1][kx]);
-            mma16<H>(acc[ky * 3 + kx], Al[kk & 1][r], Bh[st & 1][kx]);
-            mma16<H>(acc[ky * 3 + kx], Ah[kk & 1][r], Bl[st & 1][kx]);
-          }
-        }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();                                     // the loaders have filled the other buffer; this one is free
-    cur ^= 1;
-  }
-  // D[i = co][j = ci]: lane -> ci = ci0 + it*32 + (lane&31); reg r -> co = co0 + ct*32 + (r&3) + 8(r>>2) + 4(lane>>5)
-  const float inv = 1.f / (s_x * s_g), invg = 1.f / s_g;
-  const int ci = ci0 + it * 32 + (lane & 31), g5 = lane >> 5;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = co0 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g5;
-    float* o = a.part + (((size_t)ks * a.Cout + co) * a.Cin + ci) * 9;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) o[tap] = acc[tap][r] * inv;
-    if (want_bias && (lane & 31) == 0) a.bpart[(size_t)ks * a.Cout + co] = accb[r] * invg;
-  }
-}
 
 // per-sample max |x| of an fp32 map (fp32 bit pattern, atomicMax into a zeroed word): the scale of a gradient map that no
 // convolution epilogue produced (the L2-norm backward's outputs, with the confidence heads' contribution added)
@@ -1035,101 +23,6 @@ static __global__ __launch_bounds__(256) void absmax_map_kernel(const float* __r
   m = wave_max_f32(m);
   if ((threadIdx.x & 63) == 0 && __float_as_uint(m) > __hip_atomic_load(amax + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
     atomicMax(amax + b, __float_as_uint(m));
-}
-
-// conv0: dW0[co][k = c*9+tap] over the NCHW fp32 input (k padded to 32 as one "ci tile").
-struct Wgrad0Args {
-  const float* x;        // [B,3,H,W], channel planes x_plane elements apart
-  size_t x_plane;
-  const void* g;         // d(loss)/d(conv0 pre-activation) NHWC T [B,H,W,64]
-  float* part;           // [KS][2 row-halves][64][32]
-  float* bpart;          // [KS][2][64]
-  int B, H, W, tiles_x, tiles_y, ntile, KS;
-  int row_begin;         // first pixel row that carries gradient
-  const int* dyn;        // as WgradArgs::dyn / dyn_desc
-  int dyn_desc;
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void wgrad0_kernel(Wgrad0Args a) {
-  constexpr int EPL = 16 / sizeof(T), STR = wg_stride<T>(), PPX = 64 * (int)sizeof(T) / 16, KPX = KStep<T>::PX;
-  constexpr int IW = 48;   // plane row pitch (32 + 2 halo + K-step overrun)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* Gs = smem;
-  float* in = (float*)(smem + WG_TH * 32 * STR);     // [3][WG_TH+2][IW]
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, ct = wv & 1, half = wv >> 1;
-  const int ks = blockIdx.x;
-  f32x16 acc, accb;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { acc[r] = 0.f; accb[r] = 0.f; }
-  const uint4 ones = frag_ones<T>();
-  const int j = lane & 31, g5 = lane >> 5;            // B operand: column j = k index (c, ky, kx)
-  const int jc = j < 27 ? j / 9 : 0, jky = (j % 9) / 3, jkx = j % 3;
-  const WgTiles tl(a.dyn, a.dyn_desc, a.H, a.W, a.row_begin, a.tiles_x, a.tiles_y, a.ntile, a.B, 0);
-  for (int tile = ks; tile < tl.ntile; tile += a.KS) {
-    int b, y0, x0, gx0, gx1;
-    tl.origin(tile, b, y0, x0, gx0, gx1);
-    __syncthreads();
-    // (every load of a tile is requested before the first LDS write: as two rolled loops this was 14 dependent
-    //  load -> wait -> write round trips per tile against a few microseconds of MFMA work -- the kernel ran at 68 TF)
-    constexpr int NI = (3 * (WG_TH + 2) * IW + 255) / 256, NG = WG_TH * 32 * PPX / 256;
-    static_assert(WG_TH * 32 * PPX % 256 == 0, "gradient tile pieces per thread");
-    float vi[NI];
-    uint4 vg[NG];
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const int e = t + it * 256;
-      const int c = e / ((WG_TH + 2) * IW), r = e % ((WG_TH + 2) * IW), iy = r / IW, ix = r % IW;
-      const int y = y0 - 1 + iy, x = x0 - 1 + ix;
-      vi[it] = 0.f;
-      if (e < 3 * (WG_TH + 2) * IW && ix < HWID && y >= 0 && y < a.H && x >= 0 && x < a.W)
-        vi[it] = a.x[((size_t)b * 3 + c) * a.x_plane + (size_t)y * a.W + x];
-    }
-#pragma unroll
-    for (int it = 0; it < NG; ++it) {
-      const int e = t + it * 256;
-      const int pix = e / PPX, part = e % PPX;
-      const int y = y0 + pix / 32, x = x0 + pix % 32;
-      vg[it] = make_uint4(0, 0, 0, 0);
-      if (y < a.H && x >= gx0 && x < gx1)
-        vg[it] = *(const uint4*)((const T*)a.g + (((size_t)b * a.H + y) * a.W + x) * 64 + part * EPL);
-    }
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const int e = t + it * 256;
-      if (e < 3 * (WG_TH + 2) * IW) in[e] = vi[it];
-    }
-#pragma unroll
-    for (int it = 0; it < NG; ++it) {
-      const int e = t + it * 256;
-      *(uint4*)(Gs + (e / PPX) * STR + (e % PPX) * 16) = vg[it];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int rr = 0; rr < WG_TH / 2; ++rr) {
-      const int r = half * (WG_TH / 2) + rr;
-#pragma unroll
-      for (int kk = 0; kk < 32 / KPX; ++kk) {
-        const uint4 A = frag_kmajor<T>(Gs, STR, r * 32 + kk * KPX, ct * 32, lane);
-        T e[EPL];
-        const float* row = in + (jc * (WG_TH + 2) + r + jky) * IW + jkx + kk * KPX;
-#pragma unroll
-        for (int jj = 0; jj < EPL; ++jj) {
-          // bf16: k = 8*g5 + jj ; fp32: k = 2*jj + g5   (pixel offset inside the K-step, see KStep)
-          const int k = sizeof(T) == 2 ? 8 * g5 + jj : 2 * jj + g5;
-          e[jj] = (T)(j < 27 ? row[k] : 0.f);
-        }
-        mma16<T>(acc, A, __builtin_bit_cast(uint4, e));
-        mma16<T>(accb, A, ones);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int co = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g5;
-    a.part[(((size_t)ks * 2 + half) * 64 + co) * 32 + j] = acc[r];
-    if (j == 0) a.bpart[((size_t)ks * 2 + half) * 64 + co] = accb[r];
-  }
 }
 
 // out[i] = sum_k part[k][i]  (fixed order: deterministic).  Generic 2-D gather: element i = (row, col) with col < out_inner,
@@ -1590,7 +483,6 @@ struct BwdPlan {
 enum { GA_X21 = 0, GA_D2A, GA_X18, GA_X3P, GA_D1A, GA_X15, GA_X8P, GA_A12, GA_A10, GA_X8, GA_A5, GA_X3, GA_A0, GA_X24, GA_D3A,
        GA_X2P, GA_C2, kGradAmaxSlots = 24 };
 
-static std::atomic<unsigned long long> g_wgrad_dma_ok{0};     // per device: wgrad_dma_kernel's LDS request was accepted
 // per device (bit = device id; ids >= 64 never set a bit and take the fallback kernels): the wave-specialised weight-gradient
 // kernel's LDS request was accepted.  One word per kernel -- wgrad_split_ws_kernel asks for 115 KB, wgrad_ws_kernel<T> for 96 KB:
 // a device or partition mode may grant one and refuse the other.
@@ -1696,19 +588,15 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
       //  wgrad_split_kernel -- ws_ok, per device)
       int d = 0;
       (void)hipGetDevice(&d);
-      const bool ok = hipFuncSetAttribute((const void*)wgrad_split_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_ws_lds_bytes()) == hipSuccess;
+      const bool ok = hipFuncSetAttribute((const void*)wgrad_split_ws_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_ws_lds_bytes()) == hipSuccess;
       if (ok) g_wgrad_split_ws_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
-      return hipFuncSetAttribute((const void*)wgrad_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_lds_bytes());
+      return hipFuncSetAttribute((const void*)wgrad_split_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, wgs_lds_bytes());
     }
     else {
       if constexpr (sizeof(T) == 2) {
         int d = 0;
         (void)hipGetDevice(&d);
-        // 72 KB: refused (a partition mode with a smaller per-workgroup limit) -> the plain launches fall back to wgrad_kernel<T>
-        // 
-        const bool dma = hipFuncSetAttribute((const void*)wgrad_dma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wgd_lds_bytes()) == hipSuccess;
-        if (dma) g_wgrad_dma_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
-        // 96 KB of dynamic LDS: refused -> the launches fall back (g_wgrad_ws_ok)
+        // 96 KB of dynamic LDS: refused -> the launches fall back to wgrad_kernel<T> (g_wgrad_ws_ok)
         const bool ws = hipFuncSetAttribute((const void*)wgrad_ws_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_ws_lds_bytes<T>()) == hipSuccess;
         if (ws) g_wgrad_ws_ok.fetch_or(dev_bit(d)); else (void)hipGetLastError();
       }
@@ -1870,34 +758,30 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
     a.B = B; a.H = Hout; a.W = Wout; a.Cout = kLayers[l].cout; a.Cin = kLayers[l].cin;
     a.row_begin = row_begin > 0 ? row_begin : 0;
     a.tiles_x = (Wout + 31) / 32; a.tiles_y = (Hout - a.row_begin + WG_TH - 1) / WG_TH; a.ntile = B * a.tiles_x * a.tiles_y;
-    a.KS = wgrad_ksplit(a.Cout, a.Cin, a.ntile);
-    bool ws = false, dma_ok = false;
-    {
+    // wave-specialised kernels (split and 16-bit, unless the device refused their LDS or the caller asks for the two-phase ones):
+    // one 8-wave workgroup per CU -> 256 workgroups are one resident generation; two-phase: two 4-wave workgroups -> 512
+    bool ws = false;
+    if constexpr (SPLIT || sizeof(T) == 2) {
       int d = 0;
       (void)hipGetDevice(&d);
-      dma_ok = (g_wgrad_dma_ok.load() & dev_bit(d)) != 0;
-    }
-    if constexpr (SPLIT || sizeof(T) == 2) {                      // wave-specialised kernels: one 8-wave workgroup per CU -> 256
-      int d = 0;                                                  // workgroups are one resident generation
-      (void)hipGetDevice(&d);
       ws = ((SPLIT ? g_wgrad_split_ws_ok : g_wgrad_ws_ok).load() & dev_bit(d)) != 0 && !(flags & HLA_VGG_BWD_WGRAD_TWO_PHASE);
-      if (ws) a.KS = wgrad_ksplit(a.Cout, a.Cin, a.ntile, 256);
     }
+    a.KS = wgrad_ksplit(a.Cout, a.Cin, a.ntile, ws ? 256 : 512);
     a.part = (float*)(bw + bp.part);
     a.bpart = (kLayers[l].has_bias && gr->db[l]) ? (float*)(bw + bp.bpart) : nullptr;
     const double P = (double)B * (Hout - a.row_begin) * Wout;
     hla_prof_begin_dyn(K_WGRAD, 2.0 * 9 * a.Cin * a.Cout * P, P * (a.Cin + a.Cout) * sizeof(T), st,
                        a.dyn ? a.dyn + a.dyn_desc : nullptr, a.tiles_x * a.tiles_y);
+    const dim3 grid(a.KS, a.Cin / 64, a.Cout / 64), block(ws ? 512 : 256);
     if constexpr (SPLIT) {
-      WgradSplitExtra ex{FA(fa1), FA(fa2), GA(ga)};
-      if (ws) hipLaunchKernelGGL(wgrad_split_ws_kernel, dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(512), wgs_ws_lds_bytes(), st, a, ex);
-      else hipLaunchKernelGGL(wgrad_split_kernel, dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wgs_lds_bytes(), st, a, ex);
-    } else if constexpr (sizeof(T) == 2) {
-      if (ws) hipLaunchKernelGGL((wgrad_ws_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(512), wg_ws_lds_bytes<T>(), st, a);
-      else if (!unpool && dma_ok) hipLaunchKernelGGL((wgrad_dma_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wgd_lds_bytes(), st, a);
-      else hipLaunchKernelGGL((wgrad_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wg_lds_bytes<T>(), st, a);
+      const WgradSplitExtra ex{FA(fa1), FA(fa2), GA(ga)};
+      if (ws) hipLaunchKernelGGL(wgrad_split_ws_kernel<f16>, grid, block, wgs_ws_lds_bytes(), st, a, ex);
+      else hipLaunchKernelGGL(wgrad_split_kernel<f16>, grid, block, wgs_lds_bytes(), st, a, ex);
     } else {
-      hipLaunchKernelGGL((wgrad_kernel<T>), dim3(a.KS, a.Cin / 64, a.Cout / 64), dim3(256), wg_lds_bytes<T>(), st, a);
+      if constexpr (sizeof(T) == 2) {
+        if (ws) hipLaunchKernelGGL((wgrad_ws_kernel<T>), grid, block, wg_ws_lds_bytes<T>(), st, a);
+      }
+      if (!ws) hipLaunchKernelGGL((wgrad_kernel<T>), grid, block, wg_lds_bytes<T>(), st, a);
     }
     hla_prof_end(st);
     const size_t n = (size_t)a.Cout * a.Cin * 9;

@@ -2309,7 +2309,7 @@ def test_fp32_class_modes_need_fp32_lm_maps():
 @pytest.mark.parametrize('precision', ['fp16x3', 'bf16'])
 def test_wave_specialised_wgrad_matches_the_two_phase_kernels(precision, monkeypatch):
     """Round 5's weight-gradient kernels (wgrad_split_ws_kernel / wgrad_ws_kernel: 4 matrix + 4 loader waves per CU, 256 resident
-    workgroups) against the round-4 kernels they replace (args.wgrad_two_phase = 1 -> HLA_VGG_BWD_WGRAD_TWO_PHASE: wgrad_split_kernel / wgrad_dma_kernel /
+    workgroups) against the two-phase kernels they replace (args.wgrad_two_phase = 1 -> HLA_VGG_BWD_WGRAD_TWO_PHASE: wgrad_split_kernel /
     wgrad_kernel, 512 workgroups): the same products in a different split-K grouping, so every weight and bias gradient of a
     full-shape training step must agree to the order of the partial sums: 1e-5 of the tensor's norm in split mode, whose products
     are fp32-class; for bf16 2e-3 or four times what the SAME kernels differ by from one run to the next (the LM backward's

@@ -9,7 +9,8 @@ Shapes (B, H, W) -- H and W multiples of 8 -- and the edge each one hits:
   * (4, 264, 296), level 3, fp32 / fp16x3: every weight-gradient launch has more tiles than k-split workgroups (below)
 
 fp32 / fp16x3 run forward and backward against fp64 (the oracle and its autograd); bf16 / fp16 run the forward against
-``vgg_round16.forward`` -- the same fp64 arithmetic with the kernels' 16-bit rounding points -- see ``test_forward_16bit``.
+``vgg_round16.forward`` -- the same fp64 arithmetic with the kernels' 16-bit rounding points -- see ``test_forward_16bit``;
+their backward is checked for agreement between its two weight-gradient groupings (``test_backward_16bit_wgrad_groupings_agree``).
 The references of a case are computed once per session and shared by every precision (``_REFS``).
 """
 import numpy as np
@@ -374,6 +375,52 @@ def test_backward_many_tiles(precision, two_phase):
     fwd, grads, g64, g32 = _run_backward(tag, r, level, precision, _dev(), wgrad_two_phase=two_phase)
     _check_forward_fp32_class(tag, *fwd, r)
     _check_backward(tag, grads, r, g64, g32)
+
+
+GROUPING_TOL = 1e-5     # the same exact products in another split-K grouping: relative L2 of a tensor (fp32 summation order only)
+CONV0_TOL = 2e-3        # conv0.*: bit 0 also moves conv0's gradient from the fused epilogue to the stored 16-bit map's kernel
+_GROUPINGS = [(n, lv, {}) for n, lv in CASE_IDS] + [('odd_pooled', 3, dict(scale_invariant=True, dense=True, first_row8=4))]
+_GROUPING_IDS = [f'{n}-L{lv}' for n, lv in CASE_IDS] + ['odd_pooled-L3-first_row8']
+
+
+@pytest.mark.parametrize('case,level,kw', _GROUPINGS, ids=_GROUPING_IDS)
+@pytest.mark.parametrize('precision', ['bf16', 'fp16'])
+def test_backward_16bit_wgrad_groupings_agree(case, level, kw, precision):
+    """bf16 / fp16: one training forward, then the backward twice on the same saved context and upstream gradient -- with the
+    wave-specialised weight-gradient kernel (256 k-split workgroups) and with the two-phase kernel (``wgrad_two_phase`` = 1,
+    512).  A product of two 16-bit values is exact in fp32, so the two runs differ in the order of fp32 sums only: every
+    gradient to 1e-5 of its norm (the split-mode bound of test_wave_specialised_wgrad_matches_the_two_phase_kernels; no LM
+    backward here, so no atomics), conv0.* to 2e-3 (bit 0 also selects the stored-map conv0 kernel:
+    test_fused_conv0_weight_gradient_matches_the_stored_map_kernel).  The extra case trims the launches to ODD first rows
+    (first_row8 = 4 at H = 40 with confidence heads: row 15 at H/2) -- the tile origins the loaders must carry through the
+    upsample shift; both runs get the same flags."""
+    from highlyaccurate_amd.VGG import vgg_forward_nhwc, vgg_backward_nhwc
+    B, H, W, _ = CASES[case]
+    r = _ref((B, H, W), level)
+    d = _dev()
+    tag = f'groupings {precision} {case} {(B, H, W)} L{level} {kw}'
+    net = _net(r['sd'], level, precision)
+    feats, confs, inv, ctx = vgg_forward_nhwc(net, r['x'].to(d), want_conf=True, defer_norm=True, save_for_backward=True)
+    dfe = [_nhwc(u, d, r['pad'] if l == 3 else None) for l, u in enumerate(r['ups'])]
+    dcs = [u[:, 0].contiguous().float().to(d) for u in r['cups']]
+    g_ws, g_tp = [{k: g.detach().double().cpu() for k, g in vgg_backward_nhwc(net, ctx, dfe, confs, dcs, wgrad_two_phase=tp, **kw).items()}
+                  for tp in (0, 1)]
+    assert set(g_ws) == set(g_tp), (tag, sorted(set(g_ws) ^ set(g_tp)))
+    worst, worst0, bad = (0.0, ''), (0.0, ''), []
+    for k in sorted(g_ws):
+        n_ws, n_tp = float(g_ws[k].norm()), float(g_tp[k].norm())
+        assert n_ws > 0 and n_tp > 0 and np.isfinite(n_ws) and np.isfinite(n_tp), (tag, k, n_ws, n_tp)
+        e = float((g_ws[k] - g_tp[k]).norm()) / n_tp
+        conv0 = k.startswith('conv0.')
+        if conv0:
+            worst0 = max(worst0, (e, k))
+        else:
+            worst = max(worst, (e, k))
+        if e > (CONV0_TOL if conv0 else GROUPING_TOL):
+            bad.append((k, e))
+    print(f'{tag}: worst relative L2 {worst[0]:.2e} ({worst[1]}), gate {GROUPING_TOL:.0e}; conv0 {worst0[0]:.2e} ({worst0[1]}), '
+          f'gate {CONV0_TOL:.0e}; {len(g_ws)} tensors')
+    assert not bad, (tag, bad)
 
 
 def _check_forward_16bit(tag, got, emu, exact):
