@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class HlaError(RuntimeError):
@@ -178,6 +178,19 @@ def load() -> C.CDLL:
     lib.hla_pose_loss.argtypes = [C.POINTER(PoseLossArgs), vp, vp]
     lib.hla_pose_loss_bwd.restype = i
     lib.hla_pose_loss_bwd.argtypes = [C.POINTER(PoseLossArgs), C.POINTER(vp), C.POINTER(vp), C.POINTER((C.c_longlong * 3) * 3), vp]
+    ll, dbl = C.c_longlong, C.c_double
+    lib.hla_orien_corr_workspace_bytes.restype = sz
+    lib.hla_orien_corr_workspace_bytes.argtypes = [i, i, i, i, i]
+    lib.hla_orien_corr.restype = i
+    lib.hla_orien_corr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+    lib.hla_orien_corr_bwd.restype = i
+    lib.hla_orien_corr_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+    lib.hla_orien_window_bwd.restype = i
+    lib.hla_orien_window_bwd.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp]
+    lib.hla_orien_triplet_loss.restype = i
+    lib.hla_orien_triplet_loss.argtypes = [vp, vp, ll, dbl, dbl, vp, i, i, i, vp]
+    lib.hla_orien_triplet_loss_bwd.restype = i
+    lib.hla_orien_triplet_loss_bwd.argtypes = [vp, vp, ll, dbl, dbl, vp, vp, i, i, vp]
     lib.hla_prof_enable.restype = i
     lib.hla_prof_enable.argtypes = [i]
     lib.hla_prof_kernel_name.restype = C.c_char_p

@@ -51,6 +51,21 @@ def ground_plane_table(K_ori, grd_H, grd_W, ori_H, ori_W):
     return (xyz_w * w)[0].contiguous()
 
 
+def polar_plane_table(grd_H, grd_W):
+    """proj='polar' (grd_img2cam_polar, models_kitti.py:684-698 / models_ford.py:157-171): the level map is read as a polar fan on
+    the ground plane -- column u is a bearing over 45 degrees, row v a range that falls from 30 m at the top row to 30/grd_H m at
+    the bottom one.  Same fp32 op sequence as the reference so the table is bit-identical.  Every point has z > 0, so the
+    reference's all-ones mask is what the kernels' z > 0 test gives.  Returns xyz [h,w,3] fp32 (CPU)."""
+    v, u = torch.meshgrid(torch.arange(0, grd_H, dtype=torch.float32),
+                          torch.arange(0, grd_W, dtype=torch.float32), indexing='ij')
+    theta = u / grd_W * np.pi / 4
+    radius = (1 - v / grd_H) * 30
+    z = radius * torch.cos(np.pi / 4 - theta)
+    x = -radius * torch.sin(np.pi / 4 - theta)
+    y = utils.Camera_height * torch.ones_like(z)
+    return torch.stack([x, y, z], dim=-1).contiguous()
+
+
 def ford_K_network_input():
     """models_ford.py:116-130: K_FL rescaled from the 860x1656 sensor to the 256x1024 network input."""
     K = torch.tensor(FORD_K_FL, dtype=torch.float32).reshape(3, 3)
@@ -201,8 +216,19 @@ class S2GPBase(nn.Module):
         if args.level not in ((2, 3, 4) if self.ford else (3, 4)):
             raise NotImplementedError('args.level must be 3 (x15, x18, x21) or 4 (+ x24)' +
                                       (', or 2 (x18, x21)' if self.ford else "; the reference's KITTI model is shape-inconsistent at level 2"))
-        if getattr(args, 'proj', 'geo') != 'geo':
-            raise NotImplementedError("only proj='geo' is in scope")
+        # proj='polar' (train_kitti.py:472, train_ford.py:396): the polar table of `polar_plane_table` and the WHOLE level map in
+        # every step (models_kitti.py:1194-1205, models_ford.py:738-749) instead of its bottom half.  The reference takes that
+        # branch for any string other than 'geo' (an `else`); here anything else is an error.
+        proj = getattr(args, 'proj', 'geo')
+        if proj not in ('geo', 'polar'):
+            raise NotImplementedError(f"{type(self).__name__}: proj must be 'geo' or 'polar', got {proj!r} (the reference runs its "
+                                      "polar branch for any other string, 'nn' and 'CrossAttn' included: that accident is not copied)")
+        self.polar = proj == 'polar'
+        if self.polar and self.ford and args.level == 2:
+            # models_ford.py:59-65 builds the level-2 tables with grd_img2cam whatever args.proj is, and the loop then reads the
+            # whole map through the ground-plane table (rows above the horizon masked by z > 0)
+            raise NotImplementedError("LM_S2GP_Ford(level=2, proj='polar'): the reference pairs the whole-map loop with the "
+                                      "ground-plane tables there; that combination is not built (use level 3 or 4)")
         opt = getattr(args, 'Optimizer', 'LM')
         # KITTI (models_kitti.py:1176-1283): LM, SGD, ADAM, NN.  Ford (models_ford.py:751-788): LM, GN, NN and an SGD_update
         # (609-634, a sign-of-residual step of 0.001) that indexes its [B,3] update with three subscripts and raises as shipped.
@@ -232,12 +258,14 @@ class S2GPBase(nn.Module):
     def xyz_tables(self, grd_H: int, grd_W: int, device):
         """Per-level ground-plane tables.  K is given for a 256x1024 image (models_kitti.py:657-667); the
         table of level l is grd_img2cam(H/2^(3-l), W/2^(3-l), 256, 1024): identical to the reference for its
-        own 256x1024 input, and the same camera resampled for any other input size (BASELINE config 5)."""
+        own 256x1024 input, and the same camera resampled for any other input size (BASELINE config 5).
+        proj='polar': grd_img2cam_polar(H/2^(3-l), W/2^(3-l)) instead (models_kitti.py:626-633, models_ford.py:54-58)."""
         key = (grd_H, grd_W, str(device))
         if key not in self._tables:
             K = ford_K_network_input() if self.ford else KITTI_K
-            self._tables[key] = [ground_plane_table(K, grd_H / 2 ** (3 - l), grd_W / 2 ** (3 - l), 256, 1024).to(device)
-                                 for l in range(4)]
+            hw = [(grd_H / 2 ** (3 - l), grd_W / 2 ** (3 - l)) for l in range(4)]
+            self._tables[key] = [(polar_plane_table(h, w) if self.polar else ground_plane_table(K, h, w, 256, 1024)).to(device)
+                                 for h, w in hw]
         # level 2 (Ford, models_ford.py:59-65): grd_img2cam(H / 2^(2 - l)) for l = 0, 1 = the H/4 and H/2 tables
         return self._tables[key][1:3] if self.level == 2 else self._tables[key]
 
@@ -310,8 +338,9 @@ class S2GPBase(nn.Module):
             s, g = sat_feats[l], grd_feats[l]
             A, w, Cn = s.shape[1], g.shape[2], g.shape[3]
             h = tables[l].shape[0]                     # the level's full map height; g may hold only its last rows
+            row0 = 0 if self.polar else h // 2         # first row the loop reads: the bottom half for 'geo', the whole map for 'polar'
             skip = h - g.shape[1]
-            if not (s.shape[2] == A and s.shape[3] == Cn and tuple(tables[l].shape) == (h, w, 3) and 0 <= skip <= h // 2
+            if not (s.shape[2] == A and s.shape[3] == Cn and tuple(tables[l].shape) == (h, w, 3) and 0 <= skip <= row0
                     and g.shape[0] == s.shape[0] and s.is_contiguous() and g.is_contiguous()
                     and s.dtype == g.dtype and s.dtype in _FEAT_DTYPES):
                 raise ValueError(f'level {l}: inconsistent feature maps sat {tuple(s.shape)} / grd {tuple(g.shape)} '
@@ -321,7 +350,7 @@ class S2GPBase(nn.Module):
             lv[l].xyz = tables[l].data_ptr()
             lv[l].sat_inv_norm = sat_inv_norm[l].data_ptr() if sat_inv_norm is not None else 0
             lv[l].grd_inv_norm = grd_inv_norm[l].data_ptr() if grd_inv_norm is not None else 0
-            lv[l].A, lv[l].h, lv[l].w, lv[l].C, lv[l].row0, lv[l].grd_row_skip = A, h, w, Cn, h // 2, skip
+            lv[l].A, lv[l].h, lv[l].w, lv[l].C, lv[l].row0, lv[l].grd_row_skip = A, h, w, Cn, row0, skip
             if self.ford:
                 lv[l].meter_per_pixel = float(extra['side_m']) / A          # models_ford.py:230
                 lv[l].centre = float(A // 2)                                # models_ford.py:231
@@ -376,8 +405,8 @@ class S2GPBase(nn.Module):
         """The buffers ``hla_s2g_lm_solve_bwd`` accumulates into, cleared where they have to be by ONE launch (``hla_zero_fill``) on
         the current stream: (d_sat[l], d_grd[l], d_conf[l] or None, d_lambda[4]).
         * d_sat: zero-filled (the scatter adds); with ``deterministic`` not at all (the closing pass writes every element).
-        * d_grd: the loop only touches rows h_l/2.. and WRITES them on each level's first visit (cfg.grd_grad_overwrite): no
-          zero-fill and no read-modify-write of half a map there.  What still has to be zero is what the consumer reads above
+        * d_grd: the loop only touches rows row0_l.. (h_l/2; 0 for proj='polar', where nothing is left to clear) and WRITES them
+          on each level's first visit (cfg.grd_grad_overwrite): no zero-fill and no read-modify-write of half a map there.  What still has to be zero is what the consumer reads above
           them: with hla_vgg_backward(first_row8 = f) two rows (it never reads d_grd[l] above row f * 2^l - 2), else the top half.
         * d_conf: zero-filled (added to).  d_lambda: written by the call."""
         L = len(sat_feats)
@@ -479,9 +508,10 @@ class S2GPBase(nn.Module):
         else:
             sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16)
         grd_in = grd_img
-        # (only LM_update renormalises the ground features; SGD / ADAM see the whole-map L2_norm scale, so they need every row)
+        # (only LM_update renormalises the ground features; SGD / ADAM see the whole-map L2_norm scale, so they need every row;
+        #  proj='polar' reads every row of every map, so there the flag is inert)
         dead_ok = (not return_confs and self.level == 3 and getattr(self.args, 'Optimizer', 'LM') == 'LM'
-                   and bool(getattr(self.args, 'ground_crop', 1)))
+                   and bool(getattr(self.args, 'ground_crop', 1)) and not self.polar)
         skip = dead_ground_rows(grd_img.shape[-2]) if dead_ok else 0
         if skip:
             grd_in = grd_img[:, :, skip:, :]         # a row window, passed as it lies in memory (hla_vgg_forward's x_plane): no copy
@@ -509,6 +539,10 @@ class S2GPBase(nn.Module):
             raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
                              f'and {tuple(grd_img.shape)}')
         _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
+        if self.polar and self.ford and level_first:
+            # models_ford.py:935-950: the level-first loop has no proj branch and reads the bottom half of the polar table
+            raise NotImplementedError("LM_S2GP_Ford(proj='polar') with level_first=1: the reference's level-first loop reads only "
+                                      "the bottom half of the polar maps (it has no proj branch); that combination is not built")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             names = [n for n, _ in self.named_parameters()]
             params = [p for _, p in self.named_parameters()]
@@ -591,7 +625,7 @@ def dead_ground_rows(H: int) -> int:
 def _bwd_first_row8(model, grd_hw, x21_rows: int) -> int:
     """hla_vgg_backward's first_row8 for the ground branch: the ground maps' gradient lives in rows h_l/2.. (all the LM loop reads),
     so the backward skips the rows above its support (level 3, LM_update, args.bwd_trim)."""
-    inv = getattr(model.args, 'Optimizer', 'LM') == 'LM'
+    inv = getattr(model.args, 'Optimizer', 'LM') == 'LM' and not model.polar      # (proj='polar': every row carries gradient)
     f8 = (grd_hw[0] // 8) // 2 - (grd_hw[0] - x21_rows * 2) // 8
     return f8 if (inv and f8 >= 4 and model.level == 3 and bool(getattr(model.args, 'bwd_trim', 1))) else 0
 
@@ -610,7 +644,8 @@ class _LocaliseFn(torch.autograd.Function):
         # LM_update, forward and backward).  What changes is the 14th element of the train-mode tuple: the returned confidence
         # maps are then only computed from the crop on (valid from row h_l/2, zero above the crop).
         skip = 0
-        if getattr(model.args, 'train_ground_crop', 0) and model.level == 3 and getattr(model.args, 'Optimizer', 'LM') == 'LM':
+        if (getattr(model.args, 'train_ground_crop', 0) and model.level == 3 and getattr(model.args, 'Optimizer', 'LM') == 'LM'
+                and not model.polar):                   # (proj='polar' reads every row: no crop, whatever the flag says)
             skip = dead_ground_rows(grd_img.shape[-2])
         grd_in = grd_img[:, :, skip:, :] if skip else grd_img      # (a view: the extractor takes the window's plane stride)
         grd_feats, grd_confs, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_in, want_conf=want_conf,

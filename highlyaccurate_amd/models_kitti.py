@@ -5,14 +5,62 @@ The hot path (two VGG U-Nets, projection + Jacobian, N_iters x levels LM steps) 
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
+from . import _orien
 from ._g2sp import LM_G2SP  # noqa: F401  (models_kitti.py:22-499)
 from ._s2gp import S2GPBase, loss_func, loss_from_trace  # noqa: F401  (loss_func re-exported like the reference module)
 
 
 class LM_S2GP(S2GPBase):
     ford = False
+
+    def __init__(self, args):
+        super().__init__(args)
+        # models_kitti.py:642-646: built for four levels whatever args.level is (plain CPU tensors, not buffers: the state dict
+        # keeps the reference's 49 keys); device copies and the column windows of orien_corr are cached per device
+        self.polar_grids = [self.polar_coordinates(level) for level in range(4)]
+        self._polar_cache = {}
+        self.last_orien_corr = None      # [(corr [B,S] fp32, degree_per_pixel)] per level of the last orien_corr call (an extension)
+
+    # -- the coarse heading search (models_kitti.py:1494-1624) -------------------------------
+    def polar_coordinates(self, level):
+        """models_kitti.py:1518-1541: [1, A//2, 8A, 2] sampling coordinates of the polar satellite map, A = 512 / 2^(3-level)."""
+        return _orien.polar_coordinates(self.meters_per_pixel[level], level)
+
+    def polar_transform(self, sat_feat, level):
+        """models_kitti.py:1494-1516: sat_feat [B,C,A,A] -> its polar resampling [B,C,A//2,8A] (the grid is built for the map's
+        own A, as there)."""
+        from .jacobian import grid_sample
+        B, _, A, _ = sat_feat.shape
+        grd_H, grd_W = A // 2, A * 2
+        v, u = torch.meshgrid(torch.arange(0, grd_H, dtype=torch.float32), torch.arange(0, 4 * grd_W, dtype=torch.float32), indexing='ij')
+        theta = u / grd_W * np.pi * 2
+        radius = (1 - v / grd_H) * 40 / self.meters_per_pixel[level]
+        us = A / 2 + radius * torch.cos(np.pi / 4 - theta)
+        vs = A / 2 - radius * torch.sin(np.pi / 4 - theta)
+        grids = torch.stack([us, vs], dim=-1).unsqueeze(dim=0).repeat(B, 1, 1, 1).to(sat_feat.device)
+        return grid_sample(sat_feat, grids)[0]
+
+    def _polar_window(self, level, n, W, B, device):
+        """[B,H,W+S-1,2]: the columns of polar_grids[level] that the shifts of orien_corr read (``_orien.window_columns``), built
+        once per (device, level, n, W, B)."""
+        key = (str(device), level, n, W, B)
+        if key not in self._polar_cache:
+            g = self.polar_grids[level]
+            cols = torch.tensor(_orien.window_columns(g.shape[2], W, n), dtype=torch.long)
+            self._polar_cache[key] = g[:, :, cols, :].to(device).expand(B, -1, -1, -1).contiguous()
+        return self._polar_cache[key]
+
+    def orien_corr(self, sat_map, grd_img_left, gt_shiftu=None, gt_shiftv=None, gt_heading=None, mode='train',
+                   file_name=None, gt_depth=None):
+        """models_kitti.py:1543-1605, the reference's signature.  mode='train' -> the triplet loss (1607-1624), a scalar that
+        back-propagates into both extractors; any other mode -> the argmin heading of the LAST level, [B] in degrees.
+        ``self.last_orien_corr`` keeps (corr [B,S], degree_per_pixel) of every level.  sat_map must be 512 x 512 and the ground
+        image 256 rows high (the polar grids are built for that, as in the reference); the correlation reads fp32 maps in
+        every precision mode."""
+        return _orien.orien_corr(self, sat_map, grd_img_left, gt_heading, mode)
 
     def forward(self, sat_map, grd_img_left, gt_shiftu=None, gt_shiftv=None, gt_heading=None, mode='train',
                 file_name=None, gt_depth=None, loop=0, level_first=0, init_pose=None):

@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 23
+#define HLA_ABI_VERSION 24
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -273,7 +273,8 @@ typedef struct hla_s2g_level {
   const double* sat_inv_norm; /* [B] or NULL: sat_feat is raw, multiply by this (HLA_VGG_DEFER_NORM) */
   const double* grd_inv_norm; /* [B] or NULL: same for grd_feat */
   int A, h, w, C;
-  int row0;              /* first ground-image row that takes part (h/2 for proj=='geo') */
+  int row0;              /* first ground-image row that takes part: h/2 for proj=='geo' (models_kitti.py:1194-1199); 0 for
+                            proj=='polar' (1200-1205: the whole map, with the table of grd_img2cam_polar, 684-698, in xyz) */
   int grd_row_skip;      /* rows [0,grd_row_skip) of the ground map are not stored (<= row0): only the bottom half is
                             ever read (models_kitti.py:1194-1199), so a caller may extract features for the rows whose
                             receptive field reaches it and nothing above -- see DESIGN.md "dead rows"; 0 = full map */
@@ -442,6 +443,56 @@ int hla_pose_loss(const hla_pose_loss_args* args, void* out, hla_stream_t stream
  * dx[k]: gradient w.r.t. x[k], every element (b,n,l) written at dx[k][b t0 + n t1 + l t2], (t0,t1,t2) = dx_stride[k]. */
 int hla_pose_loss_bwd(const hla_pose_loss_args* args, const void* const g_out[9], float* const dx[3],
                       const long long dx_stride[3][3], hla_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * LM_S2GP.orien_corr  (models_kitti.py:1543-1605) and triplet_loss (1607-1624): the coarse heading search
+ * ------------------------------------------------------------------------- */
+/* One level of orien_corr behind the polar resampling.  The caller samples the WINDOW of the polar satellite map the shifts
+ * read -- the columns of the reference's polar_sat1 (1582-1585): -n .. W+n-1 of polar_coordinates(level) (1518-1541) modulo its
+ * width for 0 < n <= that width, n = ceil(rotation_range / (90 / W)), S = 2n + 1 -- with hla_grid_sample from the raw satellite map
+ * (and takes d_P1 back through hla_orien_window_bwd).
+ *   P1            [B,H,W+S-1,C] NHWC fp32;  p1_inv_norm [B] fp64 or NULL: P1 is multiplied by it (the map was sampled raw,
+ *                 HLA_VGG_DEFER_NORM; sampling is linear)
+ *   grd_feat      [B,H,W,C] NHWC fp32;  grd_inv_norm [B] fp64 or NULL likewise.  With f = grd_inv_norm * grd_feat:
+ *                 g = f / max(||f||_2, 1e-12) per sample (F.normalize, 1572)
+ *   S             the number of shifts (the width of the reference's conv2d output)
+ *   dot   [B,S] fp64 out   sum_{h,w,c} P1[b,h,w+s,c] g[b,h,w,c]                (the grouped conv2d, 1588-1589)
+ *   E     [B,S] fp64 out   sum_{h,w<W,c} P1[b,h,w+s,c]^2                       (avg_pool2d, divisor_override=1, 1591-1592)
+ *   gnorm [B]   fp64 out   ||f||_2
+ *   corr  [B,S] fp32 out   2 - 2 dot / max(sqrt(E), 1e-6)                      (1593-1594)
+ * Block partials are fp32 and reduced in a fixed order in fp64: the result does not depend on the order the blocks finish in.
+ * C in {16, 64, 128, 256}; any H, W (B, H <= 65535), S >= 1.  workspace: hla_orien_corr_workspace_bytes (serves both calls). */
+size_t hla_orien_corr_workspace_bytes(int B, int H, int W, int C, int S);
+int hla_orien_corr(const float* P1, const float* grd_feat, const double* p1_inv_norm, const double* grd_inv_norm, double* dot,
+                   double* E, double* gnorm, float* corr, void* workspace, size_t workspace_bytes, int B, int H, int W, int C,
+                   int S, hla_stream_t stream);
+/* Backward (what autograd derives from 1572-1594): d_corr [B,S] fp32 and the forward's dot, E, gnorm ->
+ *   d_P1       [B,H,W+S-1,C]  w.r.t. p1_inv_norm * P1:  sum_s ddot[s] g[.,x-s,.] + 2 (p1_inv_norm P1) beta[x], where
+ *              ddot = -2 d_corr / D, D = max(sqrt(E), 1e-6), beta[x] = sum of d_corr dot / D^3 over the shifts whose window covers
+ *              column x and whose sqrt(E) is not clamped (no gradient flows through a clamped E)
+ *   d_grd_feat [B,H,W,C]     w.r.t. f:  (d_g - g (g . d_g)) / ||f||,  d_g = sum_s ddot[s] P1[.,w+s,.]  (the projection is the second
+ *              normalisation's; what hla_vgg_backward takes as d_feat)
+ * Both are WRITTEN, in gather form: no atomics, bitwise reproducible. */
+int hla_orien_corr_bwd(const float* P1, const float* grd_feat, const double* p1_inv_norm, const double* grd_inv_norm,
+                       const double* dot, const double* E, const double* gnorm, const float* d_corr, float* d_P1,
+                       float* d_grd_feat, void* workspace, size_t workspace_bytes, int B, int H, int W, int C, int S,
+                       hla_stream_t stream);
+/* Backward of that window sampling (hla_grid_sample(image, optical) -> out, no jac) to the image, for this consumer: near the
+ * centre of the polar fan a texel collects about a thousand largely cancelling terms, which hla_grid_sample_bwd's fp32 atomics
+ * sum to 7-10 fp32 ulps of the map's maximum, differently in every run.  Here they are summed in fp64 (hardware fp64 atomics) and
+ * rounded once: the result is the correctly rounded sum up to 1e-16 relative, whatever the order.
+ *   optical [N,H,W,2], d_out [N,H,W,C] fp32;  acc [N,IH,IW,C] fp64 scratch (cleared by the call);  d_image [N,IH,IW,C] fp32 WRITTEN */
+int hla_orien_window_bwd(const float* optical, const float* d_out, double* acc, float* d_image, int N, int C, int IH, int IW,
+                         int H, int W, hla_stream_t stream);
+/* triplet_loss of one level (1611-1622): sum_{b,s} log(1 + exp(10 (corr[b,gt_b] - corr[b,s]))) / (B (S - 1)) with
+ * gt_b = (S-1)/2 + round(gt_heading[b] * rotation_range / degree_per_pixel) (fp32, half to even, as the reference's tensors; an
+ * index outside [-S,S), where the reference raises, gives NaN).  loss[0] (fp32) is written, or added to when accumulate != 0
+ * (the sum over the levels, 1624).  gt_heading: element b at gt_heading[b * gt_stride]. */
+int hla_orien_triplet_loss(const float* corr, const float* gt_heading, long long gt_stride, double rotation_range,
+                           double degree_per_pixel, float* loss, int accumulate, int B, int S, hla_stream_t stream);
+/* d_corr [B,S] fp32 (written) = g_loss[0] * d(loss of this level)/d(corr) */
+int hla_orien_triplet_loss_bwd(const float* corr, const float* gt_heading, long long gt_stride, double rotation_range,
+                               double degree_per_pixel, const float* g_loss, float* d_corr, int B, int S, hla_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline numbers).
