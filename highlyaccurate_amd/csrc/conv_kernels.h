@@ -22,6 +22,8 @@
 //   backward stage it through registers.  Weights are prefetched 1-2 taps ahead into a register ring.
 //   The loader handles "virtual concat + nearest 2x upsample" (VGG.py:144-151) without materialising it.
 //   The epilogue fuses bias, 2x2 max-pool, ReLU, the raw fp32 feature copy and its per-sample sum of squares.
+//   The 16-bit forward launches of the Cout >= 128 classes run the same walk on v_mfma_f32_16x16x32 (M = 16 couts, N = 16 pixels,
+//   K = the stage's 32 channels at once): template parameter SHAPE, AccMap below, kConvClassShape at launch_conv.
 // conv02_kernel -- conv0 (3->64 on the NCHW fp32 input, K = 27 padded to 32) computed by MFMA directly into the
 //   LDS halo tile of conv2, then conv2 + pool: the 64-channel full-resolution map never touches HBM.
 #include "common.h"
@@ -117,6 +119,43 @@ template <> __device__ __forceinline__ void mma16<float>(f32x16& acc, const uint
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w.y), __uint_as_float(p.y), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w.z), __uint_as_float(p.z), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w.w), __uint_as_float(p.w), acc, 0, 0, 0);
+}
+
+// ---- MFMA shape of the 16-bit forward conv3x3 kernels (template parameter SHAPE of conv3x3_kernel and what it is built from).
+// Both shapes compute D^T = W * X^T (A = weight fragment, B = pixel fragment) on a 32-pixel x 32-cout wave tile per (row i,
+// cout tile j), and a stage's 32 channels take the same matrix-pipe time either way:
+//   SHAPE_32x32x16: one f32x16 accumulator; the stage's channels are walked as 2 k-groups of 16
+//   SHAPE_16x16x32: four f32x4 accumulators t[2p + c] (pixel half p, cout half c); one MFMA takes all 32 channels
+// AccMap<SHAPE> is the ONE place that knows which (pixel, cout) a lane's accumulator register holds.  A lane's registers of a
+// tile are four quads q of four consecutive couts e = 0..3 of one pixel:
+//   SHAPE_32x32x16: pixel l&31 for every q,   couts 8q + 4(l>>5) + e
+//   SHAPE_16x16x32: pixel 16(q>>1) + (l&15),  couts 16(q&1) + 4(l>>4) + e
+// In both, pixel parity = lane parity (the 2x2 pooling pairs lane l with l^1).
+enum { SHAPE_32x32x16 = 0, SHAPE_16x16x32 = 1 };
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+struct Acc16x16 { f32x4 t[4]; };
+template <int SHAPE> struct AccMap;
+template <> struct AccMap<SHAPE_32x32x16> {
+  using Tile = f32x16;
+  static __device__ __forceinline__ float get(const Tile& a, int q, int e) { return a[q * 4 + e]; }
+  static __device__ __forceinline__ void set(Tile& a, int q, int e, float v) { a[q * 4 + e] = v; }
+  static __device__ __forceinline__ int px(int lane, int) { return lane & 31; }
+  static __device__ __forceinline__ int ch(int lane, int q) { return 8 * q + 4 * (lane >> 5); }
+};
+template <> struct AccMap<SHAPE_16x16x32> {
+  using Tile = Acc16x16;
+  static __device__ __forceinline__ float get(const Tile& a, int q, int e) { return a.t[q][e]; }
+  static __device__ __forceinline__ void set(Tile& a, int q, int e, float v) { a.t[q][e] = v; }
+  static __device__ __forceinline__ int px(int lane, int q) { return 16 * (q >> 1) + (lane & 15); }
+  static __device__ __forceinline__ int ch(int lane, int q) { return 16 * (q & 1) + 4 * (lane >> 4); }
+};
+// v_mfma_f32_16x16x32: A lane l = cout row l&15, B lane l = pixel column l&15, both k = 8(l>>4) + e
+template <typename T> __device__ __forceinline__ void mma32(f32x4& acc, const uint4& w, const uint4& p);
+template <> __device__ __forceinline__ void mma32<bf16>(f32x4& acc, const uint4& w, const uint4& p) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, p), acc, 0, 0, 0);
+}
+template <> __device__ __forceinline__ void mma32<f16>(f32x4& acc, const uint4& w, const uint4& p) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, p), acc, 0, 0, 0);
 }
 
 // ---- k-major operand fragments (weight-gradient kernels, vgg_backward.hip; the fused conv0 weight gradient below)
@@ -278,20 +317,31 @@ constexpr int HALO_TAP0 = 2, HALO_TAP1 = 6;
 constexpr int HLA_CONV_DMA_TAP = 1;
 // per-lane byte offsets of a wave's pixel fragments: [kx][kg] -> (x + kx) * PSTR + swizzled slot of (lane half g, k-group kg),
 // relative to the wave's first halo row
+// SHAPE_16x16x32: [kx][p] -> pixel half p of the row (16 p + (lane & 15)), channel slot lane >> 4: a 16-lane group of the
+// ds_read_b128 still covers 16 consecutive pixels of one row and one slot, which is what makes the swizzle conflict-free
 struct FragOff { int o[3][2]; };
+template <int SHAPE = SHAPE_32x32x16>
 __device__ __forceinline__ FragOff frag_offsets(int lane, int row0) {
-  const int x = lane & 31, g = lane >> 5;
   FragOff f;
+  if constexpr (SHAPE == SHAPE_16x16x32) {
+    const int x = lane & 15, slot = lane >> 4;
 #pragma unroll
-  for (int kx = 0; kx < 3; ++kx)
+    for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
-    for (int kg = 0; kg < 2; ++kg) f.o[kx][kg] = halo_off(row0 * HWID + x + kx, x + kx, g | (kg << 1));
+      for (int p = 0; p < 2; ++p) f.o[kx][p] = halo_off(row0 * HWID + 16 * p + x + kx, 16 * p + x + kx, slot);
+  } else {
+    const int x = lane & 31, g = lane >> 5;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+      for (int kg = 0; kg < 2; ++kg) f.o[kx][kg] = halo_off(row0 * HWID + x + kx, x + kx, g | (kg << 1));
+  }
   return f;
 }
 
 // ---------------------------------------------------------------------------------------------
 // shared epilogue: acc[i][j] holds, for lane (x = lane&31, g = lane>>5), output channels
-// cb + j*32 + 8q + 4g + {0..3} (q = r>>2) of pixel (row i, column x).
+// cb + j*32 + 8q + 4g + {0..3} (q = r>>2) of pixel (row i, column x) -- SHAPE_32x32x16; AccMap<SHAPE> in general.
 // Writing that straight to NHWC memory is 8 B per lane into 32 different 128-B lines per store instruction
 // (measured: 16-28 k cycles per wave, up to half of a block's lifetime).  Instead every wave transposes one
 // pixel row at a time through a private LDS region (`stage`, >= 32*(NT*32*4+16) bytes) and stores it as whole
@@ -413,8 +463,10 @@ __host__ __device__ __forceinline__ int epilogue_mode(const ConvArgs& a) {
 // ROUNDED values, so that inv_norm normalises exactly the map the LM loop will read.
 // STGW: bytes of the wave's row stager.  The activation-only form (EPI_ACT) stages as many output rows side by side as fit there
 // and stores them together: the LDS write -> read turn-around is paid once per batch instead of once per row.
-template <typename T, int MT, int NT, bool POOL, int EPI = EPI_GENERIC, bool R16 = false, int STGW = 0>
-__device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvArgs& a, int b, int yrow0, int x0,
+// SHAPE: which (pixel, cout) a lane's accumulator registers hold (AccMap); every loop below walks them as quads q of four
+// consecutive couts of one pixel, which is what RowStager::put takes.
+template <typename T, int MT, int NT, bool POOL, int EPI = EPI_GENERIC, bool R16 = false, int STGW = 0, int SHAPE = SHAPE_32x32x16>
+__device__ __forceinline__ void conv_epilogue(typename AccMap<SHAPE>::Tile (&acc)[MT][NT], const ConvArgs& a, int b, int yrow0, int x0,
                                               int cb, float* red, char* stage, float dsc = 1.f,
                                               PixBox addb = PixBox{0, 1 << 30, 0, 1 << 30},
                                               const float4* prebias = nullptr) {      // [NT * 4] bias values the caller already holds
@@ -434,9 +486,18 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
   // registers in the 243-register main loop.
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
-  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), x = lane & 31, g = lane >> 5;
+  const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), even = !POOL || !(lane & 1);
+  using M = AccMap<SHAPE>;
   const int Ho = POOL ? a.H >> 1 : a.H, Wo = POOL ? a.W >> 1 : a.W;
   constexpr int NPX = POOL ? 16 : 32;
+  int pxq[4];            // per quad: the (pooled) pixel of the row segment it belongs to, and whether that column is inside the image
+  bool colok[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int xq = M::px(lane, q);
+    pxq[q] = POOL ? xq >> 1 : xq;
+    colok[q] = (x0 + xq < a.W) && even;
+  }
   float4 bias[NT][4];
 #pragma unroll
   for (int j = 0; j < NT; ++j)
@@ -452,7 +513,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) bias[j][q] = *(const float4*)(a.bias + cb + j * 32 + q * 8 + g * 4);
+      for (int q = 0; q < 4; ++q) bias[j][q] = *(const float4*)(a.bias + cb + j * 32 + M::ch(lane, q));
   }
   const int xo0 = POOL ? x0 >> 1 : x0;
   const int nvalid = min(NPX, Wo - xo0);              // pixels of this row segment inside the image
@@ -468,8 +529,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
 #pragma unroll
       for (int rr = 0; rr < RB; ++rr) {
         const int i = (r0 + rr) * STEP;
-        const bool lane_ok = (yrow0 + i < a.H) && (x0 + x < a.W) && (!POOL || !(x & 1));
-        const int px = POOL ? x >> 1 : x;
+        const bool rowok = yrow0 + i < a.H;
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -477,9 +537,9 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
             float w[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              float t = acc[i][j][q * 4 + e];
+              float t = M::get(acc[i][j], q, e);
               if (POOL) {
-                t = fmaxf(t, acc[i + 1][j][q * 4 + e]);
+                t = fmaxf(t, M::get(acc[i + 1][j], q, e));
                 t = fmaxf(t, lane_xor1(t));
               }
               if (Prec<T>::SPLIT) t *= dsc;
@@ -487,8 +547,8 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
             }
             if (!NOBIAS) { w[0] += bias[j][q].x; w[1] += bias[j][q].y; w[2] += bias[j][q].z; w[3] += bias[j][q].w; }
             w[0] = fmaxf(w[0], 0.f); w[1] = fmaxf(w[1], 0.f); w[2] = fmaxf(w[2], 0.f); w[3] = fmaxf(w[3], 0.f);
-            if (Prec<T>::SPLIT && lane_ok) mx = fmaxf(fmaxf(mx, fmaxf(w[0], w[1])), fmaxf(w[2], w[3]));
-            if (!POOL || !(x & 1)) RowStager<T, NT>::put(stage + rr * ROWB, px, j * 32 + q * 8 + g * 4, w[0], w[1], w[2], w[3]);
+            if (Prec<T>::SPLIT && rowok && colok[q]) mx = fmaxf(fmaxf(mx, fmaxf(w[0], w[1])), fmaxf(w[2], w[3]));
+            if (even) RowStager<T, NT>::put(stage + rr * ROWB, pxq[q], j * 32 + M::ch(lane, q), w[0], w[1], w[2], w[3]);
           }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -506,8 +566,15 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
     const int y = yrow0 + i;
     const int yo = POOL ? y >> 1 : y;
     const bool row_ok = y < a.H;                      // wave-uniform
-    const bool lane_ok = row_ok && (x0 + x < a.W) && (!POOL || !(x & 1));
-    const int px = POOL ? x >> 1 : x;
+    // (32x32x16: a lane has ONE pixel, and its test is spelled as one flag per row -- with a flag per quad the compiler contracts
+    //  the pooled kernels' sum of squares differently in the raw-copy and the generic form, whose bits must agree)
+    const bool lane_ok = row_ok && (x0 + M::px(lane, 0) < a.W) && even;
+    auto quad_ok = [&](int q) { return SHAPE == SHAPE_32x32x16 ? lane_ok : (row_ok && colok[q]); };
+    // 16x16x32 spells the multiply-adds out, so that every form of the epilogue rounds the sum alike by construction
+    auto sumsq4 = [&](float s, float v0, float v1, float v2, float v3) {
+      if constexpr (SHAPE == SHAPE_32x32x16) return s + (v0 * v0 + v1 * v1 + v2 * v2 + v3 * v3);
+      else return __builtin_fmaf(v3, v3, __builtin_fmaf(v2, v2, __builtin_fmaf(v1, v1, __builtin_fmaf(v0, v0, s))));
+    };
     float v[NT][4][4];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -515,9 +582,9 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
       for (int q = 0; q < 4; ++q) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float t = acc[i][j][q * 4 + e];
+          float t = M::get(acc[i][j], q, e);
           if (POOL) {
-            const float u = acc[i + 1][j][q * 4 + e];
+            const float u = M::get(acc[i + 1][j], q, e);
             if (pool_sum) {
               t += u;
               t += lane_xor1(t);
@@ -537,7 +604,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
     constexpr bool ONE_PASS = RAW && sizeof(T) == 2;
     if constexpr (ONE_PASS) {
       char* stage2 = stage + 32 * RowStager<RawT, NT>::PITCH;
-      if (!POOL || !(x & 1)) {
+      if (even) {
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -547,10 +614,10 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
               w0 = (float)(f16)fminf(fmaxf(w0, -65504.f), 65504.f); w1 = (float)(f16)fminf(fmaxf(w1, -65504.f), 65504.f);
               w2 = (float)(f16)fminf(fmaxf(w2, -65504.f), 65504.f); w3 = (float)(f16)fminf(fmaxf(w3, -65504.f), 65504.f);
             }
-            RowStager<RawT, NT>::put(stage, px, j * 32 + q * 8 + g * 4, w0, w1, w2, w3);
-            if (lane_ok) ss += w0 * w0 + w1 * w1 + w2 * w2 + w3 * w3;
+            RowStager<RawT, NT>::put(stage, pxq[q], j * 32 + M::ch(lane, q), w0, w1, w2, w3);
+            if (quad_ok(q)) ss = sumsq4(ss, w0, w1, w2, w3);
             if (a.out_act)      // (kernel-uniform)
-              RowStager<T, NT>::put(stage2, px, j * 32 + q * 8 + g * 4, fmaxf(w0, 0.f), fmaxf(w1, 0.f), fmaxf(w2, 0.f), fmaxf(w3, 0.f));
+              RowStager<T, NT>::put(stage2, pxq[q], j * 32 + M::ch(lane, q), fmaxf(w0, 0.f), fmaxf(w1, 0.f), fmaxf(w2, 0.f), fmaxf(w3, 0.f));
           }
       }
       // (the row's sum of squares is complete HERE: left to itself the compiler sank the 32 multiply-adds below the flush and kept
@@ -565,19 +632,19 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
       continue;
     }
     if (has_raw) {
-      if (!POOL || !(x & 1)) {
+      if (even) {
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            RowStager<float, NT>::put(stage, px, j * 32 + q * 8 + g * 4, v[j][q][0], v[j][q][1], v[j][q][2], v[j][q][3]);
-            if (lane_ok) ss += v[j][q][0] * v[j][q][0] + v[j][q][1] * v[j][q][1] + v[j][q][2] * v[j][q][2] + v[j][q][3] * v[j][q][3];
+            RowStager<float, NT>::put(stage, pxq[q], j * 32 + M::ch(lane, q), v[j][q][0], v[j][q][1], v[j][q][2], v[j][q][3]);
+            if (quad_ok(q)) ss = sumsq4(ss, v[j][q][0], v[j][q][1], v[j][q][2], v[j][q][3]);
           }
       }
       if (row_ok) RowStager<float, NT>::template flush<true>(stage, a.out_raw + pix0 * a.Cout + cb, NPX, nvalid, a.Cout, lane);
     }
     if (has_act) {
-      if (!POOL || !(x & 1)) {
+      if (even) {
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -585,9 +652,9 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
             float w0 = v[j][q][0], w1 = v[j][q][1], w2 = v[j][q][2], w3 = v[j][q][3];
             if (relu) { w0 = fmaxf(w0, 0.f); w1 = fmaxf(w1, 0.f); w2 = fmaxf(w2, 0.f); w3 = fmaxf(w3, 0.f); }
             // (with a mask or a fan-in the stored values are formed in the flush: the maximum is taken there)
-            if (Prec<T>::SPLIT && lane_ok && !((GEN || DG) && (a.mask_act || a.add_src)))
+            if (Prec<T>::SPLIT && quad_ok(q) && !((GEN || DG) && (a.mask_act || a.add_src)))
               mx = fmaxf(fmaxf(mx, fmaxf(fabsf(w0), fabsf(w1))), fmaxf(fabsf(w2), fabsf(w3)));
-            RowStager<T, NT>::put(stage, px, j * 32 + q * 8 + g * 4, w0, w1, w2, w3);
+            RowStager<T, NT>::put(stage, pxq[q], j * 32 + M::ch(lane, q), w0, w1, w2, w3);
           }
       }
       const size_t o = pix0 * a.Cout + cb;
@@ -612,13 +679,15 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[MT][NT], const ConvA
           float am[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float t0 = acc[i][j][q * 4 + e], u = acc[i + 1][j][q * 4 + e];
-            const float rown = u > t0 ? 1.f : 0.f;             // first maximum wins, like F.max_pool2d
+            const float t0 = M::get(acc[i][j], q, e), u = M::get(acc[i + 1][j], q, e);
+            // ties: the upper row wins inside a column, then the left column wins (so maxima at (0,1) and (1,0) give 2 where
+            // F.max_pool2d's row-major first maximum gives 1); a unique maximum is F.max_pool2d's
+            const float rown = u > t0 ? 1.f : 0.f;
             const float t = fmaxf(t0, u);
             const float t2 = lane_xor1(t), r2 = lane_xor1(rown);
             am[e] = t2 > t ? 2.f * r2 + 1.f : 2.f * rown;
           }
-          if (!(x & 1)) RowStager<unsigned char, NT>::put(stage, px, j * 32 + q * 8 + g * 4, am[0], am[1], am[2], am[3]);
+          if (!(lane & 1)) RowStager<unsigned char, NT>::put(stage, pxq[q], j * 32 + M::ch(lane, q), am[0], am[1], am[2], am[3]);
         }
       if (row_ok) RowStager<unsigned char, NT>::flush(stage, a.idx_out + pix0 * a.Cout + cb, NPX, nvalid, a.Cout, lane);
     }
@@ -882,8 +951,10 @@ __device__ __forceinline__ void stagger_priority() {
   if (slot & 1) __builtin_amdgcn_s_setprio(1);
 }
 
-template <typename T, int MT, int NT, int WD, int PF, typename Mid>
-__device__ __forceinline__ void stage_mma(f32x16 (&acc)[MT][NT], const char* cur, const FragOff& fo,
+// SHAPE_16x16x32: the same loop with the fragment index renamed -- pixel fragment (row i, pixel half p), weight fragment [c][j]
+// (cout half c): 2 NT MFMAs of half the length per pixel fragment, so PF reads ahead cover the same matrix time.
+template <typename T, int MT, int NT, int WD, int PF, int SHAPE = SHAPE_32x32x16, typename Mid>
+__device__ __forceinline__ void stage_mma(typename AccMap<SHAPE>::Tile (&acc)[MT][NT], const char* cur, const FragOff& fo,
                                           WeightRing<T, MT, NT, WD, PF>& ring, Mid&& mid) {
   constexpr int RS = WD + 1;
 #pragma unroll
@@ -919,6 +990,11 @@ __device__ __forceinline__ void stage_mma(f32x16 (&acc)[MT][NT], const char* cur
         for (int c = 0; c < (kg == 0 ? 2 : 1); ++c)
 #pragma unroll
           for (int j = 0; j < NT; ++j) mma16<T>(acc[i][j], ring.wb[tap % RS][c][j], ring.pf[slot]);
+      } else if constexpr (SHAPE == SHAPE_16x16x32) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) mma32<T>(acc[i][j].t[2 * kg + c], ring.wb[tap % RS][c][j], ring.pf[slot]);
       } else {
 #pragma unroll
         for (int j = 0; j < NT; ++j) mma16<T>(acc[i][j], ring.wb[tap % RS][kg][j], ring.pf[slot]);
@@ -936,9 +1012,12 @@ __device__ __forceinline__ void stage_mma(f32x16 (&acc)[MT][NT], const char* cur
 // the data-gradient convolutions of conv2 / conv7 / conv14).  A separate instantiation: its halo loader carries the argmax bytes
 // of a piece next to the piece and applies them when the piece is WRITTEN to LDS -- masking right behind the load put an
 // s_waitcnt vmcnt(0) after every single piece, six full memory round trips per stage in the middle of the MFMA stream.
-template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false>
+// SHAPE: the MFMA shape of the main loop (16-bit plain forward kernels only; launch_conv picks it per kernel class).
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16>
 __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs a) {
   static_assert(WM * WN == 4, "4 waves per block");
+  static_assert(SHAPE == SHAPE_32x32x16 || (sizeof(T) == 2 && !UNPOOL), "16x16x32: bf16 / f16 forward kernels only");
+  using M = AccMap<SHAPE>;
   constexpr int EPL = 16 / sizeof(T), KC = SB / sizeof(T);     // channels per stage: 32 (bf16) / 16 (fp32)
   constexpr int TH = WM * MT, HPIX = (TH + 2) * HWID;
   constexpr int NPIECE = (HPIX * 4 + 255) / 256;               // 16-B pieces per thread per stage ...
@@ -1154,20 +1233,20 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
   const int ntg0 = (blockIdx.y * WN + wn) * NT;     // first global 32-channel output tile of this wave
   // The accumulators start at the bias (16-bit types; it commutes with the max-pool, and the epilogues then have neither
   // the 8 x NT bias registers nor the adds); the 4-byte types add it in the epilogue (split mode: after its power-of-two descale).
-  f32x16 acc[MT][NT];
+  typename M::Tile acc[MT][NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (sizeof(T) == 2 && a.bias) b4 = *(const float4*)(a.bias + (ntg0 + j) * 32 + q * 8 + (lane >> 5) * 4);
+      if (sizeof(T) == 2 && a.bias) b4 = *(const float4*)(a.bias + (ntg0 + j) * 32 + M::ch(lane, q));
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
-        acc[i][j][q * 4 + 0] = b4.x; acc[i][j][q * 4 + 1] = b4.y; acc[i][j][q * 4 + 2] = b4.z; acc[i][j][q * 4 + 3] = b4.w;
+        M::set(acc[i][j], q, 0, b4.x); M::set(acc[i][j], q, 1, b4.y); M::set(acc[i][j], q, 2, b4.z); M::set(acc[i][j], q, 3, b4.w);
       }
     }
 
-  const FragOff fo = frag_offsets(lane, wm * MT);
+  const FragOff fo = frag_offsets<SHAPE>(lane, wm * MT);
   // packed weights: [ntile][stage][tap][kg(2)][lane] 16-B fragments
   // (the un-pooling loader carries a piece's argmax bytes next to it: at the three-workgroup register cap that costs the 32-channel
   //  wave tile one fragment of read-ahead -- with four, 7 registers spilled and 3 scratch accesses sat inside the MFMA stream)
@@ -1197,7 +1276,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
   for (int sg = 0; sg < nstage; ++sg) {
     const bool more = sg + 1 < nstage;
     char* nxt = lds + ((sg + 1) & 1) * BUF;
-    stage_mma<T, MT, NT, WD, PF>(acc, lds + (sg & 1) * BUF, fo, ring, [&](int tap) __attribute__((always_inline)) {
+    stage_mma<T, MT, NT, WD, PF, SHAPE>(acc, lds + (sg & 1) * BUF, fo, ring, [&](int tap) __attribute__((always_inline)) {
       if constexpr (DMA) {
         if (tap == HLA_CONV_DMA_TAP && more) dma_stage(sg + 1, (sg + 1) & 1);
       } else {
@@ -1244,19 +1323,19 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
         return;
       }
     }
-    if (mode == EPI_ACT) conv_epilogue<T, MT, NT, POOL, EPI_ACT, false, LDSB / 4>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+    if (mode == EPI_ACT) conv_epilogue<T, MT, NT, POOL, EPI_ACT, false, LDSB / 4, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
     // (16-bit raw copy, HLA_VGG_FEAT16: only the three feature layers ask for it -- conv14: pooled + bias; dec1.3 / dec2.3:
     // no bias -- and exactly those forms are compiled)
     else if (T16 && RAW_SPECIAL && a.raw16 && mode == EPI_ACT_RAW)
-      conv_epilogue<T, MT, NT, POOL, (T16 && RAW_SPECIAL) ? EPI_ACT_RAW : EPI_GENERIC, T16 && RAW_SPECIAL>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, (T16 && RAW_SPECIAL) ? EPI_ACT_RAW : EPI_GENERIC, T16 && RAW_SPECIAL, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
     else if (T16 && a.raw16 && mode == EPI_ACT_RAW_NOBIAS)
-      conv_epilogue<T, MT, NT, POOL, T16 ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, T16>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
-    else if (RAW_SPECIAL && mode == EPI_ACT_RAW) conv_epilogue<T, MT, NT, POOL, RAW_SPECIAL ? EPI_ACT_RAW : EPI_GENERIC>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
-    else if (mode == EPI_DGRAD)
-      conv_epilogue<T, MT, NT, POOL, EPI_DGRAD>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, T16 ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, T16, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+    else if (RAW_SPECIAL && mode == EPI_ACT_RAW) conv_epilogue<T, MT, NT, POOL, RAW_SPECIAL ? EPI_ACT_RAW : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+    else if (SHAPE == SHAPE_32x32x16 && mode == EPI_DGRAD)      // (a backward form: the backward's launches keep 32x32x16)
+      conv_epilogue<T, MT, NT, POOL, SHAPE == SHAPE_32x32x16 ? EPI_DGRAD : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
     else if ((RAW_SPECIAL || sizeof(T) == 2) && mode == EPI_ACT_RAW_NOBIAS)      // (4-byte storage: two passes, spills as well)
-      conv_epilogue<T, MT, NT, POOL, (RAW_SPECIAL || sizeof(T) == 2) ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
-    else conv_epilogue<T, MT, NT, POOL, EPI_GENERIC>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, (RAW_SPECIAL || sizeof(T) == 2) ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+    else conv_epilogue<T, MT, NT, POOL, EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
   }
   HLA_STAMP(5);
 }
@@ -1607,6 +1686,8 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Con
 //   generic: idx = ((((nt*nstage + sg)*9 + tap)*2 + kg)*64 + lane)*EPL + j
 //            cout = nt*32 + (lane&31), cin = sg*KC + kg*2*EPL + (lane>>5)*EPL + j      (KC = 64 B of channels)
 //   conv0:   idx = ((nt*NFRAG + f)*64 + lane)*EPL + j,  k = f*2*EPL + (lane>>5)*EPL + j  (k = cin*9+tap, <27)
+//   16x16x32 (shape == SHAPE_16x16x32, 16-bit types): the same index with kg read as the cout half c:
+//            cout = nt*32 + c*16 + (lane&15), cin = sg*KC + (lane>>4)*EPL + j
 //   Every layer's buffer is padded by two taps of fragments (the kernels prefetch up to 2 taps ahead).
 //   mode 2 (dgrad): the packed conv is the transpose: Cout' = Cin_orig, Cin' = Cout_orig, taps flipped:
 //            v = w_orig[cin'][cout'][8 - tap]  with w_orig laid out [Cout_orig = Cin'][Cin_orig = Cout'][9]
@@ -1614,7 +1695,8 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Con
 // for the 16-bit types, so the bias rides in the MFMA (its rounding error 2^-17 relative; for T = float lo is exactly 0)
 template <typename T>
 __device__ __forceinline__ void pack_weights_body(const float* __restrict__ w, T* __restrict__ out, int Cout, int Cin, int first,
-                                                  size_t e0, size_t stride, const float* __restrict__ b0 = nullptr) {
+                                                  size_t e0, size_t stride, const float* __restrict__ b0 = nullptr,
+                                                  int shape = SHAPE_32x32x16) {
   constexpr int EPL = 16 / sizeof(T), KC = SB / sizeof(T), NFRAG = 32 / (2 * EPL);
   const size_t total = first == 1 ? (size_t)(Cout / 32) * NFRAG * 64 * EPL : (size_t)Cout * Cin * 9;
   for (size_t e = e0; e < total; e += stride) {
@@ -1635,7 +1717,9 @@ __device__ __forceinline__ void pack_weights_body(const float* __restrict__ w, T
       const int nsg = Cin / KC;
       const int sg = r % nsg; r /= nsg;
       const int nt = (int)r;
-      const int cout = nt * 32 + (lane & 31), cin = sg * KC + kg * 2 * EPL + (lane >> 5) * EPL + j;
+      const bool s16 = sizeof(T) == 2 && shape == SHAPE_16x16x32;
+      const int cout = s16 ? nt * 32 + kg * 16 + (lane & 15) : nt * 32 + (lane & 31);
+      const int cin = s16 ? sg * KC + (lane >> 4) * EPL + j : sg * KC + kg * 2 * EPL + (lane >> 5) * EPL + j;
       v = first == 2 ? w[((size_t)cin * Cout + cout) * 9 + (8 - tap)] : w[((size_t)cout * Cin + cin) * 9 + tap];
     }
     out[e] = (T)v;
@@ -1650,13 +1734,15 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, T* __restrict__
 struct PackTable {
   const float* w[16]; size_t off[16];      // source weights, byte offset of the packed layer
   int cout[16], cin[16], first[16];
+  int shape[16];                           // MFMA shape of the kernel class that reads the layer (16-bit types; 0 = 32x32x16)
   const float* b0;                         // conv0's bias (rides in its padded k slots, see pack_weights_body), or null
 };
 template <typename T>
 __global__ void pack_weights_multi_kernel(PackTable tb, char* __restrict__ packed) {
   const int l = blockIdx.y;
   pack_weights_body<T>(tb.w[l], (T*)(packed + tb.off[l]), tb.cout[l], tb.cin[l], tb.first[l],
-                       (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, tb.first[l] == 1 ? tb.b0 : nullptr);
+                       (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, tb.first[l] == 1 ? tb.b0 : nullptr,
+                       tb.shape[l]);
 }
 
 // Split mode, every layer of a network in ONE launch each (blockIdx.y = table row), like pack_weights_multi_kernel: a training
@@ -1859,6 +1945,15 @@ static __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x
 // (ConvArgs::unpool_idx): only then are the UNPOOL instantiations compiled into the translation unit.
 // Returns false (with the library's error string set, nothing launched) for a combination no kernel was compiled for.
 constexpr int CONV_SMALL_GRID = 320;      // workgroups: below this a forward launch takes 4-row tiles
+// MFMA shape of the 16-bit FORWARD launches per kernel class, decided by same-box A/B against 32x32x16 (EXPERIMENTS.md).  The
+// 8-row and the 4-row tile of a class share the entry (the small-grid path is bit-identical to the 8-row one), the packer lays a
+// layer's weights out for its class (vgg_pack_all), and the backward's launches (BWD) always take 32x32x16 with their own packing.
+enum { CONV_CLASS_NT2 = 0,         // Cout >= 128, plain: conv5, conv10, conv12, dec1.1, dec1.3
+       CONV_CLASS_NT2_POOL = 1,    // Cout >= 128, pooled: conv7, conv14
+       CONV_CLASS_NT1 = 2 };       // Cout == 64: dec2.1, dec2.3, dec3.x
+constexpr int kConvClassShape[3] = {SHAPE_16x16x32, SHAPE_16x16x32, SHAPE_32x32x16};
+constexpr int conv_class(int cout, bool pool) { return cout >= 128 ? (pool ? CONV_CLASS_NT2_POOL : CONV_CLASS_NT2) : CONV_CLASS_NT1; }
+template <typename T, bool BWD> constexpr int conv_shape(int cls) { return (sizeof(T) == 2 && !BWD) ? kConvClassShape[cls] : SHAPE_32x32x16; }
 template <typename T, bool BWD = false>
 static bool launch_conv(hipStream_t st, ConvArgs a, bool pool) {
   if (a.unpool_idx && !(BWD && !pool)) {      // (cannot happen from this library's callers; the plain kernels ignore the field)
@@ -1887,17 +1982,19 @@ static bool launch_conv(hipStream_t st, ConvArgs a, bool pool) {
   // is then a chain of such launches) takes 4-row tiles (MT = 2): twice the workgroups, each with half the work -- every output
   // element's sum is formed in the same order, so the result is bit-identical.  Not for the three feature layers: their
   // sum-of-squares partials are per tile, and a sample's L2 norm must not depend on its batch mates to the last bit.
+  constexpr int S_NT2 = conv_shape<T, BWD>(CONV_CLASS_NT2), S_NT2P = conv_shape<T, BWD>(CONV_CLASS_NT2_POOL),
+                S_NT1 = conv_shape<T, BWD>(CONV_CLASS_NT1);
   if constexpr (!BWD) {
     const int gy = big ? a.Cout / 128 : 1;
     if (!a.dyn && !a.sumsq && !a.unpool_idx && a.tiles_x * a.tiles_y * a.B * gy < CONV_SMALL_GRID) {
       a.tiles_y = (a.H - a.row_begin + 3) / 4;
       const dim3 g4(a.tiles_x * a.tiles_y * a.B, gy);
       if (big) {
-        if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 2, 2, true, 1>), g4, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 2, 2, false, 1>), g4, dim3(256), 0, st, a);
+        if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 2, 2, true, 1, false, S_NT2P>), g4, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 2, 2, false, 1, false, S_NT2>), g4, dim3(256), 0, st, a);
       } else {
-        if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 1, 2, 2, true, 2>), g4, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 1, 2, 2, false, 2>), g4, dim3(256), 0, st, a);
+        if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 1, 2, 2, true, 2, false, S_NT1>), g4, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 1, 2, 2, false, 2, false, S_NT1>), g4, dim3(256), 0, st, a);
       }
       hla_prof_end(st);
       return true;
@@ -1908,13 +2005,13 @@ static bool launch_conv(hipStream_t st, ConvArgs a, bool pool) {
   if (big) {
     // (weights two taps ahead for this tile as well: spills with the register-staged loader, -1 %; with the LDS-DMA loader it
     //  fits -- 232 registers -- and measures the same: 4876 / 4871 against 4870 / 4841 pairs/s)
-    if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, true, 1>), grid, dim3(256), 0, st, a);
-    else if (BWD && a.unpool_idx) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, false, 1, BWD>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, false, 1>), grid, dim3(256), 0, st, a);
+    if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, true, 1, false, S_NT2P>), grid, dim3(256), 0, st, a);
+    else if (BWD && a.unpool_idx) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, false, 1, BWD, S_NT2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, false, 1, false, S_NT2>), grid, dim3(256), 0, st, a);
   } else {
-    if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, true, 2>), grid, dim3(256), 0, st, a);
-    else if (BWD && a.unpool_idx) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, false, 2, BWD>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, false, 2>), grid, dim3(256), 0, st, a);
+    if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, true, 2, false, S_NT1>), grid, dim3(256), 0, st, a);
+    else if (BWD && a.unpool_idx) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, false, 2, BWD, S_NT1>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, false, 2, false, S_NT1>), grid, dim3(256), 0, st, a);
   }
   hla_prof_end(st);
   return true;

@@ -18,6 +18,8 @@ void vgg_pack_all(const hla_vgg_params* prm, char* packed, int dtype, hipStream_
       if (l >= kPackedLayers && !prm->w[l]) continue;      // conv_dec3.* only when the caller supplies its padded weights
       tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cout; tb.cin[n] = kLayers[l].cin;
       tb.first[n] = l == 0 ? 1 : 0;
+      // the layout of the MFMA shape the layer's forward kernel class runs on; conv0 / conv2 (conv02_kernel) keep 32x32x16
+      tb.shape[n] = l >= 2 ? conv_shape<T, false>(conv_class(kLayers[l].cout, kLayers[l].pool != 0)) : SHAPE_32x32x16;
       ++n;
     }
     hla_prof_begin(K_PACK, 0, (double)packed_offset(kAllLayers, dtype) * (1.0 + 4.0 / sizeof(T)), st);
@@ -100,6 +102,12 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   auto conv = [&](int l, const void* s1, int C1, int H_, int W_h, void* act, int relu, bool pool, const void* s2 = nullptr,
                   int C2 = 0, int up1 = 0, void* raw = nullptr, double* ss = nullptr, unsigned char* idx = nullptr,
                   int row_begin = 0, int norm_level = -1) {
+    // the packer laid the layer's weights out for the kernel class kLayers[l].pool puts it in: the launch must pick the same one
+    if (pool != (kLayers[l].pool != 0)) {
+      hla_set_error("vgg_forward: layer %d launched with pool = %d, the layer table says %d", l, (int)pool, kLayers[l].pool);
+      launch_ok = false;
+      return;
+    }
     ConvArgs a{};
     a.raw16 = (raw && (flags & HLA_VGG_FEAT16)) ? 1 : 0;
     a.row_begin = row_begin < 0 ? 0 : row_begin;

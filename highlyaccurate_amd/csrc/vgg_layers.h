@@ -2,10 +2,10 @@
 #pragma once
 #include "common.h"
 
-struct LayerDef { int cin, cout, has_bias; };
+struct LayerDef { int cin, cout, has_bias, pool; };      // pool: the layer's kernel ends in the 2x2 max-pool
 // state-dict order (VGG.py:23-56): conv0,2,5,7,10,12,14, dec1.1, dec1.3, dec2.1, dec2.3, dec3.1, dec3.3
 static const LayerDef kLayers[13] = {
-    {3, 64, 1}, {64, 64, 1}, {64, 128, 1}, {128, 128, 1}, {128, 256, 1}, {256, 256, 1}, {256, 256, 1},
+    {3, 64, 1, 0}, {64, 64, 1, 1}, {64, 128, 1, 0}, {128, 128, 1, 1}, {128, 256, 1, 0}, {256, 256, 1, 0}, {256, 256, 1, 1},
     {384, 128, 0}, {128, 128, 0}, {192, 64, 0}, {64, 64, 0},
     // conv_dec3.1 (128 -> 32) and conv_dec3.3 (32 -> 16) are run on ZERO-PADDED weights (the host pads them to 64 output /
     // 64 input channels), so every kernel keeps its 64-channel granularity; the padded channels are exactly zero
