@@ -159,6 +159,52 @@ def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True,
     return feats, confs, inv_norm
 
 
+@_lib.on_device(lambda modules, xs, *a, **k: xs[0])
+def vgg_forward_pair_nhwc(modules, xs, first_row8=(0, 0), feat16: bool = False):
+    """The inference forward of two level-3 extractors on batches of one size (``hla_vgg_forward_pair``): what
+    ``vgg_forward_nhwc(m, x, want_conf=False, defer_norm=True, first_row8=f, feat16=feat16)`` returns for each of them, bit for
+    bit, with every convolution layer of the two networks run as one launch where the library can pair them (include/hla.h).
+    Returns ``((feats0, inv_norm0), (feats1, inv_norm1), paired)``; ``paired`` tells whether the paired launches were issued."""
+    lib = _lib.load()
+    if len(modules) != 2 or len(xs) != 2:
+        raise ValueError('vgg_forward_pair_nhwc takes two modules and two images')
+    dt = _dtype_code(modules[0].precision)
+    if _dtype_code(modules[1].precision) != dt or any(m.level == 4 or getattr(m, 'folded', False) for m in modules):
+        raise ValueError('vgg_forward_pair_nhwc: two unfolded extractors of one precision, level 3')
+    if feat16 and dt not in (_lib.HLA_BF16, _lib.HLA_F16):
+        raise ValueError("feat16 needs precision 'bf16' / 'fp16'")
+    if xs[0].dim() != 4 or xs[1].dim() != 4 or xs[0].shape[1] != 3 or xs[1].shape[1] != 3 or xs[0].shape[0] != xs[1].shape[0]:
+        raise ValueError(f'expected two [B,3,H,W] images with one B, got {tuple(xs[0].shape)} and {tuple(xs[1].shape)}')
+    br = (_lib.VggBranch * 2)()
+    keep, out = [], []
+    for k, (module, x) in enumerate(zip(modules, xs)):
+        _lib.require_gpu(x, 'VGGUnet input')
+        x, x_plane = _image_window(x)
+        B, _, H, W = x.shape
+        _lib.same_device(('input', x), ('parameters', module.conv0.weight), ('first input', xs[0]))
+        prm, kp, versions = _param_table(module)
+        packed = _packed_weights(module, prm, versions, dt, x.device)
+        feats = [torch.empty(B, H >> (3 - l), W >> (3 - l), _CH[l], device=x.device, dtype=torch.float16 if feat16 else torch.float32)
+                 for l in range(3)]
+        inv_norm = torch.empty(3, B, device=x.device, dtype=torch.float64)
+        nbytes = lib.hla_vgg_workspace_bytes(B, H, W, 3, dt)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        b = br[k]
+        b.x, b.x_plane, b.params, b.packed_weights = x.data_ptr(), x_plane, C.pointer(prm), packed.data_ptr()
+        for l in range(3):
+            b.feat[l] = feats[l].data_ptr()
+        b.inv_norm, b.workspace, b.workspace_bytes = inv_norm.data_ptr(), ws.data_ptr(), nbytes
+        b.H, b.W, b.first_row8 = H, W, int(first_row8[k])
+        keep += [x, prm, kp, packed, ws]
+        out.append((feats, inv_norm))
+    flags = _lib.HLA_VGG_DEFER_NORM | (_lib.HLA_VGG_FEAT16 if feat16 else 0)
+    paired = C.c_int(0)
+    rc = lib.hla_vgg_forward_pair(br, xs[0].shape[0], 3, dt, flags, C.byref(paired), _lib.stream_ptr())
+    _lib.check(rc, 'hla_vgg_forward_pair')
+    # (the workspaces are only used by work already enqueued on this stream: see vgg_forward_nhwc)
+    return out[0], out[1], bool(paired.value)
+
+
 @_lib.on_device(lambda module, ctx, *a, **k: ctx['x'])
 def vgg_backward_nhwc(module: 'VGGUnet', ctx: dict, d_feats, confs=None, d_confs=None, scale_invariant: bool = False,
                       first_row8: int = 0, flat: bool = False, dense: bool = False, stats: dict = None,

@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class HlaError(RuntimeError):
@@ -46,6 +46,12 @@ class S2GConfig(C.Structure):
                 ('damping', C.c_double * 3), ('keep', C.c_void_p), ('keep_stride', C.c_size_t),
                 ('optimizer', C.c_int), ('beta1', C.c_double), ('beta2', C.c_double), ('count_in_view', C.c_int),
                 ('grd_grad_overwrite', C.c_int), ('deterministic', C.c_int), ('proj', C.c_int)]
+
+
+class VggBranch(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('x_plane', C.c_size_t), ('params', C.POINTER(VggParams)), ('packed_weights', C.c_void_p),
+                ('feat', C.c_void_p * 4), ('conf', C.c_void_p * 4), ('inv_norm', C.c_void_p), ('workspace', C.c_void_p),
+                ('workspace_bytes', C.c_size_t), ('H', C.c_int), ('W', C.c_int), ('first_row8', C.c_int)]
 
 
 class FillRegion(C.Structure):
@@ -88,7 +94,8 @@ def _check_binary(lib: C.CDLL, path: str) -> None:
     except AttributeError:
         raise HlaError(f'{path}: no hla_sizeof_struct export; rebuild it') from None
     fn.restype, fn.argtypes = C.c_size_t, [C.c_int]
-    for sid, cls in enumerate((VggParams, VggGrads, S2GLevel, S2GConfig, S2GLevelGrad, ProfRecord, PoseLossArgs, FillRegion)):
+    for sid, cls in enumerate((VggParams, VggGrads, S2GLevel, S2GConfig, S2GLevelGrad, ProfRecord, PoseLossArgs, FillRegion,
+                                VggBranch)):
         if fn(sid) != C.sizeof(cls):
             raise HlaError(f'{path}: sizeof({cls.__name__}) is {fn(sid)} in the library and {C.sizeof(cls)} in the binding')
 
@@ -129,6 +136,8 @@ def load() -> C.CDLL:
     lib.hla_vgg_forward.restype = i
     lib.hla_vgg_forward.argtypes = [vp, sz, C.POINTER(VggParams), vp, C.POINTER(vp), C.POINTER(vp), vp, vp, sz,
                                     i, i, i, i, i, i, i, vp]
+    lib.hla_vgg_forward_pair.restype = i
+    lib.hla_vgg_forward_pair.argtypes = [C.POINTER(VggBranch), i, i, i, i, C.POINTER(i), vp]
     lib.hla_vgg_packed_weight_bytes.restype = sz
     lib.hla_vgg_packed_weight_bytes.argtypes = [i]
     lib.hla_vgg_pack_weights.restype = i

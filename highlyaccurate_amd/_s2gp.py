@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, utils
-from .VGG import VGGUnet, vgg_forward_nhwc, vgg_backward_nhwc
+from .VGG import VGGUnet, vgg_forward_nhwc, vgg_forward_pair_nhwc, vgg_backward_nhwc
 
 KITTI_K = [[582.9802, 0.0, 496.2420], [0.0, 482.7076, 125.0034], [0.0, 0.0, 1.0]]      # models_kitti.py:657-660
 FORD_K_FL = [945.391406, 0.0, 855.502825, 0.0, 945.668274, 566.372868, 0.0, 0.0, 1.0]   # models_ford.py:116
@@ -202,6 +202,8 @@ class S2GPBase(nn.Module):
     #                      from a stored map of conv2's data gradient instead of inside that kernel's epilogue (..._WGRAD0_UNFUSED)
     #   strict_errors      0; 1: reproduce jacobian.py:172's AssertionError (costs a host sync per forward)     DESIGN.md 1
     #   small_batch_two_streams  4: inference batches up to this size run the two extractors on two streams        DESIGN.md 5
+    #   pair_extractor_launches  1: inference batches above small_batch_two_streams run every conv layer of the two extractors as
+    #                      ONE launch of two segments (hla_vgg_forward_pair); 0: the two forwards back to back.  Same bits    DESIGN.md 3.1
     #   deterministic_backward  0; 1: lm_bwd_accum accumulates d(loss)/d(sat map) in a fixed order instead of with fp32 atomics:
     #                      the same batch twice gives bitwise equal parameter gradients
     def __init__(self, args):
@@ -498,6 +500,24 @@ class S2GPBase(nn.Module):
         # ground branch's (B <= args.small_batch_two_streams, default 4: B = 1 0.700 -> 0.615 ms, B = 4 1.195 -> 1.122; at B = 32, where both are dense, the same split measured
         # 2 % slower: DESIGN 3.1).
         small = sat_map.shape[0] <= int(getattr(self.args, 'small_batch_two_streams', 4))
+        # (only LM_update renormalises the ground features; SGD / ADAM see the whole-map L2_norm scale, so they need every row;
+        #  proj='polar' reads every row of every map, so there the flag is inert)
+        dead_ok = (not return_confs and self.level == 3 and getattr(self.args, 'Optimizer', 'LM') == 'LM'
+                   and bool(getattr(self.args, 'ground_crop', 1)) and not self.polar)
+        skip = dead_ground_rows(grd_img.shape[-2]) if dead_ok else 0
+        # a row window, passed as it lies in memory (hla_vgg_forward's x_plane): no copy
+        grd_in = grd_img[:, :, skip:, :] if skip else grd_img
+        # ... and inside the extractor every layer only computes the rows the LM loop's rows depend on
+        f8 = ((grd_img.shape[-2] // 8) // 2 - skip // 8) if dead_ok else 0
+        f8 = f8 if f8 >= 4 else 0
+        # A batch that fills the chip: the two extractors are the same ten launches on two images, and each of them runs for both
+        # as ONE launch (args.pair_extractor_launches, default 1; the library falls back to the two forwards where it cannot pair)
+        if (not small and not want_conf and self.level != 4 and bool(getattr(self.args, 'pair_extractor_launches', 1))
+                and self.GrdFeatureNet.precision == self.SatFeatureNet.precision):
+            (sat_feats, sat_inv), (grd_feats, grd_inv), _ = vgg_forward_pair_nhwc(
+                (self.SatFeatureNet, self.GrdFeatureNet), (sat_map, grd_in), first_row8=(0, f8), feat16=f16)
+            L = self._levels
+            return L(sat_feats), L(sat_inv), L(grd_feats), L([None] * 3), L(grd_inv)
         if small:
             cur = torch.cuda.current_stream()
             side = _side_stream(sat_map.device)
@@ -507,17 +527,6 @@ class S2GPBase(nn.Module):
             sat_map.record_stream(side)
         else:
             sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16)
-        grd_in = grd_img
-        # (only LM_update renormalises the ground features; SGD / ADAM see the whole-map L2_norm scale, so they need every row;
-        #  proj='polar' reads every row of every map, so there the flag is inert)
-        dead_ok = (not return_confs and self.level == 3 and getattr(self.args, 'Optimizer', 'LM') == 'LM'
-                   and bool(getattr(self.args, 'ground_crop', 1)) and not self.polar)
-        skip = dead_ground_rows(grd_img.shape[-2]) if dead_ok else 0
-        if skip:
-            grd_in = grd_img[:, :, skip:, :]         # a row window, passed as it lies in memory (hla_vgg_forward's x_plane): no copy
-        # ... and inside the extractor every layer only computes the rows the LM loop's rows depend on
-        f8 = ((grd_img.shape[-2] // 8) // 2 - skip // 8) if dead_ok else 0
-        f8 = f8 if f8 >= 4 else 0
         grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_in, want_conf=want_conf, defer_norm=True,
                                                          first_row8=f8, feat16=f16)
         if small:

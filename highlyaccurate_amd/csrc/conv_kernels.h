@@ -469,7 +469,8 @@ template <typename T, int MT, int NT, bool POOL, int EPI = EPI_GENERIC, bool R16
 __device__ __forceinline__ void conv_epilogue(typename AccMap<SHAPE>::Tile (&acc)[MT][NT], const ConvArgs& a, int b, int yrow0, int x0,
                                               int cb, float* red, char* stage, float dsc = 1.f,
                                               PixBox addb = PixBox{0, 1 << 30, 0, 1 << 30},
-                                              const float4* prebias = nullptr) {      // [NT * 4] bias values the caller already holds
+                                              const float4* prebias = nullptr,        // [NT * 4] bias values the caller already holds
+                                              int blk = 0, int nblk = 1) {            // the workgroup's id / count along x in its launch segment (sumsq slot)
   using RawT = std::conditional_t<R16, f16, float>;      // 16-bit raw maps are fp16 also in bf16 mode: 11 significand bits for the LM loop
   constexpr bool GEN = EPI == EPI_GENERIC, RAW = EPI == EPI_ACT_RAW || EPI == EPI_ACT_RAW_NOBIAS, DG = EPI == EPI_DGRAD;
   // 16-bit types: the kernels START their accumulators at the bias (conv3x3_kernel / conv02_kernel), nothing to add here.
@@ -701,7 +702,7 @@ __device__ __forceinline__ void conv_epilogue(typename AccMap<SHAPE>::Tile (&acc
     if (tid == 0) {
       if (has_sumsq) {
         const int np = a.tiles_x * a.tiles_y * gridDim.y;
-        const int tile = (xcd_contiguous(blockIdx.x, gridDim.x) % (a.tiles_x * a.tiles_y)) * gridDim.y + blockIdx.y;
+        const int tile = (xcd_contiguous(blk, nblk) % (a.tiles_x * a.tiles_y)) * gridDim.y + blockIdx.y;
         a.sumsq[(size_t)b * np + tile] = ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]);
       }
       if (want_max) {    // non-negative floats order like their bit patterns; the plain read only filters (a stale value costs one
@@ -1013,8 +1014,11 @@ __device__ __forceinline__ void stage_mma(typename AccMap<SHAPE>::Tile (&acc)[MT
 // of a piece next to the piece and applies them when the piece is WRITTEN to LDS -- masking right behind the load put an
 // s_waitcnt vmcnt(0) after every single piece, six full memory round trips per stage in the middle of the MFMA stream.
 // SHAPE: the MFMA shape of the main loop (16-bit plain forward kernels only; launch_conv picks it per kernel class).
+// The body takes the workgroup's id and the workgroup count along x as arguments: a plain launch passes blockIdx.x / gridDim.x
+// (conv3x3_kernel), a two-segment launch the ids local to the workgroup's segment (conv3x3_pair_kernel below).  They are all the
+// kernel knows of its place in the grid: the XCD-contiguous map, the (b, ty, tx) decode and the sum-of-squares slot use them.
 template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16>
-__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs a) {
+__device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, const int nblk) {
   static_assert(WM * WN == 4, "4 waves per block");
   static_assert(SHAPE == SHAPE_32x32x16 || (sizeof(T) == 2 && !UNPOOL), "16x16x32: bf16 / f16 forward kernels only");
   using M = AccMap<SHAPE>;
@@ -1054,8 +1058,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
     // 160 -> 145 us for half the tiles.)
     const ConvDyn& d = *(const ConvDyn*)(a.dyn + a.dyn_desc);
     const int nl = d.n_live, nlive = nl * a.B;
-    if ((int)blockIdx.x >= nlive) return;
-    int bid = xcd_contiguous(blockIdx.x, nlive);
+    if (blk >= nlive) return;
+    int bid = xcd_contiguous(blk, nlive);
     b = bid / nl;
     const int e = a.dyn[d.list + bid % nl];
     ty = e >> 16; tx = e & 0xffff;
@@ -1067,7 +1071,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
       sb.lo2 = a.dyn[d.src_bands + 2 * b2] << sh; sb.hi2 = min(a.dyn[d.src_bands + 2 * b2 + 1] << sh, a.W);
     }
   } else {
-    int bid = xcd_contiguous(blockIdx.x, gridDim.x);
+    int bid = xcd_contiguous(blk, nblk);
     tx = bid % a.tiles_x; bid /= a.tiles_x;
     ty = bid % a.tiles_y;
     b = bid / a.tiles_y;
@@ -1323,21 +1327,71 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
         return;
       }
     }
-    if (mode == EPI_ACT) conv_epilogue<T, MT, NT, POOL, EPI_ACT, false, LDSB / 4, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+    if (mode == EPI_ACT) conv_epilogue<T, MT, NT, POOL, EPI_ACT, false, LDSB / 4, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
     // (16-bit raw copy, HLA_VGG_FEAT16: only the three feature layers ask for it -- conv14: pooled + bias; dec1.3 / dec2.3:
     // no bias -- and exactly those forms are compiled)
     else if (T16 && RAW_SPECIAL && a.raw16 && mode == EPI_ACT_RAW)
-      conv_epilogue<T, MT, NT, POOL, (T16 && RAW_SPECIAL) ? EPI_ACT_RAW : EPI_GENERIC, T16 && RAW_SPECIAL, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, (T16 && RAW_SPECIAL) ? EPI_ACT_RAW : EPI_GENERIC, T16 && RAW_SPECIAL, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
     else if (T16 && a.raw16 && mode == EPI_ACT_RAW_NOBIAS)
-      conv_epilogue<T, MT, NT, POOL, T16 ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, T16, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
-    else if (RAW_SPECIAL && mode == EPI_ACT_RAW) conv_epilogue<T, MT, NT, POOL, RAW_SPECIAL ? EPI_ACT_RAW : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, T16 ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, T16, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
+    else if (RAW_SPECIAL && mode == EPI_ACT_RAW) conv_epilogue<T, MT, NT, POOL, RAW_SPECIAL ? EPI_ACT_RAW : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
     else if (SHAPE == SHAPE_32x32x16 && mode == EPI_DGRAD)      // (a backward form: the backward's launches keep 32x32x16)
-      conv_epilogue<T, MT, NT, POOL, SHAPE == SHAPE_32x32x16 ? EPI_DGRAD : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, SHAPE == SHAPE_32x32x16 ? EPI_DGRAD : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
     else if ((RAW_SPECIAL || sizeof(T) == 2) && mode == EPI_ACT_RAW_NOBIAS)      // (4-byte storage: two passes, spills as well)
-      conv_epilogue<T, MT, NT, POOL, (RAW_SPECIAL || sizeof(T) == 2) ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
-    else conv_epilogue<T, MT, NT, POOL, EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb);
+      conv_epilogue<T, MT, NT, POOL, (RAW_SPECIAL || sizeof(T) == 2) ? EPI_ACT_RAW_NOBIAS : EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
+    else conv_epilogue<T, MT, NT, POOL, EPI_GENERIC, false, 0, SHAPE>(acc, a, b, y0 + wm * MT, x0, ntg0 * 32, red, stager, dsc, addb, nullptr, blk, nblk);
   }
   HLA_STAMP(5);
+}
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16>
+__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs a) {
+  conv3x3_body<T, MT, NT, WM, WN, POOL, WD, UNPOOL, SHAPE>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// ---- two-segment launches (inference, vgg.hip: the same layer of the two extractors in ONE grid).  The kernarg holds two
+// argument blocks and the first segment's workgroup count n0; workgroups [0, n0) along x are segment 0, the rest segment 1, and
+// blockIdx.y (the cout block) is shared.  A workgroup's segment is uniform, so its argument block is fetched with scalar loads
+// from ONE selected kernarg address: selecting between the two blocks of a by-value struct field by field keeps both live, and
+// indexing the struct dynamically makes the compiler copy it to the stack.
+template <typename A> struct PairArgs { A s[2]; int n0; };
+template <typename A>
+__device__ __forceinline__ A pair_segment_args(bool second) {
+  static_assert(sizeof(A) % 4 == 0 && offsetof(PairArgs<A>, s) == 0, "the argument blocks lead the kernarg segment");
+  typedef const __attribute__((address_space(4))) unsigned* kptr_t;
+  const kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr() + (second ? sizeof(A) / 4 : 0);
+  unsigned w[sizeof(A) / 4];
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(A) / 4; ++i) w[i] = kp[i];
+  A a;
+  __builtin_memcpy(&a, w, sizeof(A));
+  return a;
+}
+// A pointer fetched that way is a generic one to the compiler (only pointers that are kernel arguments by themselves are known to
+// be global): it would address memory with flat_load / flat_store, which count on the LDS counter as well and may not be mixed
+// into the hand-counted vmcnt waits of the stage loop.  The round trip through the global address space says what they are.
+template <typename P> __device__ __forceinline__ P* pair_global(P* p) {
+  return (P*)(__attribute__((address_space(1))) P*)(unsigned long long)p;      // (through the integer: a plain cast pair is folded away)
+}
+// Two-segment launches are inference launches: the training / backward fields are constants here, so none of their paths (the
+// device-side tile lists among them, whose loads would make the tile coordinates vector values) is kept in the pair kernels.
+__device__ __forceinline__ void pair_inference_args(ConvArgs& a) {
+  a.src1 = pair_global(a.src1); a.src2 = pair_global(a.src2); a.wpk = pair_global(a.wpk); a.bias = pair_global(a.bias);
+  a.out_act = pair_global(a.out_act); a.out_raw = pair_global(a.out_raw); a.sumsq = pair_global(a.sumsq);
+  a.amax1 = pair_global(a.amax1); a.amax2 = pair_global(a.amax2); a.amax_out = pair_global(a.amax_out); a.wscale = pair_global(a.wscale);
+  a.dyn = nullptr; a.dyn_desc = 0; a.src_row_lo = 0; a.add_row_lo = 0; a.unpool_idx = nullptr; a.mask_act = nullptr; a.add_src = nullptr;
+  a.idx_out = nullptr; a.pool_sum = 0; a.wg0_x = nullptr; a.wg0_x_plane = 0; a.wg0_part = nullptr;
+#if HLA_CONV_STAMPS
+  a.stamps = nullptr;
+#endif
+}
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, int SHAPE>
+__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_pair_kernel(PairArgs<ConvArgs> p) {
+  const int n0 = p.n0;
+  const bool second = (int)blockIdx.x >= n0;      // workgroup-uniform
+  ConvArgs a = pair_segment_args<ConvArgs>(second);
+  pair_inference_args(a);
+  conv3x3_body<T, MT, NT, WM, WN, POOL, WD, false, SHAPE>(a, second ? (int)blockIdx.x - n0 : (int)blockIdx.x,
+                                                          second ? (int)gridDim.x - n0 : n0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1374,10 +1428,9 @@ template <typename T> constexpr int conv02_lds_bytes() {
   return (64 * (int)sizeof(T) / SB) / conv02_rounds<T>() * (10 * HWID * PSTR) + 3 * 12 * 36 * 4;
 }
 
+// (the body takes the workgroup's id inside its launch segment, like conv3x3_body)
 template <typename T, int WD>
-// (three workgroups per CU, except in split mode: there the kernel is matrix-bound already -- three MFMAs per product -- and
-// the 168-register cap costs it 31 spills: 1430 us per launch either way, same-box A/B)
-__global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Conv02Args a0) {
+__device__ __forceinline__ void conv02_body(const Conv02Args& a0, const int blk) {
   constexpr bool SPLIT = Prec<T>::SPLIT;
   // 16-bit types: conv0's bias and the zeroing of halo pixels outside the image ride in the MFMA (k slots 27 / 28 = bias hi / lo
   // against an input of 1.0; an all-zero input column for a pixel outside) instead of 64 adds + 64 selects per 32 pixels and lane
@@ -1398,7 +1451,7 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Con
   HLA_STAMP_HWID();
 
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), wm = wv / WN, wn = wv % WN;
-  int bid = blockIdx.x;                    // (the XCD-contiguous order measured 2-3 % slower for this kernel)
+  int bid = blk;                           // (the XCD-contiguous order measured 2-3 % slower for this kernel)
   const int tx = bid % a0.tiles_x; bid /= a0.tiles_x;
   const int ty = bid % a0.tiles_y;
   const int b = bid / a0.tiles_y;
@@ -1680,6 +1733,25 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Con
   { struct { unsigned long long* stamps; } a = {a0.stamps}; HLA_STAMP(5); }
 #endif
 }
+// (three workgroups per CU, except in split mode: there the kernel is matrix-bound already -- three MFMAs per product -- and
+// the 168-register cap costs it 31 spills: 1430 us per launch either way, same-box A/B)
+template <typename T, int WD>
+__global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Conv02Args a0) {
+  conv02_body<T, WD>(a0, (int)blockIdx.x);
+}
+template <typename T, int WD>
+__global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_pair_kernel(PairArgs<Conv02Args> p) {
+  const int n0 = p.n0;
+  const bool second = (int)blockIdx.x >= n0;      // workgroup-uniform
+  Conv02Args a0 = pair_segment_args<Conv02Args>(second);
+  a0.x = pair_global(a0.x); a0.w0 = pair_global(a0.w0); a0.b0 = pair_global(a0.b0); a0.w2 = pair_global(a0.w2); a0.b2 = pair_global(a0.b2);
+  a0.out_act = pair_global(a0.out_act); a0.wtail = pair_global(a0.wtail); a0.amax_out = pair_global(a0.amax_out);
+  a0.a0_out = nullptr; a0.idx_out = nullptr; a0.a2_out = nullptr; a0.amax_a2_out = nullptr; a0.amax_a0_out = nullptr;      // (inference, level 3)
+#if HLA_CONV_STAMPS
+  a0.stamps = nullptr;
+#endif
+  conv02_body<T, WD>(a0, second ? (int)blockIdx.x - n0 : (int)blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------
 // weight packing: OIHW fp32 -> MFMA fragment order, T elements.
@@ -1910,8 +1982,9 @@ static __global__ __launch_bounds__(256) void inv_norm_kernel(const double* __re
   __syncthreads();
   if (threadIdx.x == 0) inv[b] = 1.0 / fmax(sqrt((sh[0] + sh[1]) + (sh[2] + sh[3])), 1e-12);
 }
-// all levels of a network in one launch: blockIdx.y = level
-struct InvNormArgs { const double* ss[4]; int np[4]; double* inv; int B; };
+// all levels of a network (or of two) in one launch: blockIdx.y = row
+// (rows = levels x networks: a paired forward normalises both networks' maps with one launch; inv[row] = that row's [B] outputs)
+struct InvNormArgs { const double* ss[8]; int np[8]; double* inv[8]; };
 static __global__ __launch_bounds__(256) void inv_norm_multi_kernel(InvNormArgs a) {
   __shared__ double sh[4];
   const int b = blockIdx.x, l = blockIdx.y, np = a.np[l];
@@ -1921,7 +1994,7 @@ static __global__ __launch_bounds__(256) void inv_norm_multi_kernel(InvNormArgs 
   s = wave_sum_f64(s);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) a.inv[(size_t)l * a.B + b] = 1.0 / fmax(sqrt((sh[0] + sh[1]) + (sh[2] + sh[3])), 1e-12);
+  if (threadIdx.x == 0) a.inv[l][b] = 1.0 / fmax(sqrt((sh[0] + sh[1]) + (sh[2] + sh[3])), 1e-12);
 }
 // scale_kernel: in-place x *= inv[b] (fp64 multiply, one rounding)
 static __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, const double* __restrict__ inv, size_t per_sample,
@@ -1954,65 +2027,107 @@ enum { CONV_CLASS_NT2 = 0,         // Cout >= 128, plain: conv5, conv10, conv12,
 constexpr int kConvClassShape[3] = {SHAPE_16x16x32, SHAPE_16x16x32, SHAPE_32x32x16};
 constexpr int conv_class(int cout, bool pool) { return cout >= 128 ? (pool ? CONV_CLASS_NT2_POOL : CONV_CLASS_NT2) : CONV_CLASS_NT1; }
 template <typename T, bool BWD> constexpr int conv_shape(int cls) { return (sizeof(T) == 2 && !BWD) ? kConvClassShape[cls] : SHAPE_32x32x16; }
-template <typename T, bool BWD = false>
-static bool launch_conv(hipStream_t st, ConvArgs a, bool pool) {
-  if (a.unpool_idx && !(BWD && !pool)) {      // (cannot happen from this library's callers; the plain kernels ignore the field)
-    hla_set_error("launch_conv: an un-pooled source needs the UNPOOL kernel (backward, no pooling epilogue)");
-    return false;
-  }
+// What a launch decides before it picks its kernel: the tile geometry (written into the arguments), the grid and the profile record.
+struct ConvPlan { bool small; int gx, gy, kid; double flops, bytes; };
+template <typename T, bool BWD>
+static ConvPlan conv_plan(ConvArgs& a, bool pool) {
   a.tiles_x = (a.W + 31) / 32;
   a.tiles_y = (a.H - a.row_begin + 7) / 8;
-#if HLA_CONV_STAMPS
-  a.stamps = nullptr;
-  if (g_hla_stamp.buf && g_hla_stamp.counter++ == g_hla_stamp.want) {
-    a.stamps = g_hla_stamp.buf;
-    g_hla_stamp.grid_x = a.tiles_x * a.tiles_y * a.B; g_hla_stamp.grid_y = a.Cout >= 128 ? a.Cout / 128 : 1;
-  }
-#endif
   // (the 64-channel block at three workgroups per CU for the Cout >= 128 layers as well: 259 against 244 us per launch, same-box A/B)
   const bool big = a.Cout >= 128;
-  const dim3 grid(a.tiles_x * a.tiles_y * a.B, big ? a.Cout / 128 : 1);
+  ConvPlan p{};
+  p.gy = big ? a.Cout / 128 : 1;
   const size_t es = sizeof(T), P = (size_t)a.B * (a.H - a.row_begin) * a.W, Po = pool ? P / 4 : P;
-  const double flops = 2.0 * 9.0 * (a.C1 + a.C2) * a.Cout * (double)P + (a.wg0_part ? 2.0 * 27 * 64 * (double)P : 0.0);
-  const double bytes = (double)P * ((a.up1 ? a.C1 / 4.0 : a.C1) + a.C2) * es + (double)Po * a.Cout * ((a.out_act ? es : 0) + (a.out_raw ? 4 : 0));
-  // (a data-dependent launch visits n_live of its tiles_x * tiles_y tiles per sample: the record carries the executed share)
-  hla_prof_begin_dyn(a.Cout >= 128 ? (pool ? K_CONV_NT2_POOL : K_CONV_NT2) : (pool ? K_CONV_NT1_POOL : K_CONV_NT1), flops, bytes, st,
-                     a.dyn ? a.dyn + a.dyn_desc : nullptr, a.tiles_x * a.tiles_y);
+  p.flops = 2.0 * 9.0 * (a.C1 + a.C2) * a.Cout * (double)P + (a.wg0_part ? 2.0 * 27 * 64 * (double)P : 0.0);
+  p.bytes = (double)P * ((a.up1 ? a.C1 / 4.0 : a.C1) + a.C2) * es + (double)Po * a.Cout * ((a.out_act ? es : 0) + (a.out_raw ? 4 : 0));
+  p.kid = big ? (pool ? K_CONV_NT2_POOL : K_CONV_NT2) : (pool ? K_CONV_NT1_POOL : K_CONV_NT1);
   // A forward launch that cannot fill the chip (a single pair's H/4 layers are 64-128 workgroups on 256 CUs, and the forward
   // is then a chain of such launches) takes 4-row tiles (MT = 2): twice the workgroups, each with half the work -- every output
   // element's sum is formed in the same order, so the result is bit-identical.  Not for the three feature layers: their
   // sum-of-squares partials are per tile, and a sample's L2 norm must not depend on its batch mates to the last bit.
+  p.small = !BWD && !a.dyn && !a.sumsq && !a.unpool_idx && a.tiles_x * a.tiles_y * a.B * p.gy < CONV_SMALL_GRID;
+  if (p.small) a.tiles_y = (a.H - a.row_begin + 3) / 4;
+  p.gx = a.tiles_x * a.tiles_y * a.B;
+  return p;
+}
+// one instantiation, as a plain launch or (PAIR) as a two-segment one: segment 0 = a / p, segment 1 = a2 / p2
+template <typename T, int MT, int NT, bool POOL, int WD, bool UNPOOL, int SHAPE, bool PAIR>
+static void conv_dispatch(hipStream_t st, const ConvArgs& a, const ConvPlan& p, const ConvArgs& a2, const ConvPlan& p2) {
+  if constexpr (PAIR) {
+    static_assert(!UNPOOL, "two-segment launches: forward inference forms only");
+    PairArgs<ConvArgs> pa{{a, a2}, p.gx};
+    hipLaunchKernelGGL((conv3x3_pair_kernel<T, MT, NT, 2, 2, POOL, WD, SHAPE>), dim3(p.gx + p2.gx, p.gy), dim3(256), 0, st, pa);
+  } else {
+    hipLaunchKernelGGL((conv3x3_kernel<T, MT, NT, 2, 2, POOL, WD, UNPOOL, SHAPE>), dim3(p.gx, p.gy), dim3(256), 0, st, a);
+  }
+}
+// PAIR: `a2` is the same layer of a second network (same Cout, pooling and kernel instantiation: the caller has checked that both
+// take the same side of CONV_SMALL_GRID); both run in ONE launch and the profile record carries the summed FLOPs and bytes.
+template <typename T, bool BWD, bool PAIR>
+static bool launch_conv_impl(hipStream_t st, ConvArgs a, ConvArgs a2, bool pool) {
+  if (a.unpool_idx && !(BWD && !pool)) {      // (cannot happen from this library's callers; the plain kernels ignore the field)
+    hla_set_error("launch_conv: an un-pooled source needs the UNPOOL kernel (backward, no pooling epilogue)");
+    return false;
+  }
+  const ConvPlan p = conv_plan<T, BWD>(a, pool);
+  ConvPlan p2{};
+  if constexpr (PAIR) {
+    p2 = conv_plan<T, BWD>(a2, pool);
+    auto infer = [](const ConvArgs& c) {      // (pair_inference_args)
+      return !c.dyn && !c.src_row_lo && !c.add_row_lo && !c.unpool_idx && !c.mask_act && !c.add_src && !c.idx_out && !c.pool_sum && !c.wg0_part;
+    };
+    if (BWD || !infer(a) || !infer(a2) || p2.small != p.small || p2.gy != p.gy || a2.Cout != a.Cout) {
+      hla_set_error("launch_conv: the two segments of a paired launch do not take the same kernel");
+      return false;
+    }
+  }
+#if HLA_CONV_STAMPS
+  // (tooling build: a paired launch is neither stamped nor counted, so `want` numbers the PLAIN launches only -- the stamp tool
+  //  runs the inference path with args.pair_extractor_launches = 0, where the k-th launch is the k-th layer as before)
+  a.stamps = a2.stamps = nullptr;
+  if (!PAIR && g_hla_stamp.buf && g_hla_stamp.counter++ == g_hla_stamp.want) {
+    a.stamps = g_hla_stamp.buf;
+    g_hla_stamp.grid_x = a.tiles_x * ((a.H - a.row_begin + 7) / 8) * a.B; g_hla_stamp.grid_y = p.gy;
+  }
+#endif
+  const bool big = a.Cout >= 128;
+  // (a data-dependent launch visits n_live of its tiles_x * tiles_y tiles per sample: the record carries the executed share)
+  hla_prof_begin_dyn(p.kid, p.flops + p2.flops, p.bytes + p2.bytes, st, a.dyn ? a.dyn + a.dyn_desc : nullptr, a.tiles_x * a.tiles_y);
   constexpr int S_NT2 = conv_shape<T, BWD>(CONV_CLASS_NT2), S_NT2P = conv_shape<T, BWD>(CONV_CLASS_NT2_POOL),
                 S_NT1 = conv_shape<T, BWD>(CONV_CLASS_NT1);
-  if constexpr (!BWD) {
-    const int gy = big ? a.Cout / 128 : 1;
-    if (!a.dyn && !a.sumsq && !a.unpool_idx && a.tiles_x * a.tiles_y * a.B * gy < CONV_SMALL_GRID) {
-      a.tiles_y = (a.H - a.row_begin + 3) / 4;
-      const dim3 g4(a.tiles_x * a.tiles_y * a.B, gy);
+  constexpr bool UNP = BWD && !PAIR;      // only the backward's translation unit compiles the UNPOOL instantiations
+  if (p.small) {      // (never with BWD: conv_plan)
+    if constexpr (!BWD) {
       if (big) {
-        if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 2, 2, true, 1, false, S_NT2P>), g4, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 2, 2, false, 1, false, S_NT2>), g4, dim3(256), 0, st, a);
+        if (pool) conv_dispatch<T, 2, 2, true, 1, false, S_NT2P, PAIR>(st, a, p, a2, p2);
+        else conv_dispatch<T, 2, 2, false, 1, false, S_NT2, PAIR>(st, a, p, a2, p2);
       } else {
-        if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 1, 2, 2, true, 2, false, S_NT1>), g4, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 1, 2, 2, false, 2, false, S_NT1>), g4, dim3(256), 0, st, a);
+        if (pool) conv_dispatch<T, 2, 1, true, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
+        else conv_dispatch<T, 2, 1, false, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
       }
-      hla_prof_end(st);
-      return true;
     }
+    hla_prof_end(st);
+    return true;
   }
   // Cout >= 128: block = 8x32 pixels x 128 channels, waves 2(M) x 2(N), wave tile 128 px x 64 ch, weights 1 tap ahead
   // Cout == 64 : block = 8x32 pixels x  64 channels, waves 2 x 2,       wave tile 128 px x 32 ch, weights 2 taps ahead
   if (big) {
     // (weights two taps ahead for this tile as well: spills with the register-staged loader, -1 %; with the LDS-DMA loader it
     //  fits -- 232 registers -- and measures the same: 4876 / 4871 against 4870 / 4841 pairs/s)
-    if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, true, 1, false, S_NT2P>), grid, dim3(256), 0, st, a);
-    else if (BWD && a.unpool_idx) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, false, 1, BWD, S_NT2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<T, 4, 2, 2, 2, false, 1, false, S_NT2>), grid, dim3(256), 0, st, a);
+    if (pool) conv_dispatch<T, 4, 2, true, 1, false, S_NT2P, PAIR>(st, a, p, a2, p2);
+    else if (UNP && a.unpool_idx) conv_dispatch<T, 4, 2, false, 1, UNP, S_NT2, PAIR>(st, a, p, a2, p2);
+    else conv_dispatch<T, 4, 2, false, 1, false, S_NT2, PAIR>(st, a, p, a2, p2);
   } else {
-    if (pool) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, true, 2, false, S_NT1>), grid, dim3(256), 0, st, a);
-    else if (BWD && a.unpool_idx) hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, false, 2, BWD, S_NT1>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 2, 2, false, 2, false, S_NT1>), grid, dim3(256), 0, st, a);
+    if (pool) conv_dispatch<T, 4, 1, true, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
+    else if (UNP && a.unpool_idx) conv_dispatch<T, 4, 1, false, 2, UNP, S_NT1, PAIR>(st, a, p, a2, p2);
+    else conv_dispatch<T, 4, 1, false, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
   }
   hla_prof_end(st);
   return true;
+}
+template <typename T, bool BWD = false>
+static bool launch_conv(hipStream_t st, const ConvArgs& a, bool pool) { return launch_conv_impl<T, BWD, false>(st, a, ConvArgs{}, pool); }
+template <typename T>
+static bool launch_conv_pair(hipStream_t st, const ConvArgs& a, const ConvArgs& a2, bool pool) {
+  return launch_conv_impl<T, false, true>(st, a, a2, pool);
 }

@@ -43,12 +43,19 @@ void vgg_pack_all(const hla_vgg_params* prm, char* packed, int dtype, hipStream_
   }
 }
 
+// Everything a forward launches for its convolution layers, as argument blocks.  The geometry (which rows a layer computes, its
+// sources, its epilogue's outputs) is decided once, here, for the plain forward and for the paired one (vgg_forward_pair_t).
+struct VggConvSet {
+  Conv02Args c02;
+  ConvArgs conv[kAllLayers];      // by layer index (vgg_layers.h); [0], [1] unused: conv0 + conv2 are c02
+  bool used[kAllLayers], pool[kAllLayers];
+  int np_used[4];                 // sum-of-squares partials per sample the feature layers actually write
+  bool ok;
+};
 template <typename T>
-int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                         float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
-                         int flags, int first_row8, hipStream_t st) {
+static void vgg_build_convs(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
+                            bool want_conf, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, VggConvSet& S) {
   const bool level4 = pl.x2r != 0;
-  const int NL = level4 ? 4 : 3;
   // HLA_VGG_FOLD_DECODER (VGGUnet_G2S, VGG.py:278-310): the maps behind the encoder are read as [2h, w/2].  On NHWC storage
   // that is the same buffer, so only the geometry the decoder launches are given changes: dH(d), dW(d) for the 1/d maps.
   const bool fold = (flags & HLA_VGG_FOLD_DECODER) != 0;
@@ -60,55 +67,39 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   const float* wtail = (const float*)(packed + packed_offset(kAllLayers, dtype));       // split mode: weight scales
   unsigned* amax = (unsigned*)(w + pl.amax);                                           // split mode: [slot][B]
   auto AM = [&](int slot) { return (SPLIT && slot >= 0) ? amax + (size_t)slot * B : (unsigned*)nullptr; };
-  if (SPLIT) HLA_CHECK_HIP(hipMemsetAsync(amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
+  const bool train = flags & HLA_VGG_SAVE_FOR_BACKWARD;
+  S = VggConvSet{};
+  S.ok = true;
+  for (int l = 0; l < 4; ++l) S.np_used[l] = pl.np[l];
   // conv0 + conv2 + pool fused (VGG.py:123-128): relu(x3)
-  auto conv02 = [&]() -> int {
-    Conv02Args a{};
+  {
+    Conv02Args& a = S.c02;
     a.x_plane = x_plane ? x_plane : (size_t)H * W;
     a.x = x; a.w0 = W_(0); a.b0 = prm->b[0]; a.w2 = W_(1); a.b2 = prm->b[1];
     a.out_act = w + pl.x3;
-    if (flags & HLA_VGG_SAVE_FOR_BACKWARD) {
+    if (train) {
       a.a0_out = w + pl.a0;
       a.idx_out = (unsigned char*)(w + pl.idx3);
     }
     if (level4) a.a2_out = w + pl.x2r;
     a.wtail = wtail; a.amax_out = AM(AM_X3); a.amax_a2_out = level4 ? AM(AM_X2) : nullptr;
-    a.amax_a0_out = (flags & HLA_VGG_SAVE_FOR_BACKWARD) ? AM(AM_A0) : nullptr;
+    a.amax_a0_out = train ? AM(AM_A0) : nullptr;
     // (first_row8, see below: x3 is needed from row 4f-16 on = conv2 row 8f-32)
-    const int f0 = (level4 || (flags & HLA_VGG_SAVE_FOR_BACKWARD)) ? 0 : first_row8;
+    const int f0 = (level4 || train) ? 0 : first_row8;
     a.row_begin = f0 ? 8 * f0 - 32 : 0;
     a.B = B; a.H = H; a.W = W; a.tiles_x = (W + 31) / 32; a.tiles_y = (H - a.row_begin + 7) / 8;
-    const double P = (double)B * (H - a.row_begin) * W;
-    constexpr int lds_bytes = conv02_lds_bytes<T>();
-    static HlaPerDeviceOnce attr_once;
-    HLA_CHECK_HIP(attr_once.run([] {
-      return hipFuncSetAttribute((const void*)conv02_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    }));
-#if HLA_CONV_STAMPS
-    a.stamps = nullptr;      // (tooling build: want = -10 - k arms the k-th conv02 launch since the call)
-    if (g_hla_stamp.buf && g_hla_stamp.want <= -10 && g_hla_stamp.want++ == -10) {
-      a.stamps = g_hla_stamp.buf; g_hla_stamp.want = -1000;
-      g_hla_stamp.grid_x = a.tiles_x * a.tiles_y * B; g_hla_stamp.grid_y = 1;
-    }
-#endif
-    hla_prof_begin(K_CONV02, 2.0 * 9 * (3 + 64) * 64 * P, P * (3 * 4 + 16 * sizeof(T)), st);
-    hipLaunchKernelGGL((conv02_kernel<T, 2>), dim3(a.tiles_x * a.tiles_y * B), dim3(256), lds_bytes, st, a);
-    hla_prof_end(st);
-    return HLA_OK;
-  };
-  const bool train = flags & HLA_VGG_SAVE_FOR_BACKWARD;
-  int np_used[4] = {pl.np[0], pl.np[1], pl.np[2], pl.np[3]};
-  bool launch_ok = true;
+  }
   auto conv = [&](int l, const void* s1, int C1, int H_, int W_h, void* act, int relu, bool pool, const void* s2 = nullptr,
                   int C2 = 0, int up1 = 0, void* raw = nullptr, double* ss = nullptr, unsigned char* idx = nullptr,
                   int row_begin = 0, int norm_level = -1) {
     // the packer laid the layer's weights out for the kernel class kLayers[l].pool puts it in: the launch must pick the same one
     if (pool != (kLayers[l].pool != 0)) {
       hla_set_error("vgg_forward: layer %d launched with pool = %d, the layer table says %d", l, (int)pool, kLayers[l].pool);
-      launch_ok = false;
+      S.ok = false;
       return;
     }
-    ConvArgs a{};
+    ConvArgs& a = S.conv[l];
+    S.used[l] = true; S.pool[l] = pool;
     a.raw16 = (raw && (flags & HLA_VGG_FEAT16)) ? 1 : 0;
     a.row_begin = row_begin < 0 ? 0 : row_begin;
     a.idx_out = train ? idx : nullptr;
@@ -124,9 +115,8 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
                                              {AM_X18, AM_X3, AM_D2A}, {AM_D2A, -1, AM_X21}, {AM_X21, AM_X2, AM_D3A}, {AM_D3A, -1, AM_X24}};
       a.amax1 = AM(kAm[l][0]); a.amax2 = AM(kAm[l][1]); a.amax_out = AM(kAm[l][2]); a.wscale = wtail + l;
     }
-    if (!launch_conv<T>(st, a, pool)) launch_ok = false;
     if (norm_level >= 0)      // sum-of-squares partials actually written by this launch: one per (tile, 128-cout block)
-      np_used[norm_level] = ((W_h + 31) / 32) * ((H_ - a.row_begin + 7) / 8) * (a.Cout >= 128 ? a.Cout / 128 : 1);
+      S.np_used[norm_level] = ((W_h + 31) / 32) * ((H_ - a.row_begin + 7) / 8) * (a.Cout >= 128 ? a.Cout / 128 : 1);
   };
   // first_row8 = f > 0: the caller reads the returned maps only from rows f (x15), 2f (x18), 4f (x21) on, so every layer only
   // has to produce the rows those depend on -- a 3x3 conv needs one more input row, a 2x upsample halves, a 2x2 pool doubles:
@@ -137,12 +127,11 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   // The 3x3 confidence heads read one row above the first confidence row that is used, so with them the decoder starts one
   // row earlier (the encoder's needs do not change: x15 [f-2..] and x8 [2f-4..] are covered).
   const int f = (level4 || train) ? 0 : first_row8;
-  const int wc = ((flags & HLA_VGG_WANT_CONF) && conf) ? 1 : 0;
+  const int wc = want_conf ? 1 : 0;
   const int r_c5 = f ? 4 * f - 15 : 0, r_c7 = f ? 4 * f - 14 : 0, r_c10 = f ? 2 * f - 6 : 0, r_c12 = f ? 2 * f - 5 : 0,
             r_c14 = f ? 2 * f - 4 : 0, r_d11 = f ? 2 * f - 2 - wc : 0, r_d13 = f ? 2 * f - 1 - wc : 0,
             r_d21 = f ? 4 * f - 1 - wc : 0, r_d23 = f ? 4 * f - wc : 0;
   // encoder (VGG.py:129-141).  ReLU commutes with max-pool, so pooled maps are stored post-ReLU.
-  if (const int rc = conv02()) return rc;
   conv(2, w + pl.x3, 64, H / 2, W / 2, w + pl.a5, 1, false, nullptr, 0, 0, nullptr, nullptr, nullptr, r_c5);      // conv5
   conv(3, w + pl.a5, 128, H / 2, W / 2, w + pl.x8, 1, true, nullptr, 0, 0, nullptr, nullptr,
        (unsigned char*)(w + pl.idx8), r_c7);                                          // conv7 + pool -> relu(x8)
@@ -165,8 +154,98 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
     conv(12, w + pl.d3a, 64, dH(1), dW(1), w + pl.x24r, 1, false, nullptr, 0, 0, feat[3],
          (double*)(w + pl.ss[3]), nullptr, 0, 3);                                      // dec3.3 -> x24 (16 real channels)
   }
+}
+
+// conv0 + conv2: one network, or (a1) the two networks of a paired forward as the two segments of one launch
+template <typename T>
+static int launch_conv02(hipStream_t st, Conv02Args a, const Conv02Args* a1) {
+  constexpr int lds_bytes = conv02_lds_bytes<T>();
+#if HLA_CONV_STAMPS
+  a.stamps = nullptr;      // (tooling build: want = -10 - k arms the k-th PLAIN conv02 launch since the call; paired ones are not counted)
+  if (!a1 && g_hla_stamp.buf && g_hla_stamp.want <= -10 && g_hla_stamp.want++ == -10) {
+    a.stamps = g_hla_stamp.buf; g_hla_stamp.want = -1000;
+    g_hla_stamp.grid_x = a.tiles_x * a.tiles_y * a.B; g_hla_stamp.grid_y = 1;
+  }
+#endif
+  auto P = [](const Conv02Args& c) { return (double)c.B * (c.H - c.row_begin) * c.W; };
+  const double Pt = P(a) + (a1 ? P(*a1) : 0.0);
+  if (a1) {
+    static HlaPerDeviceOnce attr_once;
+    HLA_CHECK_HIP(attr_once.run([] {
+      return hipFuncSetAttribute((const void*)conv02_pair_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    }));
+    PairArgs<Conv02Args> pa{{a, *a1}, a.tiles_x * a.tiles_y * a.B};
+#if HLA_CONV_STAMPS
+    pa.s[1].stamps = nullptr;
+#endif
+    hla_prof_begin(K_CONV02, 2.0 * 9 * (3 + 64) * 64 * Pt, Pt * (3 * 4 + 16 * sizeof(T)), st);
+    hipLaunchKernelGGL((conv02_pair_kernel<T, 2>), dim3(pa.n0 + a1->tiles_x * a1->tiles_y * a1->B), dim3(256), lds_bytes, st, pa);
+    hla_prof_end(st);
+    return HLA_OK;
+  }
+  static HlaPerDeviceOnce attr_once;
+  HLA_CHECK_HIP(attr_once.run([] {
+    return hipFuncSetAttribute((const void*)conv02_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  }));
+  hla_prof_begin(K_CONV02, 2.0 * 9 * (3 + 64) * 64 * Pt, Pt * (3 * 4 + 16 * sizeof(T)), st);
+  hipLaunchKernelGGL((conv02_kernel<T, 2>), dim3(a.tiles_x * a.tiles_y * a.B), dim3(256), lds_bytes, st, a);
+  hla_prof_end(st);
+  return HLA_OK;
+}
+
+// L2 normalisation: 1/||x|| per sample (always) for the NL levels of `nb` networks in one launch, then the in-place scaling unless
+// the caller folds it downstream
+struct VggNormNet { const VggConvSet* S; char* ws; const VggPlan* pl; double* inv_norm; void* const* feat; int H, W; };
+static int vgg_norms(hipStream_t st, int nb, const VggNormNet* net, int B, int NL, int flags) {
+  InvNormArgs ia{};
+  double bytes = 0;
+  for (int k = 0; k < nb; ++k)
+    for (int l = 0; l < NL; ++l) {
+      const VggNormNet& n = net[k];
+      ia.ss[k * NL + l] = (const double*)(n.ws + n.pl->ss[l]); ia.np[k * NL + l] = n.S->np_used[l];
+      ia.inv[k * NL + l] = (n.inv_norm ? n.inv_norm : (double*)(n.ws + n.pl->inv)) + (size_t)l * B;
+      bytes += (double)B * n.pl->np[l] * 8;
+    }
+  hla_prof_begin(K_L2NORM, 0, bytes, st);
+  hipLaunchKernelGGL(inv_norm_multi_kernel, dim3(B, nb * NL), dim3(256), 0, st, ia);
+  hla_prof_end(st);
+  for (int k = 0; k < nb; ++k) {
+    const int H = net[k].H, W = net[k].W;
+    const size_t per[4] = {(size_t)(H / 8) * (W / 8) * 256, (size_t)(H / 4) * (W / 4) * 128, (size_t)(H / 2) * (W / 2) * 64, (size_t)H * W * 64};
+    for (int l = 0; l < NL; ++l) {
+      if (flags & HLA_VGG_DEFER_NORM) continue;
+      int bps = (int)(per[l] / 4 / 256 / 4);
+      bps = bps < 1 ? 1 : (bps > 64 ? 64 : bps);
+      hla_prof_begin(K_L2NORM, 0, (double)B * per[l] * 8, st);
+      hipLaunchKernelGGL(scale_kernel, dim3(B * bps), dim3(256), 0, st, (float*)net[k].feat[l], ia.inv[k * NL + l], per[l], bps);
+      hla_prof_end(st);
+    }
+  }
+  return HLA_OK;
+}
+
+template <typename T>
+int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
+                         float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
+                         int flags, int first_row8, hipStream_t st) {
+  const bool level4 = pl.x2r != 0;
+  const int NL = level4 ? 4 : 3;
+  const bool fold = (flags & HLA_VGG_FOLD_DECODER) != 0;
+  auto dH = [&](int d) { return fold ? 2 * (H / d) : H / d; };
+  auto dW = [&](int d) { return fold ? (W / d) / 2 : W / d; };
+  char* w = ws;
+  constexpr bool SPLIT = Prec<T>::SPLIT;
+  if (SPLIT) HLA_CHECK_HIP(hipMemsetAsync(w + pl.amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
+  const bool want_conf = (flags & HLA_VGG_WANT_CONF) && conf;
+  VggConvSet S;
+  vgg_build_convs<T>(x, x_plane, prm, packed, dtype, feat, want_conf, ws, pl, B, H, W, flags, first_row8, S);
+  if (!S.ok) return HLA_ERR_ARG;
+  if (const int rc = launch_conv02<T>(st, S.c02, nullptr)) return rc;
+  bool launch_ok = true;
+  for (int l = 2; l < kAllLayers; ++l)
+    if (S.used[l] && !launch_conv<T>(st, S.conv[l], S.pool[l])) launch_ok = false;
   // confidence heads on the ReLU'd maps
-  if ((flags & HLA_VGG_WANT_CONF) && conf) {
+  if (want_conf) {
     using CT = std::conditional_t<SPLIT, float, T>;      // split mode stores fp32 activations: the heads run in plain fp32
     const CT* acts[4] = {(const CT*)(w + pl.x15r), (const CT*)(w + pl.x18r), (const CT*)(w + pl.x21r), (const CT*)(w + pl.x24r)};
     // (conf0 reads the UNFOLDED x15 also under HLA_VGG_FOLD_DECODER: VGG.py:322)
@@ -182,28 +261,44 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
       hla_prof_end(st);
     }
   }
-  // L2 normalisation: 1/||x|| per sample (always), in-place scaling unless the caller folds it downstream
   {
-    const size_t per[4] = {(size_t)(H / 8) * (W / 8) * 256, (size_t)(H / 4) * (W / 4) * 128, (size_t)(H / 2) * (W / 2) * 64,
-                           (size_t)H * W * 64};
-    double* inv = inv_norm ? inv_norm : (double*)(w + pl.inv);
-    {
-      InvNormArgs ia{};
-      double bytes = 0;
-      for (int l = 0; l < NL; ++l) { ia.ss[l] = (const double*)(w + pl.ss[l]); ia.np[l] = np_used[l]; bytes += (double)B * pl.np[l] * 8; }
-      ia.inv = inv; ia.B = B;
-      hla_prof_begin(K_L2NORM, 0, bytes, st);
-      hipLaunchKernelGGL(inv_norm_multi_kernel, dim3(B, NL), dim3(256), 0, st, ia);
-      hla_prof_end(st);
-    }
-    for (int l = 0; l < NL; ++l) {
-      if (flags & HLA_VGG_DEFER_NORM) continue;
-      int bps = (int)(per[l] / 4 / 256 / 4);
-      bps = bps < 1 ? 1 : (bps > 64 ? 64 : bps);
-      hla_prof_begin(K_L2NORM, 0, (double)B * per[l] * 8, st);
-      hipLaunchKernelGGL(scale_kernel, dim3(B * bps), dim3(256), 0, st, (float*)feat[l], inv + (size_t)l * B, per[l], bps);
-      hla_prof_end(st);
-    }
+    const VggNormNet net{&S, ws, &pl, inv_norm, feat, H, W};
+    if (const int rc = vgg_norms(st, 1, &net, B, NL, flags)) return rc;
+  }
+  HLA_CHECK_HIP(hipGetLastError());
+  return launch_ok ? HLA_OK : HLA_ERR_ARG;
+}
+
+// Inference forward of TWO networks (the satellite and the ground extractor) whose every convolution layer runs as ONE launch of
+// two segments.  The caller (hla_vgg_forward_pair) has checked the flags; returns HLA_PAIR_FALLBACK with nothing launched when a
+// layer's two segments would not take the same kernel instantiation (the two sides of CONV_SMALL_GRID).
+constexpr int HLA_PAIR_FALLBACK = -1000;
+template <typename T>
+int vgg_forward_pair_t(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st) {
+  constexpr bool SPLIT = Prec<T>::SPLIT;
+  VggConvSet S[2];
+  for (int k = 0; k < 2; ++k) {
+    vgg_build_convs<T>(br[k].x, br[k].x_plane, br[k].params, (const char*)br[k].packed_weights, dtype, br[k].feat, false,
+                       (char*)br[k].workspace, pl[k], B, br[k].H, br[k].W, flags, br[k].first_row8, S[k]);
+    if (!S[k].ok) return HLA_ERR_ARG;
+  }
+  for (int l = 2; l < kAllLayers; ++l) {
+    if (S[0].used[l] != S[1].used[l]) return HLA_PAIR_FALLBACK;
+    if (!S[0].used[l]) continue;
+    ConvArgs a0 = S[0].conv[l], a1 = S[1].conv[l];
+    if (conv_plan<T, false>(a0, S[0].pool[l]).small != conv_plan<T, false>(a1, S[1].pool[l]).small) return HLA_PAIR_FALLBACK;
+  }
+  if (SPLIT)
+    for (int k = 0; k < 2; ++k)
+      HLA_CHECK_HIP(hipMemsetAsync((char*)br[k].workspace + pl[k].amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
+  if (const int rc = launch_conv02<T>(st, S[0].c02, &S[1].c02)) return rc;
+  bool launch_ok = true;
+  for (int l = 2; l < kAllLayers; ++l)
+    if (S[0].used[l] && !launch_conv_pair<T>(st, S[0].conv[l], S[1].conv[l], S[0].pool[l])) launch_ok = false;
+  {
+    const VggNormNet nets[2] = {{&S[0], (char*)br[0].workspace, &pl[0], br[0].inv_norm, br[0].feat, br[0].H, br[0].W},
+                                {&S[1], (char*)br[1].workspace, &pl[1], br[1].inv_norm, br[1].feat, br[1].H, br[1].W}};
+    if (const int rc = vgg_norms(st, 2, nets, B, 3, flags)) return rc;
   }
   HLA_CHECK_HIP(hipGetLastError());
   return launch_ok ? HLA_OK : HLA_ERR_ARG;
@@ -214,11 +309,15 @@ template void vgg_pack_all<TuT>(const hla_vgg_params* prm, char* packed, int dty
 template int vgg_forward_t<TuT>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
                               int flags, int first_row8, hipStream_t st);
+template int vgg_forward_pair_t<TuT>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
 #else
 #define HLA_EXTERN_T(T) \
   extern template void vgg_pack_all<T>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st); \
   extern template int vgg_forward_t<T>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,                               int flags, int first_row8, hipStream_t st);
 HLA_EXTERN_T(float) HLA_EXTERN_T(bf16) HLA_EXTERN_T(f16) HLA_EXTERN_T(split32)
+#define HLA_EXTERN_PAIR_T(T) \
+  extern template int vgg_forward_pair_t<T>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
+HLA_EXTERN_PAIR_T(float) HLA_EXTERN_PAIR_T(bf16) HLA_EXTERN_PAIR_T(f16) HLA_EXTERN_PAIR_T(split32)
 
 extern "C" size_t hla_vgg_packed_weight_bytes(int dtype) {
   return packed_offset(kAllLayers, dtype) + (dtype == HLA_F16X3 ? kPackTailBytes : 0);
@@ -291,5 +390,39 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
                                   B, H, W, flags, first_row8, (hipStream_t)stream);
   return vgg_forward_t<float>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
                               B, H, W, flags, first_row8, (hipStream_t)stream);
+}
+
+extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level, int dtype, int flags, int* paired_out, hla_stream_t stream) {
+  HLA_REQUIRE(br, "hla_vgg_forward_pair: null argument");
+  if (paired_out) *paired_out = 0;
+  auto plain = [&]() -> int {
+    for (int k = 0; k < 2; ++k)
+      if (const int rc = hla_vgg_forward(br[k].x, br[k].x_plane, br[k].params, br[k].packed_weights, br[k].feat, br[k].conf, br[k].inv_norm,
+                                         br[k].workspace, br[k].workspace_bytes, B, br[k].H, br[k].W, level, dtype, flags, br[k].first_row8, stream))
+        return rc;
+    return HLA_OK;
+  };
+  if (level != 3 || (flags & (HLA_VGG_SAVE_FOR_BACKWARD | HLA_VGG_FOLD_DECODER | HLA_VGG_WANT_CONF)) || !hla_dtype_ok(dtype)) return plain();
+  // the argument checks of hla_vgg_forward, per network (a failed one is reported by the plain call)
+  VggPlan pl[2];
+  for (int k = 0; k < 2; ++k) {
+    const hla_vgg_branch& b = br[k];
+    const bool ok = b.x && b.params && b.packed_weights && b.workspace && B > 0 && b.H >= 8 && b.W >= 8 && b.H % 8 == 0 && b.W % 8 == 0 &&
+                    (b.x_plane == 0 || b.x_plane >= (size_t)b.H * b.W) && (size_t)b.H * b.W * 64 * 4 < ((size_t)1 << 31) &&
+                    b.feat[0] && b.feat[1] && b.feat[2] && (!(flags & HLA_VGG_DEFER_NORM) || b.inv_norm) &&
+                    (!(flags & HLA_VGG_FEAT16) || ((dtype == HLA_BF16 || dtype == HLA_F16) && (flags & HLA_VGG_DEFER_NORM))) &&
+                    (b.first_row8 == 0 || (b.first_row8 >= 4 && b.first_row8 < b.H / 8));
+    if (!ok) return plain();
+    vgg_plan(B, b.H, b.W, dtype, false, &pl[k], false, false);
+    if (b.workspace_bytes < pl[k].total) return plain();
+  }
+  int rc;
+  if (dtype == HLA_BF16) rc = vgg_forward_pair_t<bf16>(br, pl, B, dtype, flags, (hipStream_t)stream);
+  else if (dtype == HLA_F16) rc = vgg_forward_pair_t<f16>(br, pl, B, dtype, flags, (hipStream_t)stream);
+  else if (dtype == HLA_F16X3) rc = vgg_forward_pair_t<split32>(br, pl, B, dtype, flags, (hipStream_t)stream);
+  else rc = vgg_forward_pair_t<float>(br, pl, B, dtype, flags, (hipStream_t)stream);
+  if (rc == HLA_PAIR_FALLBACK) return plain();
+  if (rc == HLA_OK && paired_out) *paired_out = 1;
+  return rc;
 }
 #endif

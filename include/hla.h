@@ -63,12 +63,13 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 24
+#define HLA_ABI_VERSION 25
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
   HLA_STRUCT_VGG_PARAMS = 0, HLA_STRUCT_VGG_GRADS = 1, HLA_STRUCT_S2G_LEVEL = 2, HLA_STRUCT_S2G_CONFIG = 3,
-  HLA_STRUCT_S2G_LEVEL_GRAD = 4, HLA_STRUCT_PROF_RECORD = 5, HLA_STRUCT_POSE_LOSS_ARGS = 6, HLA_STRUCT_FILL_REGION = 7
+  HLA_STRUCT_S2G_LEVEL_GRAD = 4, HLA_STRUCT_PROF_RECORD = 5, HLA_STRUCT_POSE_LOSS_ARGS = 6, HLA_STRUCT_FILL_REGION = 7,
+  HLA_STRUCT_VGG_BRANCH = 8
 } hla_struct_id;
 size_t hla_sizeof_struct(int id);  /* sizeof of the struct with that hla_struct_id, 0 for an unknown id */
 
@@ -142,6 +143,29 @@ size_t hla_vgg_workspace_bytes_flags(int B, int H, int W, int level, int dtype, 
 int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights, void* const feat[4],
                     float* const conf[4], double* inv_norm, void* workspace, size_t workspace_bytes, int B, int H,
                     int W, int level, int dtype, int flags, int first_row8, hla_stream_t stream);
+
+/* One network of hla_vgg_forward_pair: the per-network arguments of hla_vgg_forward, with the same meaning. */
+typedef struct hla_vgg_branch {
+  const float* x;
+  size_t x_plane;
+  const hla_vgg_params* params;
+  const void* packed_weights;
+  void* feat[4];
+  float* conf[4];
+  double* inv_norm;
+  void* workspace;
+  size_t workspace_bytes;
+  int H, W, first_row8;
+} hla_vgg_branch;
+
+/* The inference forward of TWO networks on batches of one size B (the satellite and the ground extractor of LM_S2GP): computes
+ * exactly what hla_vgg_forward(br[0]...) followed by hla_vgg_forward(br[1]...) computes, bit for bit, into the same outputs.
+ * When it can, every convolution layer of the two networks runs as ONE launch whose workgroups are dealt to two segments (10
+ * launches -- conv0 + conv2 fused and the nine 3x3 layers -- instead of 20, and one inv_norm launch for both): level 3, no HLA_VGG_SAVE_FOR_BACKWARD / HLA_VGG_FOLD_DECODER /
+ * HLA_VGG_WANT_CONF, and every layer's two launches on the same side of the small-grid threshold (they must be one kernel).
+ * Otherwise it makes the two hla_vgg_forward calls and returns what they return: being unable to pair is never an error.
+ * paired_out (may be NULL) receives 1 when the paired launches were issued and 0 when the two plain forwards ran. */
+int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level, int dtype, int flags, int* paired_out, hla_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Backward of VGGUnet (autograd through VGG.py:121-203 in the reference).

@@ -13,7 +13,8 @@ from highlyaccurate_amd.models_kitti import LM_S2GP
 from highlyaccurate_amd import _lib
 prec = sys.argv[1] if len(sys.argv) > 1 else 'bf16'
 d = torch.device('cuda:0')
-args = SimpleNamespace(level=3, N_iters=5, using_weight=0, loss_method=0, proj='geo', Optimizer='LM', rotation_range=10.0, shift_range_lat=20.0, shift_range_lon=20.0, damping=0.1, train_damping=0, dropout=0, use_hessian=0, use_gt_depth=0, visualize=0, coe_shift_lat=100.0, coe_shift_lon=100.0, coe_heading=100.0, coe_L1=100.0, coe_L2=100.0, coe_L3=100.0, coe_L4=100.0, estimate_depth=0, precision=prec)
+args = SimpleNamespace(level=3, N_iters=5, using_weight=0, loss_method=0, proj='geo', Optimizer='LM', rotation_range=10.0, shift_range_lat=20.0, shift_range_lon=20.0, damping=0.1, train_damping=0, dropout=0, use_hessian=0, use_gt_depth=0, visualize=0, coe_shift_lat=100.0, coe_shift_lon=100.0, coe_heading=100.0, coe_L1=100.0, coe_L2=100.0, coe_L3=100.0, coe_L4=100.0, estimate_depth=0, precision=prec,
+                       pair_extractor_launches=0)      # the stamps number the plain launches: one layer of one network each
 net = LM_S2GP(args).to(d).eval()
 lib = _lib.load()
 assert hasattr(lib, 'hla_debug_conv_stamps'), 'not a -DHLA_CONV_STAMPS=1 build (HLA_LIB=...libhla_stamps.so)'
