@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class HlaError(RuntimeError):
@@ -36,7 +36,9 @@ class S2GLevel(C.Structure):
     _fields_ = [('sat_feat', C.c_void_p), ('grd_feat', C.c_void_p), ('grd_conf', C.c_void_p), ('xyz', C.c_void_p),
                 ('sat_inv_norm', C.c_void_p), ('grd_inv_norm', C.c_void_p),
                 ('A', C.c_int), ('h', C.c_int), ('w', C.c_int), ('C', C.c_int), ('row0', C.c_int), ('grd_row_skip', C.c_int),
-                ('meter_per_pixel', C.c_double), ('centre', C.c_double), ('feat_dtype', C.c_int)]
+                ('meter_per_pixel', C.c_double), ('centre', C.c_double), ('feat_dtype', C.c_int),
+                ('ray', C.c_void_p), ('depth', C.c_void_p), ('depth_row', C.c_void_p), ('depth_col', C.c_void_p),
+                ('depth_h', C.c_int), ('depth_w', C.c_int)]
 
 
 class S2GConfig(C.Structure):

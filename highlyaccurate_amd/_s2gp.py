@@ -33,10 +33,8 @@ def _phase(name: str):
         h(name)
 
 
-def ground_plane_table(K_ori, grd_H, grd_W, ori_H, ori_W):
-    """Back-project the pixel grid onto the ground plane y = camera height
-    (models_kitti.py:655-682 / models_ford.py:132-155).  Same fp32 op sequence as the reference so the
-    table is bit-identical.  Returns xyz [h,w,3] fp32 (CPU)."""
+def _camera_rays(K_ori, grd_H, grd_W, ori_H, ori_W):
+    """``xyz_w`` of grd_img2cam (models_kitti.py:657-673): K^-1 [u,v,1] with K rescaled to the level grid, [1,h,w,3] fp32."""
     K = torch.tensor(K_ori, dtype=torch.float32).reshape(1, 3, 3)
     Ks = K.clone()
     Ks[:, :1, :] = K[:, :1, :] * grd_W / ori_W
@@ -45,10 +43,31 @@ def ground_plane_table(K_ori, grd_H, grd_W, ori_H, ori_W):
     v, u = torch.meshgrid(torch.arange(0, grd_H, dtype=torch.float32),
                           torch.arange(0, grd_W, dtype=torch.float32), indexing='ij')
     uv1 = torch.stack([u, v, torch.ones_like(u)], dim=-1).unsqueeze(0)
-    xyz_w = torch.sum(Kinv[:, None, None, :, :] * uv1[:, :, :, None, :], dim=-1)
+    return torch.sum(Kinv[:, None, None, :, :] * uv1[:, :, :, None, :], dim=-1)
+
+
+def ray_table(K_ori, grd_H, grd_W, ori_H, ori_W):
+    """The camera rays of the pixel grid, ``xyz_grds[l][2]`` of the reference (models_kitti.py:673,682): what args.use_gt_depth
+    multiplies by the depth map (741-745).  Same fp32 op sequence, bit-identical.  Returns [h,w,3] fp32 (CPU)."""
+    return _camera_rays(K_ori, grd_H, grd_W, ori_H, ori_W)[0].contiguous()
+
+
+def ground_plane_table(K_ori, grd_H, grd_W, ori_H, ori_W):
+    """Back-project the pixel grid onto the ground plane y = camera height
+    (models_kitti.py:655-682 / models_ford.py:132-155).  Same fp32 op sequence as the reference so the
+    table is bit-identical.  Returns xyz [h,w,3] fp32 (CPU)."""
+    xyz_w = _camera_rays(K_ori, grd_H, grd_W, ori_H, ori_W)
     y = xyz_w[..., 1:2]
     w = utils.Camera_height / torch.where(torch.abs(y) > utils.EPS, y, utils.EPS * torch.ones_like(y))
     return (xyz_w * w)[0].contiguous()
+
+
+def nearest_indices(n_in: int, n_out: int):
+    """Source index of every destination index under ``F.interpolate(x, size=n_out)`` in its default (nearest) mode along one
+    axis: torch's own rule, min(floor(dst * fp32(n_in / n_out)), n_in - 1) with the product in fp32.  int32 [n_out] (CPU)."""
+    scale = np.float32(n_in) / np.float32(n_out)
+    src = np.floor(np.arange(n_out, dtype=np.float32) * scale).astype(np.int64)
+    return torch.from_numpy(np.minimum(src, n_in - 1).astype(np.int32))
 
 
 def polar_plane_table(grd_H, grd_W):
@@ -241,7 +260,7 @@ class S2GPBase(nn.Module):
         if getattr(args, 'estimate_depth', 0):
             raise NotImplementedError('estimate_depth (Ford height heads, VGG.py:85-118) is out of scope')
         # args.use_gt_depth only takes effect when a gt_depth tensor is passed to forward (models_kitti.py:741); neither
-        # driver ever passes one (train_kitti.py:357,49), so the flag is accepted and forward() rejects an actual depth map
+        # driver ever passes one (train_kitti.py:357,49).  LM_S2GP.forward then lifts every ground pixel by its depth (`_depth_arg`)
         precision = getattr(args, 'precision', 'fp32')
         self.SatFeatureNet = VGGUnet(self.level, precision=precision)
         self.GrdFeatureNet = VGGUnet(self.level, precision=precision)
@@ -251,6 +270,8 @@ class S2GPBase(nn.Module):
             self.damping = nn.Parameter(torch.zeros(size=(), dtype=torch.float32))
         self.meters_per_pixel = [utils.get_meter_per_pixel() * (2 ** (3 - l)) for l in range(4)]
         self._tables = {}
+        self._ray_tables = {}
+        self._depth_idx = {}
         self.last_trace = None       # [B, N_iters, Level, 3] (shift_u, shift_v, theta) of the last forward
         self.last_normal_eq = None
         self.last_keep = None
@@ -270,6 +291,33 @@ class S2GPBase(nn.Module):
                                  for h, w in hw]
         # level 2 (Ford, models_ford.py:59-65): grd_img2cam(H / 2^(2 - l)) for l = 0, 1 = the H/4 and H/2 tables
         return self._tables[key][1:3] if self.level == 2 else self._tables[key]
+
+    def ray_tables(self, grd_H: int, grd_W: int, device):
+        """Per-level camera-ray tables (``ray_table``), sized and cached like ``xyz_tables``: what a depth map lifts."""
+        key = (grd_H, grd_W, str(device))
+        if key not in self._ray_tables:
+            K = ford_K_network_input() if self.ford else KITTI_K
+            self._ray_tables[key] = [ray_table(K, grd_H / 2 ** (3 - l), grd_W / 2 ** (3 - l), 256, 1024).to(device) for l in range(4)]
+        return self._ray_tables[key][1:3] if self.level == 2 else self._ray_tables[key]
+
+    def depth_indices(self, h: int, w: int, dH: int, dW: int, device):
+        """(rows int32 [h], columns int32 [w]) on the device: ``nearest_indices`` of a [dH,dW] depth map for an h x w level map."""
+        key = (h, w, dH, dW, str(device))
+        if key not in self._depth_idx:
+            self._depth_idx[key] = (nearest_indices(dH, h).to(device), nearest_indices(dW, w).to(device))
+        return self._depth_idx[key]
+
+    def _depth_arg(self, gt_depth, B: int, device):
+        """The depth map as the kernels read it -- ``.to(device).float().contiguous()`` [B,dH,dW] -- or None."""
+        if gt_depth is None:
+            return None
+        if self.polar:
+            # the reference indexes xyz_grds[l][2], which grd_img2cam_polar does not return: IndexError there
+            raise NotImplementedError("proj='polar' with a depth map: the reference's polar tables have no camera rays to lift "
+                                      "(models_kitti.py:742 raises IndexError)")
+        if gt_depth.dim() != 3 or gt_depth.shape[0] != B or gt_depth.shape[1] < 1 or gt_depth.shape[2] < 1:
+            raise ValueError(f'gt_depth must be [B,dH,dW] with B = {B}, got {tuple(gt_depth.shape)}')
+        return gt_depth.detach().to(device).float().contiguous()
 
     def _levels(self, maps):
         """The extractor always computes x15, x18, x21 (x15 feeds the decoder); level 2 uses the last two (VGG.py:183-184,198-199)."""
@@ -330,10 +378,12 @@ class S2GPBase(nn.Module):
             keep[k, inds] = 1
         return torch.from_numpy(keep).to(device)
 
-    def _lm_structs(self, sat_feats, grd_feats, grd_confs, grd_hw, extra, level_first, sat_inv_norm, grd_inv_norm):
+    def _lm_structs(self, sat_feats, grd_feats, grd_confs, grd_hw, extra, level_first, sat_inv_norm, grd_inv_norm, depth=None):
+        """``depth``: the result of ``_depth_arg`` (the caller keeps it alive over the call), or None."""
         dev = sat_feats[0].device
         L = len(sat_feats)
         tables = self.xyz_tables(grd_hw[0], grd_hw[1], dev)
+        rays = self.ray_tables(grd_hw[0], grd_hw[1], dev) if depth is not None else None
         cfg = self._config(L, level_first)
         lv = (_lib.S2GLevel * L)()
         for l in range(L):
@@ -350,6 +400,10 @@ class S2GPBase(nn.Module):
             lv[l].sat_feat, lv[l].grd_feat, lv[l].feat_dtype = s.data_ptr(), g.data_ptr(), _FEAT_DTYPES[s.dtype]
             lv[l].grd_conf = grd_confs[l].data_ptr() if (self.using_weight and grd_confs[l] is not None) else 0
             lv[l].xyz = tables[l].data_ptr()
+            if depth is not None:      # per-sample points ray * depth, mask depth != -1 (models_kitti.py:741-748; include/hla.h)
+                ri, ci = self.depth_indices(h, w, depth.shape[1], depth.shape[2], dev)
+                lv[l].ray, lv[l].depth, lv[l].depth_row, lv[l].depth_col = rays[l].data_ptr(), depth.data_ptr(), ri.data_ptr(), ci.data_ptr()
+                lv[l].depth_h, lv[l].depth_w = depth.shape[1], depth.shape[2]
             lv[l].sat_inv_norm = sat_inv_norm[l].data_ptr() if sat_inv_norm is not None else 0
             lv[l].grd_inv_norm = grd_inv_norm[l].data_ptr() if grd_inv_norm is not None else 0
             lv[l].A, lv[l].h, lv[l].w, lv[l].C, lv[l].row0, lv[l].grd_row_skip = A, h, w, Cn, row0, skip
@@ -365,14 +419,17 @@ class S2GPBase(nn.Module):
 
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def lm_solve(self, sat_feats, grd_feats, grd_confs, grd_hw, extra=None, level_first=0, init_pose=None,
-                 sat_inv_norm=None, grd_inv_norm=None, keep_normal_eq=None):
+                 sat_inv_norm=None, grd_inv_norm=None, keep_normal_eq=None, gt_depth=None):
         """sat_feats/grd_feats: NHWC fp32 lists (L2-normalised, or raw together with their [L,B] fp64
-        inverse norms); returns trace [B,N_iters,L,3] = (shift_u, shift_v, theta)."""
+        inverse norms); returns trace [B,N_iters,L,3] = (shift_u, shift_v, theta).
+        ``gt_depth`` [B,dH,dW] (any size): every ground pixel is lifted to ray * depth instead of onto the ground plane, with
+        the mask depth != -1 (models_kitti.py:741-748); None: the flat-ground tables."""
         lib = _lib.load()
         dev = sat_feats[0].device
         B, L = sat_feats[0].shape[0], len(sat_feats)
+        depth = self._depth_arg(gt_depth, B, dev)
         cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, level_first,
-                                               sat_inv_norm, grd_inv_norm)
+                                               sat_inv_norm, grd_inv_norm, depth)
         steps = L * self.N_iters
         reinit = (self.ford or cfg.dof == 3) and cfg.optimizer in (0, 3)
         rand_uv = self._draw_reinit(steps, B, dev) if reinit else None
@@ -437,16 +494,18 @@ class S2GPBase(nn.Module):
 
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def lm_backward(self, sat_feats, grd_feats, grd_confs, grd_hw, trace, normal_eq, d_trace, extra=None, level_first=0,
-                    init_pose=None, sat_inv_norm=None, grd_inv_norm=None, keep=None, grd_first_row8=0, overwrite=True):
+                    init_pose=None, sat_inv_norm=None, grd_inv_norm=None, keep=None, grd_first_row8=0, overwrite=True, gt_depth=None):
         """Backward of ``lm_solve``: d(loss)/d(trace) [B,N,L,3] -> (d_sat[l], d_grd[l], d_conf[l] or None, d_lambda[4]).
         ``keep``: the forward's dropout mask (``self.last_keep``), if args.dropout.
         Map gradients are NHWC fp32 and taken w.r.t. the L2-normalised maps (inv_norm * stored map).
-        ``args.deterministic_backward``: hla_s2g_config.deterministic."""
+        ``args.deterministic_backward``: hla_s2g_config.deterministic.  ``gt_depth``: the forward's depth map (no gradient
+        is taken w.r.t. it)."""
         lib = _lib.load()
         dev = sat_feats[0].device
         B, L = sat_feats[0].shape[0], len(sat_feats)
+        depth = self._depth_arg(gt_depth, B, dev)
         cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, level_first,
-                                               sat_inv_norm, grd_inv_norm)
+                                               sat_inv_norm, grd_inv_norm, depth)
         if keep is not None:
             cfg.keep, cfg.keep_stride = keep.data_ptr(), keep.shape[1]
         det = bool(getattr(self.args, 'deterministic_backward', 0))
@@ -537,17 +596,19 @@ class S2GPBase(nn.Module):
         return L(sat_feats), L(sat_inv), L(grd_feats), L(grd_confs), L(grd_inv)
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
-    def localise(self, sat_map, grd_img, want_conf, extra, level_first, init_pose, return_confs=True):
+    def localise(self, sat_map, grd_img, want_conf, extra, level_first, init_pose, return_confs=True, gt_depth=None):
         """Both feature pyramids (normalisation deferred into the LM sums) + the whole LM loop.
         return_confs=False (mode='test'): the caller does not need full-size confidence maps, so the ground extractor
         only runs on the image rows that can influence the bottom half of its maps (``dead_ground_rows``).
         Under autograd (training) the same kernels run inside one autograd.Function whose backward is the HIP
-        backward pass (hla_s2g_lm_solve_bwd + hla_vgg_backward for both extractors)."""
+        backward pass (hla_s2g_lm_solve_bwd + hla_vgg_backward for both extractors).
+        ``gt_depth`` [B,dH,dW] or None: ``lm_solve``'s depth map; it gets no gradient."""
         if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
                 or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
             raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
                              f'and {tuple(grd_img.shape)}')
         _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
+        gt_depth = self._depth_arg(gt_depth, sat_map.shape[0], sat_map.device)      # (checked before the extractors run)
         if self.polar and self.ford and level_first:
             # models_ford.py:935-950: the level-first loop has no proj branch and reads the bottom half of the polar table
             raise NotImplementedError("LM_S2GP_Ford(proj='polar') with level_first=1: the reference's level-first loop reads only "
@@ -555,12 +616,12 @@ class S2GPBase(nn.Module):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             names = [n for n, _ in self.named_parameters()]
             params = [p for _, p in self.named_parameters()]
-            out = _LocaliseFn.apply(self, names, sat_map, grd_img, want_conf, extra, level_first, init_pose, *params)
+            out = _LocaliseFn.apply(self, names, sat_map, grd_img, want_conf, extra, level_first, init_pose, gt_depth, *params)
             return out[0], list(out[1:]) if want_conf else [None] * self.level
         # (the two dense extractor passes on two streams measured 2 % slower than back to back: DESIGN.md 3.1)
         sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, want_conf, return_confs)
         trace = self.lm_solve(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], extra, level_first, init_pose,
-                              sat_inv, grd_inv)
+                              sat_inv, grd_inv, gt_depth=gt_depth)
         return trace, grd_confs
 
 
@@ -643,7 +704,7 @@ class _LocaliseFn(torch.autograd.Function):
     """forward: trace [B,N,L,3] (+ the three ground confidence maps); backward: parameter gradients from HIP kernels."""
 
     @staticmethod
-    def forward(ctx, model, names, sat_map, grd_img, want_conf, extra, level_first, init_pose, *params):
+    def forward(ctx, model, names, sat_map, grd_img, want_conf, extra, level_first, init_pose, gt_depth, *params):
         sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True,
                                                      save_for_backward=True)
         _phase('fwd_sat')
@@ -664,9 +725,10 @@ class _LocaliseFn(torch.autograd.Function):
         ctx.conf0 = grd_confs[0] if (model.level == 2 and grd_confs is not None) else None      # (the head's backward needs its own map)
         sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = L(sat_feats), L(sat_inv), L(grd_feats), L(grd_confs), L(grd_inv)
         trace = model.lm_solve(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], extra, level_first, init_pose,
-                               sat_inv, grd_inv, keep_normal_eq=True)
+                               sat_inv, grd_inv, keep_normal_eq=True, gt_depth=gt_depth)
         _phase('lm_fwd')
         ctx.model, ctx.names, ctx.extra, ctx.level_first, ctx.init_pose = model, names, extra, level_first, init_pose
+        ctx.gt_depth = gt_depth                         # (no gradient: kept as it is for the backward's recomputed projection)
         ctx.state = (sat_feats, grd_feats, grd_confs, tuple(grd_img.shape[-2:]), trace.detach(), model.last_normal_eq, sat_inv, grd_inv, cs, cg,
                      model.last_keep)
         out_confs = ()
@@ -696,7 +758,8 @@ class _LocaliseFn(torch.autograd.Function):
         # the ground maps' gradient lives in rows h_l/2.. (all the LM loop reads): the backward skips the rows above its support
         f8 = _bwd_first_row8(model, grd_hw, grd_feats[-1].shape[1])       # (grd_feats[-1]: the H/2 map)
         d_sat, d_grd, d_conf, d_lam = model.lm_backward(sat_feats, grd_feats, grd_confs, grd_hw, trace, neq, d_trace, ctx.extra,
-                                                   ctx.level_first, ctx.init_pose, sat_inv, grd_inv, keep, grd_first_row8=f8)
+                                                   ctx.level_first, ctx.init_pose, sat_inv, grd_inv, keep, grd_first_row8=f8,
+                                                   gt_depth=ctx.gt_depth)
         _phase('lm_bwd')
         if model.level == 2:        # x15 takes no part in the loop: its gradient (and its confidence map's) is zero
             zf = lambda cx: torch.zeros_like(cx['feats'][0], dtype=torch.float32)
@@ -757,6 +820,6 @@ class _LocaliseFn(torch.autograd.Function):
                 sync.finish(sync.start({'damping': grads['damping']}))
         ctx.state = None            # release the saved workspaces now, not when the loss tensor dies
         _phase('vgg_bwd')
-        return (None,) * 8 + tuple(grads.get(n) for n in ctx.names)
+        return (None,) * 9 + tuple(grads.get(n) for n in ctx.names)
 
 

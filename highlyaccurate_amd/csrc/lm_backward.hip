@@ -220,7 +220,7 @@ __global__ __launch_bounds__(64) void lm_bwd_solve(BwdSolveArgs a) {
 
 
 struct BwdAccumArgs {
-  const float* sat; const float* grd; const float* conf; const float* xyz;
+  const float* sat; const float* grd; const float* conf; LmPoints pts;
   const double* coef;      // [B,COEF_N] forward coefficients of this step
   const double* adj;       // [B,16]: gS gG A00 A01 A02 A11 A12 A22 gU0 gU1 gU2 gV0 gV1 gV2
   const double* sat_inv;   // [B] or null
@@ -242,7 +242,7 @@ struct BwdAccumArgs {
 template <int C, bool USE_W, bool DET = false>
 __global__ __launch_bounds__(256, USE_W ? 3 : 4) void lm_bwd_accum(BwdAccumArgs a, BwdSolveArgs sa) {
   __shared__ PixParam pp[MAX_TP];
-  __shared__ float pxyz[MAX_TP][3];   // the pixel's ground-plane point (the coefficient adjoints weight by it)
+  __shared__ float pxyz[MAX_TP][3];   // the pixel's 3-D point, lifted by the depth map if there is one (the coefficient adjoints weight by it)
   __shared__ double red[4][12];
   __shared__ double c12s[12][256];
   int b, tile;
@@ -261,8 +261,9 @@ __global__ __launch_bounds__(256, USE_W ? 3 : 4) void lm_bwd_accum(BwdAccumArgs 
     const int p = p0 + tt;
     const int r = a.row0 + p / a.w, c = p % a.w;
     const float cw = USE_W ? a.conf[((size_t)b * a.hs + (r - a.rskip)) * a.w + c] : 1.f;
-    const float* qx = a.xyz + ((size_t)r * a.w + c) * 3;
-    PixParam P = lm_pixel<C>(cf, qx, a.A, cw);
+    float qx[3];
+    const bool gm = lm_point(a.pts, b, r, c, a.w, qx);
+    PixParam P = lm_pixel<C>(cf, qx, gm, a.A, cw);
     if (a.keep && !a.keep[p]) {          // dropped by args.dropout: the pixel leaves every sum (models_kitti.py:968-974)
       P.wx0 = P.wx1 = P.wy0 = P.wy1 = 0.f; P.off = P.dxo = P.dyo = 0; P.j2u = P.j2v = 0.f; P.gm = P.wt = P.m = 0.f;
     }
@@ -599,7 +600,7 @@ extern "C" int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
     const int l = step_level(k);
     const hla_s2g_level& v = lv[l];
     BwdAccumArgs aa{};
-    aa.sat = (const float*)v.sat_feat; aa.grd = (const float*)v.grd_feat; aa.conf = v.grd_conf; aa.xyz = v.xyz; aa.coef = coef; aa.adj = adj;
+    aa.sat = (const float*)v.sat_feat; aa.grd = (const float*)v.grd_feat; aa.conf = v.grd_conf; aa.pts = lm_points_of(v); aa.coef = coef; aa.adj = adj;
     aa.sat_inv = v.sat_inv_norm; aa.grd_inv = v.grd_inv_norm;
     aa.d_sat = gr[l].d_sat_feat; aa.d_grd = gr[l].d_grd_feat; aa.d_conf = gr[l].d_grd_conf; aa.part = part;
     aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.row0 = v.row0; aa.npix = (v.h - v.row0) * v.w;

@@ -10,7 +10,7 @@ struct __attribute__((aligned(16))) PixParam {
   int off, dxo, dyo;            // element offsets of the NW tap and the +x / +y neighbours
   float wx0, wx1, wy0, wy1;     // clamped-corner bilinear weights x in-bounds x ground mask
   float j2u, j2v;               // d(uv)/d(theta) at this pixel
-  float gm, wt;                 // ground mask (z>0), LM weight
+  float gm, wt;                 // ground mask (lm_point), LM weight
   float m;                      // in-bounds x ground mask (0/1)
 };
 
@@ -63,15 +63,44 @@ __device__ __forceinline__ bool lm_block_map(int xcd_affine, int nt, int nb, int
   return true;
 }
 
-// One ground pixel: satellite coordinates in fp64 from the sample's projection coefficients and the fp32
-// ground-plane table; clamped-corner bilinear weights with the hard in-bounds mask of jacobian.py:146-177.
+// Where a ground pixel's 3-D point comes from.  depth == null: the shared table `xyz` [h,w,3] (ground plane or polar fan), ground
+// mask z > 0.  depth != null (args.use_gt_depth, models_kitti.py:741-748): `xyz` holds the level's RAY table K^-1 [u,v,1] and the
+// point of sample b is ray * depth[b, ri[r], ci[c]] -- three fp32 products, like the reference's `xyz_w * depth` -- with the mask
+// depth != -1 AND NOTHING ELSE: a depth of 0 or a negative one other than -1 takes part (z > 0 is not tested on this path).
+// ri [h] / ci [w] are the source indices of F.interpolate's nearest resampling of the [dH,dW] map to the level, made by the host.
+struct LmPoints {
+  const float* xyz;
+  const float* depth;      // [B,dH,dW] fp32, indexed by the GLOBAL sample b, or null
+  const int* ri; const int* ci;
+  int dH, dW;
+};
+
+static inline LmPoints lm_points_of(const hla_s2g_level& v) {      // (hla_s2g_validate has checked the depth fields)
+  LmPoints P{};
+  P.xyz = v.depth ? v.ray : v.xyz; P.depth = v.depth; P.ri = v.depth_row; P.ci = v.depth_col; P.dH = v.depth_h; P.dW = v.depth_w;
+  return P;
+}
+
+// -> q[3] and the ground mask of pixel (r, c) of sample b; w = the level map's width
+__device__ __forceinline__ bool lm_point(const LmPoints& S, int b, int r, int c, int w, float q[3]) {
+  const float* t = S.xyz + ((size_t)r * w + c) * 3;
+  if (S.depth) {
+    const float d = S.depth[((size_t)b * S.dH + S.ri[r]) * S.dW + S.ci[c]];
+    q[0] = t[0] * d; q[1] = t[1] * d; q[2] = t[2] * d;
+    return d != -1.f;
+  }
+  q[0] = t[0]; q[1] = t[1]; q[2] = t[2];
+  return q[2] > 0.f;
+}
+
+// One ground pixel: satellite coordinates in fp64 from the sample's projection coefficients and the pixel's fp32 point and
+// ground mask (lm_point); clamped-corner bilinear weights with the hard in-bounds mask of jacobian.py:146-177.
 template <int C>
-__device__ __forceinline__ PixParam lm_pixel(const double* cf, const float* q, int A, float conf_w) {
+__device__ __forceinline__ PixParam lm_pixel(const double* cf, const float* q, bool gm, int A, float conf_w) {
   const double X = q[0], Y = q[1], Z = q[2];
   const double u = cf[0] * X + cf[1] * Y + cf[2] * Z + cf[3];
   const double v = cf[4] * X + cf[5] * Y + cf[6] * Z + cf[7];
   const double lim = (double)(A - 1);
-  const bool gm = q[2] > 0.f;
   const bool inb = (u >= 0.0) && (u <= lim) && (v >= 0.0) && (v <= lim);   // jacobian.py:168-170
   PixParam o;
   o.gm = gm ? 1.f : 0.f;

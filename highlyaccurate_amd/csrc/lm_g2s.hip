@@ -414,6 +414,7 @@ extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
     HLA_REQUIRE(lv[l].feat_dtype == HLA_F32, "hla_g2s_lm_solve: level %d: fp32 feature maps only", l);
     HLA_REQUIRE(!cfg->using_weight || lv[l].grd_conf, "hla_g2s_lm_solve: using_weight needs grd_conf");
     HLA_REQUIRE(lv[l].grd_row_skip == 0, "hla_g2s_lm_solve: the whole ground map is sampled (grd_row_skip must be 0)");
+    HLA_REQUIRE(!lv[l].depth, "hla_g2s_lm_solve: level %d: a depth map belongs to hla_s2g_* (LM_G2SP ignores gt_depth)", l);
   }
   size_t oc, op, opart;
   const size_t need = g2s_layout(cfg, lv, B, &oc, &op, &opart);
@@ -821,6 +822,7 @@ extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
   if (const int rc = g2s_validate("hla_g2s_lm_solve_bwd", cfg, lv, camera_k, ori_h, ori_w)) return rc;
   for (int l = 0; l < cfg->n_levels; ++l) {
     HLA_REQUIRE(lv[l].feat_dtype == HLA_F32 && lv[l].grd_row_skip == 0, "hla_g2s_lm_solve_bwd: level %d: whole fp32 maps only", l);
+    HLA_REQUIRE(!lv[l].depth, "hla_g2s_lm_solve_bwd: level %d: a depth map belongs to hla_s2g_* (LM_G2SP ignores gt_depth)", l);
     HLA_REQUIRE(lv[l].sat_feat && lv[l].grd_feat && gr[l].d_sat_feat && gr[l].d_grd_feat, "hla_g2s_lm_solve_bwd: level %d buffers missing", l);
     HLA_REQUIRE(!cfg->using_weight || lv[l].grd_conf, "hla_g2s_lm_solve_bwd: using_weight needs grd_conf");
   }

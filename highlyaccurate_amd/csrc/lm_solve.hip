@@ -119,7 +119,7 @@ struct AccumArgs {
   const void* sat;    // [B,A,A,C]  F elements (fp32, or bf16 / fp16 in the reduced-precision inference modes)
   const void* grd;    // [B,h,w,C]
   const float* conf;  // [B,h,w] or null
-  const float* xyz;   // [h,w,3]
+  LmPoints pts;       // the pixels' 3-D points: shared table, or ray table x per-sample depth (lm_common.h)
   const double* coef; // [B,COEF_N]
   double* part;       // [B,part_ld,PART_N]: a sample's rows do not move with the level, so that stream groups on different
                       // steps (levels with different nt) never share a row
@@ -189,7 +189,9 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
     const int p = p0 + tt;
     const int r = a.row0 + p / a.w, c = p % a.w;
     const float cw = USE_W ? a.conf[((size_t)b * a.hs + (r - a.rskip)) * a.w + c] : 1.f;
-    PixParam P = lm_pixel<C>(cf, a.xyz + ((size_t)r * a.w + c) * 3, a.A, cw);
+    float q[3];
+    const bool gm = lm_point(a.pts, b, r, c, a.w, q);
+    PixParam P = lm_pixel<C>(cf, q, gm, a.A, cw);
     if (a.keep && !a.keep[p]) {          // dropped by args.dropout: the pixel leaves every sum (models_kitti.py:968-974)
       P.wx0 = P.wx1 = P.wy0 = P.wy1 = 0.f; P.off = P.dxo = P.dyo = 0; P.j2u = P.j2v = 0.f; P.gm = P.wt = P.m = 0.f;
     }
@@ -295,14 +297,17 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
 
 // ---------------------------------------------------------------------------------------------
 // hla_s2g_config.count_in_view: the quantity jacobian.py:172 asserts on -- how many pixels of the WHOLE level map (all rows,
-// whatever their z > 0 mask) have satellite coordinates inside the map.  Geometry only; one thread per pixel.
-__global__ __launch_bounds__(256) void lm_inview_kernel(const double* __restrict__ coef, const float* __restrict__ xyz, int A,
+// whatever their ground mask) have satellite coordinates inside the map.  Geometry only; one thread per pixel.  With a depth map
+// the points are the lifted ones (lm_point); the mask is still ignored.
+__global__ __launch_bounds__(256) void lm_inview_kernel(const double* __restrict__ coef, LmPoints pts, int w, int A,
                                                         int npix, int* __restrict__ count, int b0) {
   const int b = b0 + blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
   const double* cf = coef + (size_t)b * COEF_N;
   int in = 0;
   if (p < npix) {
-    const double X = xyz[(size_t)p * 3], Y = xyz[(size_t)p * 3 + 1], Z = xyz[(size_t)p * 3 + 2];
+    float q[3];
+    (void)lm_point(pts, b, p / w, p % w, w, q);
+    const double X = q[0], Y = q[1], Z = q[2];
     const double u = cf[0] * X + cf[1] * Y + cf[2] * Z + cf[3];
     const double v = cf[4] * X + cf[5] * Y + cf[6] * Z + cf[7];
     const double lim = (double)(A - 1);
@@ -371,6 +376,15 @@ int hla_s2g_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_l
     HLA_REQUIRE(lv[l].row0 >= 0 && lv[l].row0 < lv[l].h, "%s: bad row0", who);
     HLA_REQUIRE(lv[l].grd_row_skip >= 0 && lv[l].grd_row_skip <= lv[l].row0, "%s: grd_row_skip must be in [0,row0]", who);
     HLA_REQUIRE((size_t)lv[l].A * lv[l].A * C < (1u << 31), "%s: satellite map too large", who);
+    if (lv[l].depth) {      // args.use_gt_depth (hla.h): KITTI chain only, all of the depth fields together
+      HLA_REQUIRE(!cfg->ford, "%s: level %d: a depth map is not supported with cfg->ford = 1 (models_ford.py has no gt_depth)", who, l);
+      HLA_REQUIRE(lv[l].ray && lv[l].depth_row && lv[l].depth_col && lv[l].depth_h > 0 && lv[l].depth_w > 0,
+                  "%s: level %d: depth needs ray, depth_row, depth_col and depth_h, depth_w > 0", who, l);
+      HLA_REQUIRE((size_t)B * lv[l].depth_h * lv[l].depth_w < (1u << 31), "%s: level %d: depth map too large", who, l);
+    } else {
+      HLA_REQUIRE(!lv[l].ray && !lv[l].depth_row && !lv[l].depth_col && !lv[l].depth_h && !lv[l].depth_w,
+                  "%s: level %d: ray / depth_row / depth_col / depth_h / depth_w given without depth", who, l);
+    }
   }
   return HLA_OK;
 }
@@ -521,7 +535,7 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
     const int l = step_level(k), it = step_iter(k);
     const hla_s2g_level& v = lv[l];
     AccumArgs aa{};
-    aa.sat = v.sat_feat; aa.grd = v.grd_feat; aa.conf = v.grd_conf; aa.xyz = v.xyz; aa.coef = coef; aa.part = part;
+    aa.sat = v.sat_feat; aa.grd = v.grd_feat; aa.conf = v.grd_conf; aa.pts = lm_points_of(v); aa.coef = coef; aa.part = part;
     aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.row0 = v.row0; aa.npix = (v.h - v.row0) * v.w;
     aa.hs = v.h - v.grd_row_skip; aa.rskip = v.grd_row_skip;
     aa.keep = cfg->keep ? cfg->keep + (size_t)k * cfg->keep_stride : nullptr;
@@ -542,7 +556,7 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
       hipStream_t gs = gst[g];
       aa.b0 = gb0[g]; aa.nb = gb0[g + 1] - gb0[g];
       if (count)
-        hipLaunchKernelGGL(lm_inview_kernel, dim3((v.h * v.w + 255) / 256, aa.nb), dim3(256), 0, gs, coef, v.xyz, v.A, v.h * v.w,
+        hipLaunchKernelGGL(lm_inview_kernel, dim3((v.h * v.w + 255) / 256, aa.nb), dim3(256), 0, gs, coef, aa.pts, v.w, v.A, v.h * v.w,
                            in_view + (size_t)k * B, aa.b0);
       const int nblk = aa.xcd_affine ? 8 * ((aa.nb + 7) / 8) * aa.nt : aa.nb * aa.nt;
       hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,

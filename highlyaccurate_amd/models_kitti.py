@@ -67,12 +67,15 @@ class LM_S2GP(S2GPBase):
         """sat_map [B,3,A,A], grd_img_left [B,3,H,W] fp32 in [0,1] on the GPU.
         mode='test'  -> (shift_lat[B], shift_lon[B], theta[B])   (models_kitti.py:1316)
         mode='train' -> the reference's 14-tuple                 (models_kitti.py:1312-1314)
-        ``init_pose`` [B,3] (shift_u, shift_v, heading) is an extension; the reference always starts at 0."""
-        if gt_depth is not None and getattr(self.args, 'use_gt_depth', 0):
-            raise NotImplementedError('projection with a ground-truth depth map (models_kitti.py:741-747) is out of scope')
+        ``init_pose`` [B,3] (shift_u, shift_v, heading) is an extension; the reference always starts at 0.
+        ``gt_depth`` [B,dH,dW] with ``args.use_gt_depth``: every ground pixel is lifted to its camera ray times the depth
+        (nearest-resampled to each level), masked where the depth is -1, instead of onto the flat ground
+        (models_kitti.py:741-748); without the flag, or without a map, it is ignored as in the reference."""
+        if not getattr(self.args, 'use_gt_depth', 0):
+            gt_depth = None
         want_conf = bool(self.using_weight) or mode == 'train'
         trace, grd_confs = self.localise(sat_map, grd_img_left, want_conf, None, level_first, init_pose,
-                                          return_confs=(mode == 'train'))
+                                          return_confs=(mode == 'train'), gt_depth=gt_depth)
         shift_lons, shift_lats, thetas = trace[..., 0], trace[..., 1], trace[..., 2]   # models_kitti.py:1281-1283
         if mode == 'train':
             a = self.args

@@ -65,6 +65,21 @@ def images(seed: int, B: int, grd_hw=(256, 1024), sat_a=512):
     return sat, grd, gt[0], gt[1], gt[2]
 
 
+def gt_depth(B: int, dH: int, dW: int, seed: int, device='cpu', hole_fraction: float = 0.15):
+    """A synthetic ``gt_depth`` [B,dH,dW] fp32 for ``LM_S2GP.forward`` with args.use_gt_depth (no dataset here carries depth):
+    the depth at which the KITTI camera's ray through each pixel meets the flat ground (camera height / |y of K^-1 [u,v,1]|, the
+    camera of models_kitti.py:657-660 rescaled to dH x dW, capped at 200 m around the horizon), times 1 + 0.2 U(0,1) per pixel,
+    with ``hole_fraction`` of the pixels set to -1 (the reference's "no measurement" value, models_kitti.py:746).  Every sample
+    draws its own noise and holes from ``numpy.random.RandomState(seed)``, in sample order."""
+    rs = np.random.RandomState(seed)
+    fy, cy = 482.7076 * dH / 256.0, 125.0034 * dH / 256.0
+    y = (np.arange(dH, dtype=np.float64) - cy) / fy
+    plane = np.minimum(1.65 / np.maximum(np.abs(y), 1e-6), 200.0)[None, :, None]
+    d = plane * (1.0 + 0.2 * rs.random_sample((B, dH, dW)))
+    d[rs.random_sample((B, dH, dW)) < hole_fraction] = -1.0
+    return torch.from_numpy(d.astype(np.float32)).to(device)
+
+
 def fixture_sample_idx(numel: int, salt: int, n: int = 64):
     """The deterministic sample positions of the committed feature / gradient fixtures (tests/make_idx.py, oracle/make_golden.py)."""
     return np.random.RandomState(1000 + salt).randint(0, numel, size=n)

@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 25
+#define HLA_ABI_VERSION 26
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -310,6 +310,19 @@ typedef struct hla_s2g_level {
                             reinterpret fp16 bits; it is only for bf16 maps a caller made itself).  Inference in the
                             reduced-precision modes: half the bytes through the HBM-bound LM loop; all LM arithmetic stays
                             fp32 / fp64 */
+  /* args.use_gt_depth with a depth map (models_kitti.py:741-748; hla_s2g_lm_solve / _bwd and their workspace functions, KITTI
+     chain only).  All six NULL / 0: the flat-ground projection through `xyz`, as before.  With `depth` set, the point of pixel
+     (r, c) of sample b is  ray[r,c,:] * depth[b, depth_row[r], depth_col[c]]  -- three fp32 products, then used as the table
+     entry is -- and its ground mask is  depth != -1  and nothing else: a depth of 0 (the point at the camera) and a negative
+     depth other than -1 (a point behind the camera) take part; the z > 0 rule of `xyz` is NOT applied.  `xyz` is not read
+     then (it may stay set); row0 / grd_row_skip keep their meaning; count_in_view counts on the lifted points.  No gradient is
+     taken w.r.t. the depth.  hla_g2s_* and cfg->ford = 1 refuse a non-NULL depth. */
+  const float* ray;      /* [h,w,3] fp32: K^-1 [u,v,1], the `xyz_w` of grd_img2cam (models_kitti.py:673) at this level's size */
+  const float* depth;    /* [B,depth_h,depth_w] fp32, one map per sample; -1 marks a hole */
+  const int* depth_row;  /* [h] int32 in [0,depth_h): source row of level row r under F.interpolate(depth, (h, w)) (nearest) */
+  const int* depth_col;  /* [w] int32 in [0,depth_w): source column of level column c.  Both are the caller's to make and to keep
+                            inside their ranges (device arrays: the library cannot check them) */
+  int depth_h, depth_w;
 } hla_s2g_level;
 
 typedef struct hla_s2g_config {

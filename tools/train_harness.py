@@ -71,7 +71,7 @@ def test1(net, args, save_path, best_rank_result, epoch, device, gen, rank=0):
     t0 = time.time()
     for _ in range(args.test_batches):
         sat_map, grd_left_imgs, (gt_shift_u, gt_shift_v, gt_heading) = synthetic_batch(args, device, gen)
-        shifts_lat, shifts_lon, theta = net(sat_map, grd_left_imgs, mode='test')
+        shifts_lat, shifts_lon, theta = net(sat_map, grd_left_imgs, mode='test', gt_depth=synthetic_depth(args, device, gen))
         shifts = torch.stack([shifts_lat, shifts_lon], dim=-1)
         headings = theta.unsqueeze(dim=-1)
         gt_shift = torch.cat([gt_shift_v, gt_shift_u], dim=-1)
@@ -111,6 +111,16 @@ def synthetic_batch(args, device, gen):
     grd = torch.rand(B, 3, args.grd_h, args.grd_w, generator=gen).to(device)
     gt = [(torch.rand(B, 1, generator=gen) * 2 - 1).to(device) for _ in range(3)]
     return sat, grd, gt
+
+
+def synthetic_depth(args, device, gen):
+    """--use_gt_depth 1: a depth map per sample at the ground image's size (synthetic.gt_depth; no dataset here provides depth:
+    the reference's drivers never pass one, train_kitti.py:357,49), seeded from the batch generator; else None."""
+    if not args.use_gt_depth:
+        return None
+    from highlyaccurate_amd import synthetic
+    seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=gen))
+    return synthetic.gt_depth(args.batch_size, args.grd_h, args.grd_w, seed, device)
 
 
 def main(argv=None):
@@ -154,7 +164,7 @@ def main(argv=None):
             loss, loss_decrease, shift_lat_decrease, shift_lon_decrease, thetas_decrease, loss_last, \
                 shift_lat_last, shift_lon_last, theta_last, L1, L2, L3, L4, grd_conf_list = \
                 net(sat_map, grd_left_imgs, gt_shift_u, gt_shift_v, gt_heading, mode='train', file_name=None,
-                    loop=Loop, level_first=args.level_first)
+                    gt_depth=synthetic_depth(args, device, gen), loop=Loop, level_first=args.level_first)
             loss.backward()
             optimizer.step()
             optimizer.zero_grad()
