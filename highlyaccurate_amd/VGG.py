@@ -208,7 +208,7 @@ def vgg_forward_pair_nhwc(modules, xs, first_row8=(0, 0), feat16: bool = False):
 @_lib.on_device(lambda module, ctx, *a, **k: ctx['x'])
 def vgg_backward_nhwc(module: 'VGGUnet', ctx: dict, d_feats, confs=None, d_confs=None, scale_invariant: bool = False,
                       first_row8: int = 0, flat: bool = False, dense: bool = False, stats: dict = None,
-                      wgrad_two_phase: int = 0):
+                      wgrad_two_phase: int = 0, workspace: torch.Tensor = None):
     """Backward of ``vgg_forward_nhwc(..., defer_norm=True, save_for_backward=True)``.
     d_feats[l]: NHWC fp32 gradient w.r.t. the L2-normalised map l.  Returns {parameter name: gradient} for the
     22 tensors that receive one at level 3 (conv0..conv14 weights+biases, conv_dec1/2 weights), plus the conf head weights
@@ -222,7 +222,10 @@ def vgg_backward_nhwc(module: 'VGGUnet', ctx: dict, d_feats, confs=None, d_confs
     ``stats`` (a dict, diagnostics: costs a device synchronisation) receives 'live_tiles' / 'total_tiles' per sample, summed over
     the data- and weight-gradient launches; both 0 when the call took the dense walk.
     ``wgrad_two_phase`` (``args.wgrad_two_phase`` on the models; A/B and tests): bit 0 HLA_VGG_BWD_WGRAD_TWO_PHASE, bit 1
-    HLA_VGG_BWD_WGRAD0_UNFUSED (conv0's weight gradient from a stored map of conv2's data gradient, as before round 6)."""
+    HLA_VGG_BWD_WGRAD0_UNFUSED (conv0's weight gradient from a stored map of conv2's data gradient, as before round 6).
+    ``workspace`` (tests, diagnostics): a caller-allocated uint8 tensor on the input's device of at least
+    ``hla_vgg_bwd_workspace_bytes[_flags]`` bytes, used in place of the internal allocation -- the caller can pre-fill it and
+    read every intermediate gradient map after the call (the layout: ``BwdPlan``, csrc/vgg_backward.hip)."""
     lib = _lib.load()
     x, dt = ctx['x'], ctx['dt']
     if x._version != ctx.get('x_version', x._version):
@@ -278,7 +281,14 @@ def vgg_backward_nhwc(module: 'VGGUnet', ctx: dict, d_feats, confs=None, d_confs
     fold = bool(getattr(module, 'folded', False))
     nbytes = lib.hla_vgg_bwd_workspace_bytes_flags(B, H, W, L, dt, _lib.HLA_VGG_BWD_FOLD_DECODER) if fold \
         else lib.hla_vgg_bwd_workspace_bytes(B, H, W, L, dt)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    if workspace is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    else:
+        ws = workspace
+        if ws.dtype != torch.uint8 or ws.device != x.device or not ws.is_contiguous():
+            raise ValueError('workspace must be a contiguous uint8 tensor on the device of the input')
+        if ws.numel() < nbytes:
+            raise ValueError(f'workspace too small: {ws.numel()} bytes, the backward needs {nbytes}')
     rc = lib.hla_vgg_backward(_lib.ptr(x), ctx.get('x_plane', 0), C.byref(prm), _lib.ptr(cache['buf']), _lib.ptr(ctx['ws']), fp, _lib.ptr(ctx['inv_norm']),
                               dp, cp, dcp, C.byref(gs), _lib.ptr(ws), nbytes, B, H, W, L, dt,
                               (_lib.HLA_VGG_BWD_SCALE_INVARIANT if scale_invariant else 0)

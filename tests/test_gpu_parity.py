@@ -1231,8 +1231,10 @@ def test_ablation_optimisers_train_step_vs_oracle_autograd_small(opt):
 
 # bf16: the one-hop gradient (conv_dec2.3) agrees to 0.5 %; deeper layers differ by up to ~17 % in relative L2 because
 # bf16 rounding of the FORWARD flips max-pool argmax / ReLU signs of near-ties (a flipped argmax moves a gradient
-# element to a neighbouring pixel).  That is a property of bf16 training, not of the backward kernels, whose logic
-# the fp32 run pins to 2e-6; the bf16 bound below only guards against gross breakage.
+# element to a neighbouring pixel).  That is a property of bf16 training, not of the backward kernels.  The fp32 run pins
+# the layer walk of vgg_backward_t to 2e-6, NOT the 16-bit instantiations of the kernels (their loaders, stagers and
+# epilogues): those are checked launch by launch against fp64 in test_vgg_backward_16bit_vs_fp64.py; the bf16 / fp16
+# bounds below only guard against gross breakage.
 @pytest.mark.parametrize('precision,tol', [('fp32', 2e-4), ('bf16', 0.3), ('fp16', 0.1)])
 def test_vgg_backward_small_vs_oracle_autograd(precision, tol):
     """hla_vgg_backward (L2-norm bwd, dgrad convs with fused ReLU mask / fan-in / unpool / upsample-sum, MFMA wgrad,

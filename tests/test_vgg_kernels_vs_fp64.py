@@ -10,7 +10,9 @@ Shapes (B, H, W) -- H and W multiples of 8 -- and the edge each one hits:
 
 fp32 / fp16x3 run forward and backward against fp64 (the oracle and its autograd); bf16 / fp16 run the forward against
 ``vgg_round16.forward`` -- the same fp64 arithmetic with the kernels' 16-bit rounding points -- see ``test_forward_16bit``;
-their backward is checked for agreement between its two weight-gradient groupings (``test_backward_16bit_wgrad_groupings_agree``).
+here their backward is only checked for agreement between its two weight-gradient groupings
+(``test_backward_16bit_wgrad_groupings_agree``): what it computes is checked launch by launch against fp64 in
+``test_vgg_backward_16bit_vs_fp64.py`` (``vgg_bwd16_ref.py``).
 The references of a case are computed once per session and shared by every precision (``_REFS``).
 """
 import numpy as np
