@@ -18,7 +18,8 @@ bool hla_prof_on();
 
 // per-wave cycle stamps of ONE conv3x3_kernel launch (tooling builds only: python -m highlyaccurate_amd.build --out=libhla_stamps.so
 // -DHLA_CONV_STAMPS=1; tools/probes/conv_stamps.py): launch_conv hands `buf` to the launch whose ordinal since the last
-// hla_debug_conv_stamps call equals `want`; every wave writes HLA_STAMP_N 64-bit words at ((blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave).
+// hla_debug_conv_stamps call equals `want`; every wave writes HLA_STAMP_N 64-bit words at (blockIdx.x * 4 + wave);
+// the launch is a 1-D grid of grid_x (tiles) * grid_y (output-channel blocks) workgroups.
 #ifndef HLA_CONV_STAMPS
 #define HLA_CONV_STAMPS 0
 #endif

@@ -27,6 +27,7 @@
 // conv02_kernel -- conv0 (3->64 on the NCHW fp32 input, K = 27 padded to 32) computed by MFMA directly into the
 //   LDS halo tile of conv2, then conv2 + pool: the 64-channel full-resolution map never touches HBM.
 #include "common.h"
+#include "conv_block_map.h"
 #include <type_traits>
 
 typedef __bf16 bf16;
@@ -223,14 +224,6 @@ __device__ __forceinline__ float wave_max_f32(float v) {
   return v;
 }
 
-// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Remap the linear id so that every XCD works on
-// a CONTIGUOUS run of tiles: vertically adjacent tiles, which share two halo rows, then hit the same L2.  Bijective for
-// any grid size (cdna_hip_programming.md "XCD swizzle must be bijective").  Measured: +1 % in one A/B, within noise in the next.
-__device__ __forceinline__ int xcd_contiguous(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 struct ConvArgs {
   const void* src1;   // NHWC T, C1 channels; at half resolution when up1
   const void* src2;   // NHWC T, C2 channels (virtual concat after src1), or null
@@ -239,7 +232,7 @@ struct ConvArgs {
   void* out_act;      // NHWC T [B,Ho,Wo,Cout] (post-ReLU when relu_act) or null
   float* out_raw;     // NHWC fp32 (pre-ReLU) or null; T elements instead when raw16 (HLA_VGG_FEAT16)
   int raw16;
-  double* sumsq;      // [B, tiles_per_img * gridDim.y] sum of squares of out_raw, or null
+  double* sumsq;      // [B, tiles_per_img * cout blocks] sum of squares of out_raw, or null
   int C1, C2, up1;
   int B, H, W, Cout;
   int relu_act;
@@ -272,13 +265,16 @@ struct ConvArgs {
   unsigned long long* stamps;       // tooling build: per-wave cycle stamps of this launch, or null (common.h)
 #endif
 };
+// Output-channel blocks of a conv3x3 launch (conv_plan's gy): a workgroup is two waves wide in channels, 64 * NT of them.  The
+// 32-channel wave tile only serves Cout == 64, one block: a constant there, so those kernels keep their plain tile decode.
+template <int NT> __host__ __device__ __forceinline__ int conv_cout_blocks(const ConvArgs& a) { return NT == 1 ? 1 : a.Cout / (64 * NT); }
 #if HLA_CONV_STAMPS
 // s_memtime (shader-clock cycles), HW_ID / XCC_ID: which CU / SIMD / slot the wave ran on
 #define HLA_STAMP(K) do { if (a.stamps) { const unsigned long long ts_ = __builtin_readcyclecounter(); \
-    if ((threadIdx.x & 63) == 0) a.stamps[((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * HLA_STAMP_N + (K)] = ts_; } } while (0)
+    if ((threadIdx.x & 63) == 0) a.stamps[((size_t)blockIdx.x * 4 +(threadIdx.x >> 6)) * HLA_STAMP_N + (K)] = ts_; } } while (0)
 #define HLA_STAMP_HWID() do { if (a.stamps && (threadIdx.x & 63) == 0) { \
     const unsigned long long hw_ = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4), xc_ = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20); \
-    a.stamps[((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * HLA_STAMP_N + 7] = hw_ | (xc_ << 32); } } while (0)
+    a.stamps[((size_t)blockIdx.x * 4 +(threadIdx.x >> 6)) * HLA_STAMP_N + 7] = hw_ | (xc_ << 32); } } while (0)
 #else
 #define HLA_STAMP(K) do {} while (0)
 #define HLA_STAMP_HWID() do {} while (0)
@@ -470,7 +466,7 @@ __device__ __forceinline__ void conv_epilogue(typename AccMap<SHAPE>::Tile (&acc
                                               int cb, float* red, char* stage, float dsc = 1.f,
                                               PixBox addb = PixBox{0, 1 << 30, 0, 1 << 30},
                                               const float4* prebias = nullptr,        // [NT * 4] bias values the caller already holds
-                                              int blk = 0, int nblk = 1) {            // the workgroup's id / count along x in its launch segment (sumsq slot)
+                                              int blk = 0, int nblk = 1) {            // the workgroup's id / count in its launch segment (sumsq slot)
   using RawT = std::conditional_t<R16, f16, float>;      // 16-bit raw maps are fp16 also in bf16 mode: 11 significand bits for the LM loop
   constexpr bool GEN = EPI == EPI_GENERIC, RAW = EPI == EPI_ACT_RAW || EPI == EPI_ACT_RAW_NOBIAS, DG = EPI == EPI_DGRAD;
   // 16-bit types: the kernels START their accumulators at the bias (conv3x3_kernel / conv02_kernel), nothing to add here.
@@ -701,8 +697,9 @@ __device__ __forceinline__ void conv_epilogue(typename AccMap<SHAPE>::Tile (&acc
     __syncthreads();
     if (tid == 0) {
       if (has_sumsq) {
-        const int np = a.tiles_x * a.tiles_y * gridDim.y;
-        const int tile = (xcd_contiguous(blk, nblk) % (a.tiles_x * a.tiles_y)) * gridDim.y + blockIdx.y;
+        // the remapped id is (b * tiles + tile) * gy + cout block (conv_block_map): its remainder is the slot tile * gy + cout block
+        const int np = a.tiles_x * a.tiles_y * conv_cout_blocks<NT>(a);
+        const int tile = xcd_contiguous(blk, nblk) % np;
         a.sumsq[(size_t)b * np + tile] = ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]);
       }
       if (want_max) {    // non-negative floats order like their bit patterns; the plain read only filters (a stale value costs one
@@ -1014,9 +1011,10 @@ __device__ __forceinline__ void stage_mma(typename AccMap<SHAPE>::Tile (&acc)[MT
 // of a piece next to the piece and applies them when the piece is WRITTEN to LDS -- masking right behind the load put an
 // s_waitcnt vmcnt(0) after every single piece, six full memory round trips per stage in the middle of the MFMA stream.
 // SHAPE: the MFMA shape of the main loop (16-bit plain forward kernels only; launch_conv picks it per kernel class).
-// The body takes the workgroup's id and the workgroup count along x as arguments: a plain launch passes blockIdx.x / gridDim.x
-// (conv3x3_kernel), a two-segment launch the ids local to the workgroup's segment (conv3x3_pair_kernel below).  They are all the
-// kernel knows of its place in the grid: the XCD-contiguous map, the (b, ty, tx) decode and the sum-of-squares slot use them.
+// The grid is 1-D, tiles x output-channel blocks (conv_block_map.h).  The body takes the workgroup's id and the workgroup count as
+// arguments: a plain launch passes blockIdx.x / gridDim.x (conv3x3_kernel), a two-segment launch the ids local to the workgroup's
+// segment (conv3x3_pair_kernel below).  They are all the kernel knows of its place in the grid: the XCD-contiguous map, the
+// (b, ty, tx, channel block) decode and the sum-of-squares slot use them.
 template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16>
 __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, const int nblk) {
   static_assert(WM * WN == 4, "4 waves per block");
@@ -1046,7 +1044,8 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), wm = wv / WN, wn = wv % WN;
   // source / fan-in bounds: the image (and the caller's static first rows), narrowed by the device-side boxes if there are any
   const int sy0 = a.src_row_lo, sy1 = a.H;
-  int tx, ty, b;
+  int tx, ty, b, cblk;
+  const int gy = conv_cout_blocks<NT>(a);      // workgroup-uniform: the map below is scalar arithmetic
   // column interval of the source per halo row class: top halo row / the tile's own rows / bottom halo row
   // (six scalars, not arrays: once the halo row of a piece is a run-time value the compiler turns a select over array elements
   // into an indexed load from a stack copy of the array)
@@ -1058,8 +1057,10 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
     // 160 -> 145 us for half the tiles.)
     const ConvDyn& d = *(const ConvDyn*)(a.dyn + a.dyn_desc);
     const int nl = d.n_live, nlive = nl * a.B;
-    if (blk >= nlive) return;
-    int bid = xcd_contiguous(blk, nlive);
+    if (blk >= nlive * gy) return;
+    const ConvBlock m = conv_block_map(blk, nlive * gy, gy);
+    const int bid = m.tile;
+    cblk = __builtin_amdgcn_readfirstlane(m.cb);      // (n_live is a load: keep the weight and bias addresses scalar all the same)
     b = bid / nl;
     const int e = a.dyn[d.list + bid % nl];
     ty = e >> 16; tx = e & 0xffff;
@@ -1071,7 +1072,9 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
       sb.lo2 = a.dyn[d.src_bands + 2 * b2] << sh; sb.hi2 = min(a.dyn[d.src_bands + 2 * b2 + 1] << sh, a.W);
     }
   } else {
-    int bid = xcd_contiguous(blk, nblk);
+    const ConvBlock m = conv_block_map(blk, nblk, gy);
+    int bid = m.tile;
+    cblk = m.cb;
     tx = bid % a.tiles_x; bid /= a.tiles_x;
     ty = bid % a.tiles_y;
     b = bid / a.tiles_y;
@@ -1234,7 +1237,7 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
 #undef HLA_DMA_STEP
   };
 
-  const int ntg0 = (blockIdx.y * WN + wn) * NT;     // first global 32-channel output tile of this wave
+  const int ntg0 = (cblk * WN + wn) * NT;    // first global 32-channel output tile of this wave
   // The accumulators start at the bias (16-bit types; it commutes with the max-pool, and the epilogues then have neither
   // the 8 x NT bias registers nor the adds); the 4-byte types add it in the epilogue (split mode: after its power-of-two descale).
   typename M::Tile acc[MT][NT];
@@ -1349,8 +1352,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
 }
 
 // ---- two-segment launches (inference, vgg.hip: the same layer of the two extractors in ONE grid).  The kernarg holds two
-// argument blocks and the first segment's workgroup count n0; workgroups [0, n0) along x are segment 0, the rest segment 1, and
-// blockIdx.y (the cout block) is shared.  A workgroup's segment is uniform, so its argument block is fetched with scalar loads
+// argument blocks and the first segment's workgroup count n0 (its tiles x cout blocks); workgroups [0, n0) are segment 0, the rest
+// segment 1, each with its own XCD-contiguous map.  A workgroup's segment is uniform, so its argument block is fetched with scalar loads
 // from ONE selected kernarg address: selecting between the two blocks of a by-value struct field by field keeps both live, and
 // indexing the struct dynamically makes the compiler copy it to the stack.
 template <typename A> struct PairArgs { A s[2]; int n0; };
@@ -2055,10 +2058,10 @@ template <typename T, int MT, int NT, bool POOL, int WD, bool UNPOOL, int SHAPE,
 static void conv_dispatch(hipStream_t st, const ConvArgs& a, const ConvPlan& p, const ConvArgs& a2, const ConvPlan& p2) {
   if constexpr (PAIR) {
     static_assert(!UNPOOL, "two-segment launches: forward inference forms only");
-    PairArgs<ConvArgs> pa{{a, a2}, p.gx};
-    hipLaunchKernelGGL((conv3x3_pair_kernel<T, MT, NT, 2, 2, POOL, WD, SHAPE>), dim3(p.gx + p2.gx, p.gy), dim3(256), 0, st, pa);
+    PairArgs<ConvArgs> pa{{a, a2}, p.gx * p.gy};
+    hipLaunchKernelGGL((conv3x3_pair_kernel<T, MT, NT, 2, 2, POOL, WD, SHAPE>), dim3((p.gx + p2.gx) * p.gy), dim3(256), 0, st, pa);
   } else {
-    hipLaunchKernelGGL((conv3x3_kernel<T, MT, NT, 2, 2, POOL, WD, UNPOOL, SHAPE>), dim3(p.gx, p.gy), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((conv3x3_kernel<T, MT, NT, 2, 2, POOL, WD, UNPOOL, SHAPE>), dim3(p.gx * p.gy), dim3(256), 0, st, a);
   }
 }
 // PAIR: `a2` is the same layer of a second network (same Cout, pooling and kernel instantiation: the caller has checked that both
