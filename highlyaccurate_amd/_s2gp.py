@@ -276,6 +276,7 @@ class S2GPBase(nn.Module):
         self.last_normal_eq = None
         self.last_keep = None
         self.keep_normal_eq = False
+        self.last_search = None      # forward_search: cost, sums, start_index, traces, final_cost, best of the last call
 
     # -- geometry tables ---------------------------------------------------------------------
     def xyz_tables(self, grd_H: int, grd_W: int, device):
@@ -546,6 +547,68 @@ class S2GPBase(nn.Module):
                                'from its last step to an earlier one; the result is not valid (run without args.deterministic_backward)')
         return d_sat, d_grd, d_conf, d_lambda[:3]
 
+    @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
+    def score_poses(self, sat_feats, grd_feats, grd_confs, grd_hw, poses, level, extra=None, sat_inv_norm=None, grd_inv_norm=None):
+        """The LM objective at given poses, on feature maps extracted once (``hla_s2g_pose_score``, include/hla.h): low-level like
+        ``lm_solve``, with the same map arguments.  ``poses`` [K,3] (shared by the samples) or [B,K,3], (shift_u, shift_v, theta)
+        in normalised units; ``level`` indexes the lists.  Returns (cost [B,K] fp32, sums [B,K,8] fp64): sum s^2, sum g^2,
+        sum s g, the same three weighted, pixels in view, pixels with the ground mask."""
+        B, L = sat_feats[0].shape[0], len(sat_feats)
+        p = _poses_arg(poses, B)
+        if not 0 <= int(level) < L:
+            raise ValueError(f'level must be in [0, {L}), got {level}')
+        _lib.require_gpu(sat_feats[0], 'sat_feats')
+        lib = _lib.load()
+        dev = sat_feats[0].device
+        cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, 0, sat_inv_norm, grd_inv_norm)
+        p = p.to(dev).contiguous()
+        K = p.shape[1]
+        one = C.byref(lv[int(level)])
+        cost = torch.empty(B, K, device=dev, dtype=torch.float32)
+        sums = torch.empty(B, K, 8, device=dev, dtype=torch.float64)
+        nbytes = lib.hla_s2g_pose_score_workspace_bytes(C.byref(cfg), one, B, K)
+        if nbytes == 0:
+            _lib.check(-1, 'hla_s2g_pose_score_workspace_bytes')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.hla_s2g_pose_score(C.byref(cfg), one, _lib.ptr(R_FL), _lib.ptr(T_FL), _lib.ptr(p), K, _lib.ptr(sums), _lib.ptr(cost),
+                                    _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
+        _lib.check(rc, 'hla_s2g_pose_score')
+        return cost, sums
+
+    @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
+    def _search(self, sat_map, grd_img, extra, candidates, top_m, score_level, min_in_view, level_first):
+        """``forward_search`` of both models: extract once, score the candidates at ``score_level``, run the LM loop from the
+        ``top_m`` best eligible ones, keep the final pose that scores best at the finest level.  -> trace-ordered pose [B,3]."""
+        if getattr(self.args, 'dropout', 0):
+            raise NotImplementedError('forward_search with args.dropout: a pose is scored on every pixel, the dropout loop on a '
+                                      'random half -- their objectives differ')
+        _lib.require_gpu(sat_map, 'sat_map')
+        _lib.require_gpu(grd_img, 'grd_img')
+        if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
+                or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
+            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
+                             f'and {tuple(grd_img.shape)}')
+        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
+        B, M = sat_map.shape[0], int(top_m)
+        cand = _poses_arg(candidates, B, 'candidates').to(sat_map.device)
+        if not 1 <= M <= cand.shape[1]:
+            raise ValueError(f'top_m must be in [1, {cand.shape[1]}] (the number of candidates), got {top_m}')
+        with torch.no_grad():
+            sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, bool(self.using_weight), False)
+            hw = grd_img.shape[-2:]
+            score = lambda poses, level: self.score_poses(sat_feats, grd_feats, grd_confs, hw, poses, level, extra, sat_inv, grd_inv)
+            cost, sums = score(cand, score_level)
+            start_index = torch.topk(eligible_cost(cost, sums, min_in_view), M, dim=1, largest=False, sorted=True).indices
+            starts = cand.gather(1, start_index[:, :, None].expand(-1, -1, 3))
+            traces = torch.stack([self.lm_solve(sat_feats, grd_feats, grd_confs, hw, extra, level_first, starts[:, m].contiguous(),
+                                                sat_inv, grd_inv) for m in range(M)], dim=1)
+            finals = traces[:, :, -1, -1, :].contiguous()
+            final_cost, _ = score(finals, len(sat_feats) - 1)
+            best = final_cost.argmin(dim=1)
+            pose = finals.gather(1, best[:, None, None].expand(-1, 1, 3))[:, 0]
+        self.last_search = dict(cost=cost, sums=sums, start_index=start_index, traces=traces, final_cost=final_cost, best=best)
+        return pose
+
     def _features(self, sat_map, grd_img, want_conf, return_confs):
         """Both extractors of the inference path: (sat_feats, sat_inv, grd_feats, grd_confs, grd_inv), normalisation deferred."""
         # Reduced-precision inference modes: the LM loop reads fp16 feature maps (written saturating by the three feature
@@ -623,6 +686,45 @@ class S2GPBase(nn.Module):
         trace = self.lm_solve(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], extra, level_first, init_pose,
                               sat_inv, grd_inv, gt_depth=gt_depth)
         return trace, grd_confs
+
+
+def pose_grid(n_u: int, n_v: int, n_theta: int, span=(1., 1., 1.)):
+    """Candidate poses for ``forward_search``: a centred lattice over [-span, span] per component, in the normalised units of the
+    pose (1 = shift_range / rotation_range), [n_u * n_v * n_theta, 3] fp32 (shift_u, shift_v, theta).  The counts are odd so that
+    the zero pose is on the lattice; it is candidate 0, the others follow with shift_u outermost and theta innermost."""
+    axes = []
+    for name, n, s in zip(('n_u', 'n_v', 'n_theta'), (n_u, n_v, n_theta), span):
+        if int(n) != n or n < 1 or n % 2 == 0:
+            raise ValueError(f'{name} must be a positive odd count (the lattice is centred on the zero pose), got {n}')
+        half = (int(n) - 1) // 2
+        axes.append(torch.tensor([float(s) * i / half if half else 0.0 for i in range(-half, half + 1)], dtype=torch.float32))
+    grid = torch.cartesian_prod(*axes).reshape(-1, 3)
+    zero = (len(axes[0]) // 2 * len(axes[1]) + len(axes[1]) // 2) * len(axes[2]) + len(axes[2]) // 2
+    order = [zero] + [i for i in range(grid.shape[0]) if i != zero]
+    return grid[order].contiguous()
+
+
+def eligible_cost(cost, sums, min_in_view):
+    """The ranking rule of ``forward_search``: a candidate is eligible when its pixels in view (``sums[..., 6]``) reach
+    ``min_in_view`` times the sample's maximum over its candidates; the others get +inf.  (A pose with nothing in view scores 1,
+    below the ~2 of a mismatch, and would otherwise win.)  A sample without any eligible candidate keeps candidate 0.
+    cost [B,K], sums [B,K,8] -> [B,K] in cost's dtype."""
+    in_view = sums[..., 6]
+    ok = in_view >= float(min_in_view) * in_view.max(dim=1, keepdim=True).values
+    out = torch.where(ok, cost, torch.full_like(cost, float('inf')))
+    none = ~ok.any(dim=1)
+    out[:, 0] = torch.where(none, torch.zeros_like(cost[:, 0]), out[:, 0])
+    return out
+
+
+def _poses_arg(poses, B: int, name: str = 'poses'):
+    """[K,3] (shared) or [B,K,3] -> [B,K,3] fp32, K >= 1."""
+    p = torch.as_tensor(poses, dtype=torch.float32)
+    if p.dim() == 2 and p.shape[1] == 3 and p.shape[0] >= 1:
+        return p[None].expand(B, -1, -1)
+    if p.dim() == 3 and p.shape[0] == B and p.shape[2] == 3 and p.shape[1] >= 1:
+        return p
+    raise ValueError(f'{name} must be [K,3] or [B,K,3] with B = {B} and K >= 1, got {tuple(p.shape)}')
 
 
 def draw_reinit(n_steps: int, B: int, device):

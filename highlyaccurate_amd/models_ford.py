@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch
 
-from ._s2gp import S2GPBase, loss_func, loss_from_trace  # noqa: F401
+from ._s2gp import S2GPBase, loss_func, loss_from_trace, pose_grid  # noqa: F401
 
 
 class LM_S2GP_Ford(S2GPBase):
@@ -32,3 +32,12 @@ class LM_S2GP_Ford(S2GPBase):
         if torch.is_grad_enabled():
             res = tuple(r.clone().requires_grad_(True) for r in res)
         return res
+
+    def forward_search(self, sat_map, grd_img_left, satmap_sidelength_meters, R_FL, T_FL, candidates, top_m=1, score_level=0,
+                       min_in_view=0.5, level_first=0):
+        """``LM_S2GP.forward_search`` on the Ford chain: the candidates are scored on feature maps extracted once, the LM loop runs
+        from the ``top_m`` best eligible ones and the final pose that scores best at the finest level is returned as the tuple
+        of ``forward(mode='test')``: (shift_u[B], shift_v[B], theta[B]).  ``last_search`` keeps the scores and the traces."""
+        extra = dict(R_FL=R_FL, T_FL=T_FL, side_m=float(satmap_sidelength_meters))
+        pose = self._search(sat_map, grd_img_left, extra, candidates, top_m, score_level, min_in_view, level_first)
+        return pose[:, 0], pose[:, 1], pose[:, 2]

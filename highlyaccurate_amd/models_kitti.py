@@ -10,7 +10,7 @@ import torch
 
 from . import _orien
 from ._g2sp import LM_G2SP  # noqa: F401  (models_kitti.py:22-499)
-from ._s2gp import S2GPBase, loss_func, loss_from_trace  # noqa: F401  (loss_func re-exported like the reference module)
+from ._s2gp import S2GPBase, loss_func, loss_from_trace, pose_grid  # noqa: F401  (loss_func re-exported like the reference module)
 
 
 class LM_S2GP(S2GPBase):
@@ -90,3 +90,18 @@ class LM_S2GP(S2GPBase):
             # train_kitti.py:63-64 calls .backward() on the test outputs "to release the graph"
             res = tuple(r.clone().requires_grad_(True) for r in res)
         return res
+
+    def forward_search(self, sat_map, grd_img_left, candidates, top_m=1, score_level=0, min_in_view=0.5, level_first=0,
+                       gt_depth=None):
+        """A pose search around the LM loop (an extension; the reference starts its loop at the zero pose).  The features are
+        extracted once (the mode='test' path); ``candidates`` -- [K,3] shared by the samples or [B,K,3], (shift_u, shift_v,
+        heading) in normalised units, e.g. ``pose_grid(5, 5, 5)`` -- are scored at level ``score_level`` with the loop's own
+        objective (``score_poses``); the ``top_m`` best of those that keep at least ``min_in_view`` of the sample's best pixel
+        count in view start one LM loop each (each draws its own re-initialisation values: ``top_m`` times the RNG consumption
+        of ``forward``), and the final pose that scores best at the finest level is returned, as the tuple of
+        ``forward(mode='test')``: (shift_lat[B], shift_lon[B], theta[B]).  Always without gradients; no host sync.
+        ``last_search`` keeps cost [B,K], sums [B,K,8], start_index [B,M], traces [B,M,N,L,3], final_cost [B,M], best [B]."""
+        if gt_depth is not None and getattr(self.args, 'use_gt_depth', 0):
+            raise NotImplementedError('forward_search with a depth map: depth-lifted pose scoring is not built')
+        pose = self._search(sat_map, grd_img_left, None, candidates, top_m, score_level, min_in_view, level_first)
+        return pose[:, 1], pose[:, 0], pose[:, 2]

@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 26
+#define HLA_ABI_VERSION 27
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -377,6 +377,33 @@ size_t hla_s2g_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* l
 int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* levels, const float* R_FL,
                      const float* T_FL, const float* pose0, const float* rand_uv, float* trace,
                      double* normal_eq, void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * Pose scoring (no reference function: the objective of LM_update, models_kitti.py:982-996 / models_ford.py:414-430, read back
+ * at given poses).  For ONE level, B samples and K candidate poses per sample, without Jacobians.  Over the pixels of rows
+ * row0..h-1 of the level's ground map, for sample b and hypothesis k:
+ *   s = the bilinearly sampled satellite feature x (ground mask x in-bounds), the weights of the LM loop's own sampling
+ *   g = the ground feature x ground mask
+ *   w = grd_conf x ground mask iff cfg->using_weight, else the ground mask
+ *   (both maps times their *_inv_norm when the level carries them: the sums are rescaled in the closing pass, like normal_eq)
+ * sums [B,K,8] fp64 out:
+ *   [0] sum s^2   [1] sum g^2   [2] sum s g   [3] sum w s^2   [4] sum w g^2   [5] sum w s g
+ *   [6] pixels of those rows with the ground mask set AND inside the satellite map (an exact integer)
+ *   [7] pixels of those rows with the ground mask set
+ *   without using_weight, [3..5] are bitwise copies of [0..2]
+ * cost [B,K] fp32 out: with ns = max(sqrt(sums[0]), 1e-6), ng = max(sqrt(sums[1]), 1e-6),
+ *   sums[3]/ns^2 + sums[4]/ng^2 - 2 sums[5]/(ns ng)  =  sum w (s/ns - g/ng)^2, formed in fp64 and rounded once.  In [0, 4]; a pose
+ *   with nothing in view scores sum w g^2 / ng^2 (1 without weights), BELOW the ~2 of a mismatch: rank with sums[6] at hand
+ * cfg      read: ford, using_weight, shift_range_lat, shift_range_lon, rotation_range.  cfg->keep must be NULL
+ * level    ONE hla_s2g_level; depth must be NULL (depth-lifted scoring is not built); feat_dtype HLA_F32 / HLA_F16 / HLA_BF16;
+ *          C in {16, 64, 128, 256}; row0 / grd_row_skip as in hla_s2g_lm_solve
+ * R_FL, T_FL  Ford only, else NULL;  poses [B,K,3] fp32 (shift_u, shift_v, theta), normalised units;  K >= 1
+ * Two launches; per-tile fp32 partials in the workspace, reduced in a fixed order in fp64.  The tile size follows from the level
+ * alone: sums and cost of (b, k) do not depend, bit for bit, on the other hypotheses, on k's position, on K, on B or on repeats. */
+size_t hla_s2g_pose_score_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K);
+int hla_s2g_pose_score(const hla_s2g_config* cfg, const hla_s2g_level* level, const float* R_FL, const float* T_FL,
+                       const float* poses, int K, double* sums, float* cost, void* workspace, size_t workspace_bytes, int B,
+                       hla_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Backward of the LM pose loop (what autograd does in the reference through models_kitti.py:1176-1283,
