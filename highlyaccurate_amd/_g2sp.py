@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import _lib, utils
-from ._s2gp import loss_from_trace, loss_func, raise_like_reference  # noqa: F401
+from ._s2gp import _poses_arg, eligible_cost, loss_from_trace, loss_func, raise_like_reference  # noqa: F401
 from .VGG import VGGUnet, VGGUnet_G2S, vgg_backward_nhwc, vgg_forward_nhwc
 
 
@@ -133,11 +133,71 @@ class LM_G2SP(nn.Module):
         _lib.check(rc, 'hla_g2s_lm_solve_bwd')
         return d_sat, d_grd, d_conf, d_lambda
 
+    @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
+    def score_poses(self, sat_feats, grd_feats, grd_confs, camera_k, ori_hw, poses, level, sat_inv_norm=None, grd_inv_norm=None):
+        """The matching term of this direction at given poses, on feature maps extracted once (``hla_g2s_pose_score``,
+        include/hla.h): low-level like ``lm_solve``, with the same map arguments.  ``poses`` [K,3] (shared by the samples) or
+        [B,K,3], (shift_u, shift_v, heading) in normalised units; ``level`` indexes the lists.  Returns (cost [B,K] fp32, sums
+        [B,K,8] fp64): over the satellite pixels whose projection is in view sum f^2, sum s^2, sum f s, the same three weighted,
+        their number, and sum s^2 over all pixels; cost = sum w (f/||f|| - s/||s||)^2 over the overlap, +inf with nothing in view."""
+        B, L = sat_feats[0].shape[0], len(sat_feats)
+        p = _poses_arg(poses, B)
+        if not 0 <= int(level) < L:
+            raise ValueError(f'level must be in [0, {L}), got {level}')
+        _lib.require_gpu(sat_feats[0], 'sat_feats')
+        lib = _lib.load()
+        dev = sat_feats[0].device
+        cfg, lv, Kc = self._structs(sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm)
+        p = p.to(dev).contiguous()
+        K = p.shape[1]
+        one = C.byref(lv[int(level)])
+        cost = torch.empty(B, K, device=dev, dtype=torch.float32)
+        sums = torch.empty(B, K, 8, device=dev, dtype=torch.float64)
+        nbytes = lib.hla_g2s_pose_score_workspace_bytes(C.byref(cfg), one, B, K)
+        if nbytes == 0:
+            _lib.check(-1, 'hla_g2s_pose_score_workspace_bytes')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))
+        rc = lib.hla_g2s_pose_score(C.byref(cfg), one, _lib.ptr(Kc), oh, ow, _lib.ptr(p), K, _lib.ptr(sums), _lib.ptr(cost),
+                                    _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
+        _lib.check(rc, 'hla_g2s_pose_score')
+        return cost, sums
+
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
-    def forward(self, sat_map, grd_img_left, left_camera_k, gt_shift_u=None, gt_shift_v=None, gt_heading=None,
-                mode='train', file_name=None, gt_depth=None, init_pose=None):
-        """mode='test' -> (shift_lat[B], shift_lon[B], theta[B]) (models_kitti.py:498-499);
-        mode='train' -> the 14-tuple (486-496); under autograd its loss back-propagates through the HIP backward (_G2sFn)."""
+    def forward_search(self, sat_map, grd_img_left, left_camera_k, candidates, top_m=1, score_level=0, min_in_view=0.5):
+        """A pose search in front of the LM loop, the composition of ``S2GPBase._search`` in this direction: extract the features
+        once, score the ``candidates`` ([K,3] or [B,K,3]; ``pose_grid``) at ``score_level``, run the loop from the ``top_m`` best
+        eligible ones (``eligible_cost``), keep the final pose that scores best at the finest level.  No autograd, no host sync,
+        no random numbers.  -> (shift_lat[B], shift_lon[B], theta[B]) like ``forward(mode='test')``; ``last_search`` keeps cost,
+        sums, start_index [B,top_m], traces [B,top_m,N_iters,L,3], final_cost [B,top_m] and best [B]."""
+        _lib.require_gpu(sat_map, 'sat_map')
+        _lib.require_gpu(grd_img_left, 'grd_img')
+        self._check_images(sat_map, grd_img_left)
+        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img_left), ('parameters', self.damping))
+        B, M = sat_map.shape[0], int(top_m)
+        cand = _poses_arg(candidates, B, 'candidates').to(sat_map.device)
+        if not 1 <= M <= cand.shape[1]:
+            raise ValueError(f'top_m must be in [1, {cand.shape[1]}] (the number of candidates), got {top_m}')
+        with torch.no_grad():
+            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
+            grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_img_left, want_conf=bool(self.using_weight),
+                                                             defer_norm=True)
+            hw = grd_img_left.shape[-2:]
+            score = lambda poses, level: self.score_poses(sat_feats, grd_feats, grd_confs, left_camera_k, hw, poses, level,
+                                                          sat_inv, grd_inv)
+            cost, sums = score(cand, score_level)
+            start_index = torch.topk(eligible_cost(cost, sums, min_in_view), M, dim=1, largest=False, sorted=True).indices
+            starts = cand.gather(1, start_index[:, :, None].expand(-1, -1, 3))
+            traces = torch.stack([self.lm_solve(sat_feats, grd_feats, grd_confs, left_camera_k, hw, starts[:, m].contiguous(),
+                                                sat_inv, grd_inv) for m in range(M)], dim=1)
+            finals = traces[:, :, -1, -1, :].contiguous()
+            final_cost, _ = score(finals, len(sat_feats) - 1)
+            best = final_cost.argmin(dim=1)
+            pose = finals.gather(1, best[:, None, None].expand(-1, 1, 3))[:, 0]
+        self.last_search = dict(cost=cost, sums=sums, start_index=start_index, traces=traces, final_cost=final_cost, best=best)
+        return pose[:, 1], pose[:, 0], pose[:, 2]
+
+    def _check_images(self, sat_map, grd_img_left):
         if sat_map.dim() != 4 or grd_img_left.dim() != 4 or sat_map.shape[0] != grd_img_left.shape[0] \
                 or sat_map.shape[2] != sat_map.shape[3]:
             raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W], got {tuple(sat_map.shape)} and '
@@ -148,6 +208,13 @@ class LM_G2SP(nn.Module):
                 raise ValueError(f"proj='nn' warps the FOLDED ground maps ([H,W] -> [2H,W/2]) in the satellite maps' plane, so they must "
                                  f'be the satellite maps\' size: grd_img must be [B,3,A/2,2A] = [B,3,{A // 2},{2 * A}] for sat_map '
                                  f'[B,3,{A},{A}], got {tuple(grd_img_left.shape)}')
+
+    @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
+    def forward(self, sat_map, grd_img_left, left_camera_k, gt_shift_u=None, gt_shift_v=None, gt_heading=None,
+                mode='train', file_name=None, gt_depth=None, init_pose=None):
+        """mode='test' -> (shift_lat[B], shift_lon[B], theta[B]) (models_kitti.py:498-499);
+        mode='train' -> the 14-tuple (486-496); under autograd its loss back-propagates through the HIP backward (_G2sFn)."""
+        self._check_images(sat_map, grd_img_left)
         want_conf = bool(self.using_weight) or mode == 'train'
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             names = [n for n, _ in self.named_parameters()]

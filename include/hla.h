@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 27
+#define HLA_ABI_VERSION 28
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -359,7 +359,7 @@ typedef struct hla_s2g_config {
                              pairs whose bound outgrew the first one's by more than 2^(50 - P), i.e. put the 63-bit range at
                              risk (must be 0: repeat the call with a smaller P).  Costs 8 B per satellite-map element of
                              workspace, its memset and the closing pass */
-  int proj;               /* hla_g2s_lm_solve / hla_g2s_lm_solve_bwd only.  0: proj == 'geo', the camera chain.  1: proj == 'nn', the
+  int proj;               /* hla_g2s_* only.  0: proj == 'geo', the camera chain.  1: proj == 'nn', the
                              in-plane similarity warp of the (folded) ground map (models_kitti.py:289-332).  hla_s2g_* require 0 */
 } hla_s2g_config;
 
@@ -438,6 +438,35 @@ size_t hla_g2s_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* l
 int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* levels, const float* camera_k, int ori_h, int ori_w,
                      const float* pose0, float* trace, double* normal_eq, void* workspace, size_t workspace_bytes,
                      int B, hla_stream_t stream);
+
+/* Pose scoring in the ground -> satellite direction (no reference function: the matching term of LM_G2SP, i.e. the projection
+ * of project_grd_to_map, models_kitti.py:163-303, or of inplane_grd_to_map, 289-332, and the residual of LM_update, 333-379, read
+ * back at given poses).  For ONE level, B samples and K candidate poses per sample, without Jacobians.  Over the A x A pixels of
+ * the level's satellite map, for sample b and hypothesis k:
+ *   f = the ground feature sampled where the pixel projects: the set-up, weights and hard in-bounds mask of hla_g2s_lm_solve
+ *   s = the satellite feature;   w = the projected confidence iff cfg->using_weight, else 1
+ *   a pixel is IN VIEW when its projection is in bounds, 0 <= u <= w-1 and 0 <= v <= h-1, tested in fp64
+ *   (both maps times their *_inv_norm when the level carries them: the sums are rescaled in the closing pass, like normal_eq)
+ * sums [B,K,8] fp64 out, [0..5] over the pixels in view:
+ *   [0] sum f^2   [1] sum s^2   [2] sum f s   [3] sum w f^2   [4] sum w s^2   [5] sum w f s
+ *   [6] pixels in view (an exact integer)     [7] sum s^2 over ALL A^2 pixels (the same for every k)
+ *   without using_weight, [3..5] are bitwise copies of [0..2]
+ * cost [B,K] fp32 out: with nf = max(sqrt(sums[0]), 1e-6), ns = max(sqrt(sums[1]), 1e-6),
+ *   sums[3]/nf^2 + sums[4]/ns^2 - 2 sums[5]/(nf ns)  =  sum w (f/nf - s/ns)^2 over the overlap, formed in fp64 and rounded once;
+ *   in [0, 4]; +inf when nothing is in view.  (The loop's own objective, sum w (f - s)^2 over all pixels with f = 0 out of view,
+ *   rewards a pose for seeing less; without weights it is sums[0] - 2 sums[2] + sums[7].)
+ * cfg      read: proj, using_weight, shift_range_lat, shift_range_lon, rotation_range; ford must be 0
+ * level    ONE hla_s2g_level as hla_g2s_lm_solve takes it: feat_dtype HLA_F32, grd_row_skip = 0, depth NULL; C in {64, 128, 256},
+ *          also 16 with proj 1; no weights with proj 1
+ * camera_k, ori_h, ori_w  as in hla_g2s_lm_solve (not read with proj 1);  poses [B,K,3] fp32 (shift_u, shift_v, heading), K >= 1
+ * A pose of any value, finite or not, reads only inside the sample's own maps.  Two launches; per-tile fp32 partials in the
+ * workspace, reduced in a fixed order in fp64.  The tile size follows from C alone: sums and cost of (b, k) do not depend, bit
+ * for bit, on the other hypotheses, on k's position, on K, on B or on repeats.
+ * hla_g2s_pose_score_workspace_bytes returns 0 and sets the last error on bad arguments. */
+size_t hla_g2s_pose_score_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K);
+int hla_g2s_pose_score(const hla_s2g_config* cfg, const hla_s2g_level* level, const float* camera_k, int ori_h, int ori_w,
+                       const float* poses, int K, double* sums, float* cost, void* workspace, size_t workspace_bytes, int B,
+                       hla_stream_t stream);
 
 typedef struct hla_s2g_level_grad {
   float* d_sat_feat; /* [B,A,A,C] fp32 */
