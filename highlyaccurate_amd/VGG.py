@@ -79,6 +79,12 @@ def _packed_weights(module: 'VGGUnet', prm, versions, dt: int, device):
     return cache['buf']
 
 
+def _alloc(*shape, dtype, device):
+    """Every output map and workspace of the forward wrappers below comes from here: uninitialised memory.  (A test replaces this
+    function to hand out NaN-filled buffers: whatever a forward leaves unwritten must never reach a result.)"""
+    return torch.empty(*shape, dtype=dtype, device=device)
+
+
 def _image_window(x: torch.Tensor):
     """(x, x_plane) for the C side: an fp32 NCHW image whose rows are W apart and whose samples are 3 planes apart is passed as
     it lies in memory -- in particular ``img[:, :, r0:, :]``, a window of rows of a taller image (x_plane = the full plane), is
@@ -94,7 +100,8 @@ def _image_window(x: torch.Tensor):
 
 @_lib.on_device(lambda module, x, *a, **k: x)
 def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True, defer_norm: bool = False,
-                     save_for_backward: bool = False, first_row8: int = 0, feat16: bool = False):
+                     save_for_backward: bool = False, first_row8: int = 0, feat16: bool = False, first_col32: int = 0,
+                     col_state: dict = None):
     """Run the three-level extractor.  Returns (feats, confs, inv_norm): lists of NHWC fp32 tensors
     [B,h,w,C] and [B,h,w] (or None), and inv_norm [3,B] fp64 = 1/max(||map||, 1e-12).
     With ``defer_norm`` the maps are left un-normalised (the LM loop folds inv_norm into its sums);
@@ -102,7 +109,12 @@ def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True,
     ``first_row8`` = f > 0 promises that only rows f / 2f / 4f.. of the three maps will be read (include/hla.h): the layers
     skip the rows nothing depends on, the rows above stay unwritten and inv_norm covers the computed rows only.
     ``feat16`` (bf16 / fp16 precision, ``defer_norm`` only, inference only): the raw maps are returned in the 16-bit activation
-    type instead of fp32 -- half the bytes through the HBM-bound LM loop, whose arithmetic stays fp32 / fp64."""
+    type instead of fp32 -- half the bytes through the HBM-bound LM loop, whose arithmetic stays fp32 / fp64.
+    ``first_col32`` = c > 0 promises that only columns 16c+2 / 32c+6 / 64c+14.. of the three maps will be read (include/hla.h): the
+    layers start at tile column c / 2c / 4c, those columns are bit-identical to the full forward's, the ones left of them are not
+    valid or not written (``promised_cols`` gives the three columns).  Inference with ``defer_norm`` only; elsewhere, and in
+    'fp16x3', every column is computed (include/hla.h).  ``col_state`` (a dict) receives what ``vgg_fixup_nhwc`` needs to complete
+    the maps of chosen samples afterwards."""
     _lib.require_gpu(x, 'VGGUnet input')
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f'expected [B,3,H,W], got {tuple(x.shape)}')
@@ -131,7 +143,7 @@ def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True,
         return (2 * h, w // 2) if folded else (h, w)
 
     # level 4: x24 is stored with 64 channels, the 16 real ones first, zeros behind them (see include/hla.h)
-    feats = [torch.empty(B, *hw(l, fold), 64 if l == 3 else _CH[l], device=x.device, dtype=fdt) for l in range(L)]
+    feats = [_alloc(B, *hw(l, fold), 64 if l == 3 else _CH[l], device=x.device, dtype=fdt) for l in range(L)]
     # (the folded extractor's conf0 reads the unfolded x15, VGG.py:322)
     confs = [torch.empty(B, *hw(l, fold and l > 0), device=x.device, dtype=torch.float32) if want_conf else None
              for l in range(L)]
@@ -141,14 +153,18 @@ def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True,
     flags = (_lib.HLA_VGG_WANT_CONF if want_conf else 0) | (_lib.HLA_VGG_DEFER_NORM if defer_norm else 0) | \
             (_lib.HLA_VGG_FEAT16 if feat16 else 0) | (_lib.HLA_VGG_FOLD_DECODER if fold else 0)
     nbytes = lib.hla_vgg_workspace_bytes_flags(B, H, W, L, dt, flags) if fold else lib.hla_vgg_workspace_bytes(B, H, W, L, dt)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _alloc(nbytes, dtype=torch.uint8, device=x.device)
     if save_for_backward:
         if not defer_norm:
             raise ValueError('save_for_backward needs defer_norm=True (the backward works on the raw maps)')
         flags |= _lib.HLA_VGG_SAVE_FOR_BACKWARD
-    rc = lib.hla_vgg_forward(_lib.ptr(x), x_plane, C.byref(prm), _lib.ptr(packed), fp, cp, _lib.ptr(inv_norm), _lib.ptr(ws), nbytes,
-                             B, H, W, L, dt, flags, int(first_row8), _lib.stream_ptr())
+    c32 = _check_first_col32(first_col32, W)
+    rc = lib.hla_vgg_forward_cols(_lib.ptr(x), x_plane, C.byref(prm), _lib.ptr(packed), fp, cp, _lib.ptr(inv_norm), _lib.ptr(ws), nbytes,
+                                  B, H, W, L, dt, flags, int(first_row8), c32, None, _lib.stream_ptr())
     _lib.check(rc, 'hla_vgg_forward')
+    if col_state is not None:
+        col_state.update(x=x, x_plane=x_plane, prm=prm, keep=keep, packed=packed, feats=feats, inv_norm=inv_norm, ws=ws, B=B, H=H, W=W,
+                         L=L, dt=dt, flags=flags, first_row8=int(first_row8), first_col32=c32)
     # ws is only used by work already enqueued on this stream; the caching allocator keeps the block
     # stream-ordered, so dropping the Python reference here is safe.
     if save_for_backward:
@@ -159,12 +175,49 @@ def vgg_forward_nhwc(module: 'VGGUnet', x: torch.Tensor, want_conf: bool = True,
     return feats, confs, inv_norm
 
 
+def _check_first_col32(first_col32, W: int) -> int:
+    c = int(first_col32)
+    if c < 0 or (c > 0 and 128 * c >= W):
+        raise ValueError(f'first_col32 must be 0 or leave a column of the maps (128 * first_col32 < W = {W}), got {first_col32}')
+    return c
+
+
+def promised_cols(first_col32: int):
+    """First column of (x15, x18, x21) that a forward with ``first_col32`` = c leaves bit-identical to the full forward's: conv2
+    is exact from its first column 128c (it computes conv0's halo from the image), every later 3x3 layer loses one column to the
+    zero it reads left of its first one, a pool halves and an up-sampling doubles (csrc/vgg.hip, vgg_build_convs)."""
+    c = int(first_col32)
+    return (16 * c + 2, 32 * c + 6, 64 * c + 14) if c > 0 else (0, 0, 0)
+
+
+@_lib.on_device(lambda state, gate: gate)
+def vgg_fixup_nhwc(state: dict, gate: torch.Tensor) -> None:
+    """The fix-up pass of a forward made with ``first_col32`` > 0 (``state``: its ``col_state``): for every sample b with
+    ``gate[b] != 0`` (int32 [B] on the device) the columns that forward skipped or left wrong are computed, and inv_norm again --
+    in place, on the current stream, without a host synchronisation.  Such a sample's maps and inv_norm are then bit for bit the
+    full forward's; the others are not touched."""
+    s = state
+    if not s or not s['first_col32']:
+        return
+    if gate.dtype != torch.int32 or gate.numel() != s['B'] or not gate.is_contiguous() or gate.device != s['x'].device:
+        raise ValueError('gate must be a contiguous int32 [B] tensor on the device of the maps')
+    L = s['L']
+    fp = (C.c_void_p * 4)(*([f.data_ptr() for f in s['feats']] + [0] * (4 - L)))
+    cp = (C.c_void_p * 4)(0, 0, 0, 0)
+    rc = _lib.load().hla_vgg_forward_cols(_lib.ptr(s['x']), s['x_plane'], C.byref(s['prm']), _lib.ptr(s['packed']), fp, cp,
+                                     _lib.ptr(s['inv_norm']), _lib.ptr(s['ws']), s['ws'].numel(), s['B'], s['H'], s['W'], L, s['dt'],
+                                     s['flags'], s['first_row8'], s['first_col32'], _lib.ptr(gate), _lib.stream_ptr())
+    _lib.check(rc, 'hla_vgg_forward_cols (fix-up pass)')
+
+
 @_lib.on_device(lambda modules, xs, *a, **k: xs[0])
-def vgg_forward_pair_nhwc(modules, xs, first_row8=(0, 0), feat16: bool = False):
+def vgg_forward_pair_nhwc(modules, xs, first_row8=(0, 0), feat16: bool = False, first_col32=(0, 0), col_state: dict = None):
     """The inference forward of two level-3 extractors on batches of one size (``hla_vgg_forward_pair``): what
     ``vgg_forward_nhwc(m, x, want_conf=False, defer_norm=True, first_row8=f, feat16=feat16)`` returns for each of them, bit for
     bit, with every convolution layer of the two networks run as one launch where the library can pair them (include/hla.h).
-    Returns ``((feats0, inv_norm0), (feats1, inv_norm1), paired)``; ``paired`` tells whether the paired launches were issued."""
+    Returns ``((feats0, inv_norm0), (feats1, inv_norm1), paired)``; ``paired`` tells whether the paired launches were issued.
+    ``first_col32`` per network as in ``vgg_forward_nhwc``; ``col_state`` (a dict) receives the ``vgg_fixup_nhwc`` state of the
+    FIRST network."""
     lib = _lib.load()
     if len(modules) != 2 or len(xs) != 2:
         raise ValueError('vgg_forward_pair_nhwc takes two modules and two images')
@@ -184,19 +237,23 @@ def vgg_forward_pair_nhwc(modules, xs, first_row8=(0, 0), feat16: bool = False):
         _lib.same_device(('input', x), ('parameters', module.conv0.weight), ('first input', xs[0]))
         prm, kp, versions = _param_table(module)
         packed = _packed_weights(module, prm, versions, dt, x.device)
-        feats = [torch.empty(B, H >> (3 - l), W >> (3 - l), _CH[l], device=x.device, dtype=torch.float16 if feat16 else torch.float32)
+        feats = [_alloc(B, H >> (3 - l), W >> (3 - l), _CH[l], device=x.device, dtype=torch.float16 if feat16 else torch.float32)
                  for l in range(3)]
         inv_norm = torch.empty(3, B, device=x.device, dtype=torch.float64)
         nbytes = lib.hla_vgg_workspace_bytes(B, H, W, 3, dt)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ws = _alloc(nbytes, dtype=torch.uint8, device=x.device)
         b = br[k]
         b.x, b.x_plane, b.params, b.packed_weights = x.data_ptr(), x_plane, C.pointer(prm), packed.data_ptr()
         for l in range(3):
             b.feat[l] = feats[l].data_ptr()
         b.inv_norm, b.workspace, b.workspace_bytes = inv_norm.data_ptr(), ws.data_ptr(), nbytes
-        b.H, b.W, b.first_row8 = H, W, int(first_row8[k])
+        b.H, b.W, b.first_row8, b.first_col32 = H, W, int(first_row8[k]), _check_first_col32(first_col32[k], W)
         keep += [x, prm, kp, packed, ws]
         out.append((feats, inv_norm))
+        if k == 0 and col_state is not None:
+            col_state.update(x=x, x_plane=x_plane, prm=prm, keep=kp, packed=packed, feats=feats, inv_norm=inv_norm, ws=ws, B=B, H=H, W=W,
+                             L=3, dt=dt, flags=_lib.HLA_VGG_DEFER_NORM | (_lib.HLA_VGG_FEAT16 if feat16 else 0),
+                             first_row8=int(first_row8[k]), first_col32=b.first_col32)
     flags = _lib.HLA_VGG_DEFER_NORM | (_lib.HLA_VGG_FEAT16 if feat16 else 0)
     paired = C.c_int(0)
     rc = lib.hla_vgg_forward_pair(br, xs[0].shape[0], 3, dt, flags, C.byref(paired), _lib.stream_ptr())

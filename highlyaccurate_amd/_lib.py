@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class HlaError(RuntimeError):
@@ -47,13 +47,15 @@ class S2GConfig(C.Structure):
                 ('shift_range_lat', C.c_double), ('shift_range_lon', C.c_double), ('rotation_range', C.c_double),
                 ('damping', C.c_double * 3), ('keep', C.c_void_p), ('keep_stride', C.c_size_t),
                 ('optimizer', C.c_int), ('beta1', C.c_double), ('beta2', C.c_double), ('count_in_view', C.c_int),
-                ('grd_grad_overwrite', C.c_int), ('deterministic', C.c_int), ('proj', C.c_int)]
+                ('grd_grad_overwrite', C.c_int), ('deterministic', C.c_int), ('proj', C.c_int),
+                ('reach_mode', C.c_int), ('reach_flag', C.c_void_p), ('reach_col0', C.c_int * 4)]
 
 
 class VggBranch(C.Structure):
     _fields_ = [('x', C.c_void_p), ('x_plane', C.c_size_t), ('params', C.POINTER(VggParams)), ('packed_weights', C.c_void_p),
                 ('feat', C.c_void_p * 4), ('conf', C.c_void_p * 4), ('inv_norm', C.c_void_p), ('workspace', C.c_void_p),
-                ('workspace_bytes', C.c_size_t), ('H', C.c_int), ('W', C.c_int), ('first_row8', C.c_int)]
+                ('workspace_bytes', C.c_size_t), ('H', C.c_int), ('W', C.c_int), ('first_row8', C.c_int),
+                ('first_col32', C.c_int)]
 
 
 class FillRegion(C.Structure):
@@ -138,6 +140,9 @@ def load() -> C.CDLL:
     lib.hla_vgg_forward.restype = i
     lib.hla_vgg_forward.argtypes = [vp, sz, C.POINTER(VggParams), vp, C.POINTER(vp), C.POINTER(vp), vp, vp, sz,
                                     i, i, i, i, i, i, i, vp]
+    lib.hla_vgg_forward_cols.restype = i
+    lib.hla_vgg_forward_cols.argtypes = [vp, sz, C.POINTER(VggParams), vp, C.POINTER(vp), C.POINTER(vp), vp, vp, sz,
+                                         i, i, i, i, i, i, i, i, vp, vp]
     lib.hla_vgg_forward_pair.restype = i
     lib.hla_vgg_forward_pair.argtypes = [C.POINTER(VggBranch), i, i, i, i, C.POINTER(i), vp]
     lib.hla_vgg_packed_weight_bytes.restype = sz

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, utils
-from .VGG import VGGUnet, vgg_forward_nhwc, vgg_forward_pair_nhwc, vgg_backward_nhwc
+from .VGG import VGGUnet, vgg_forward_nhwc, vgg_forward_pair_nhwc, vgg_backward_nhwc, vgg_fixup_nhwc, promised_cols
 
 KITTI_K = [[582.9802, 0.0, 496.2420], [0.0, 482.7076, 125.0034], [0.0, 0.0, 1.0]]      # models_kitti.py:657-660
 FORD_K_FL = [945.391406, 0.0, 855.502825, 0.0, 945.668274, 566.372868, 0.0, 0.0, 1.0]   # models_ford.py:116
@@ -214,6 +214,10 @@ class S2GPBase(nn.Module):
     #   lm_feat16          1: bf16 / fp16 inference hands the LM loop fp16 feature maps; 0: fp32 maps           DESIGN.md 3.3
     #   ground_crop        1: mode='test' skips the ground-image rows (and, layer by layer, the feature rows) that cannot
     #                      reach the rows the LM loop reads; 0: whole image.  Computed rows are bit-identical  DESIGN.md 3.5
+    #   sat_reach_crop     1: mode='test' (KITTI, proj='geo', LM, level 3, no confidence heads, no depth map, not 'fp16x3') skips the
+    #                      left columns of the satellite maps that no pose inside the configured shift / rotation range reads;
+    #                      a sample whose loop leaves that reach is detected on the device and recomputed exactly, without a
+    #                      host synchronisation.  0: whole maps                                                  DESIGN.md 3.5
     #   train_ground_crop  0; 1: the same for training (changes the returned confidence maps above the crop)   DESIGN.md 3.5
     #   bwd_trim           1: the backward skips rows / tiles whose gradient is exactly zero; 0: dense walk     DESIGN.md 6
     #   bwd_two_streams    1: the two extractors' backward passes run on two streams (single-GPU training)       DESIGN.md 6
@@ -270,12 +274,16 @@ class S2GPBase(nn.Module):
             self.damping = nn.Parameter(torch.zeros(size=(), dtype=torch.float32))
         self.meters_per_pixel = [utils.get_meter_per_pixel() * (2 ** (3 - l)) for l in range(4)]
         self._tables = {}
+        self._reach = {}
         self._ray_tables = {}
         self._depth_idx = {}
         self.last_trace = None       # [B, N_iters, Level, 3] (shift_u, shift_v, theta) of the last forward
         self.last_normal_eq = None
         self.last_keep = None
         self.keep_normal_eq = False
+        self.keep_features = False   # True: localise keeps (sat_feats, sat_inv, grd_feats, grd_inv) of its inference path in last_features
+        self.last_features = None
+        self.last_reach_flag = None  # int32 [B] of the last localise that ran with args.sat_reach_crop in effect (1: recomputed), else None
         self.last_search = None      # forward_search: cost, sums, start_index, traces, final_cost, best of the last call
 
     # -- geometry tables ---------------------------------------------------------------------
@@ -319,6 +327,21 @@ class S2GPBase(nn.Module):
         if gt_depth.dim() != 3 or gt_depth.shape[0] != B or gt_depth.shape[1] < 1 or gt_depth.shape[2] < 1:
             raise ValueError(f'gt_depth must be [B,dH,dW] with B = {B}, got {tuple(gt_depth.shape)}')
         return gt_depth.detach().to(device).float().contiguous()
+
+    def sat_first_col32(self, A: int, grd_H: int, grd_W: int) -> int:
+        """args.sat_reach_crop: the tile columns (32 px at H/4) the satellite extractor may skip for an A x A image and this
+        ground geometry -- ``sat_reach`` over the configured pose range, walked back through the extractor.  Geometry only:
+        cached per (A, ground size, ranges).  0 where the trim does not apply."""
+        a = self.args
+        if self.ford or self.polar or self.level != 3 or A % 8:
+            return 0
+        key = (A, grd_H, grd_W, float(a.shift_range_lat), float(a.shift_range_lon), float(a.rotation_range))
+        if key not in self._reach:
+            tables = [t.cpu() for t in self.xyz_tables(grd_H, grd_W, 'cpu')]
+            mpp = [utils.get_meter_per_pixel() * utils.get_process_satmap_sidelength() / (A >> (3 - l)) for l in range(3)]
+            cols = sat_reach(tables[:3], [A >> (3 - l) for l in range(3)], mpp, key[3], key[4], key[5])
+            self._reach[key] = first_col32_of_reach(cols, A)
+        return self._reach[key]
 
     def _levels(self, maps):
         """The extractor always computes x15, x18, x21 (x15 feeds the decoder); level 2 uses the last two (VGG.py:183-184,198-199)."""
@@ -420,11 +443,16 @@ class S2GPBase(nn.Module):
 
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def lm_solve(self, sat_feats, grd_feats, grd_confs, grd_hw, extra=None, level_first=0, init_pose=None,
-                 sat_inv_norm=None, grd_inv_norm=None, keep_normal_eq=None, gt_depth=None):
+                 sat_inv_norm=None, grd_inv_norm=None, keep_normal_eq=None, gt_depth=None, reach=None):
         """sat_feats/grd_feats: NHWC fp32 lists (L2-normalised, or raw together with their [L,B] fp64
         inverse norms); returns trace [B,N_iters,L,3] = (shift_u, shift_v, theta).
         ``gt_depth`` [B,dH,dW] (any size): every ground pixel is lifted to ray * depth instead of onto the ground plane, with
-        the mask depth != -1 (models_kitti.py:741-748); None: the flat-ground tables."""
+        the mask depth != -1 (models_kitti.py:741-748); None: the flat-ground tables.
+        ``reach`` = (col0, fixup): the satellite maps are only valid from column ``col0[l]`` on (a forward made with first_col32).
+        The loop then reports, per sample, whether it read left of that (``self.last_reach_flag``); ``fixup(flag)`` must complete the
+        maps of the flagged samples (``vgg_fixup_nhwc``), and the loop runs again for those samples alone, with the same random
+        draws.  A flagged sample ends with the trace and normal equations of the loop on whole maps, bit for bit; nothing waits
+        for the host."""
         lib = _lib.load()
         dev = sat_feats[0].device
         B, L = sat_feats[0].shape[0], len(sat_feats)
@@ -445,9 +473,23 @@ class S2GPBase(nn.Module):
         nbytes = lib.hla_s2g_workspace_bytes(C.byref(cfg), lv, B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         p0 = init_pose.to(dev).float().contiguous() if init_pose is not None else None
+        flag = None
+        if reach is not None:
+            flag = torch.empty(B, dtype=torch.int32, device=dev)       # (cleared by the loop's init launch)
+            cfg.reach_mode, cfg.reach_flag = 1, flag.data_ptr()
+            for l in range(L):
+                cfg.reach_col0[l] = int(reach[0][l])
         rc = lib.hla_s2g_lm_solve(C.byref(cfg), lv, _lib.ptr(R_FL), _lib.ptr(T_FL), _lib.ptr(p0), _lib.ptr(rand_uv),
                                   _lib.ptr(trace), _lib.ptr(neq), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
         _lib.check(rc, 'hla_s2g_lm_solve')
+        if reach is not None:
+            # enqueued on every call, gated per sample on the device: the maps' missing columns, then the whole loop again
+            reach[1](flag)
+            cfg.reach_mode = 2
+            rc = lib.hla_s2g_lm_solve(C.byref(cfg), lv, _lib.ptr(R_FL), _lib.ptr(T_FL), _lib.ptr(p0), _lib.ptr(rand_uv),
+                                      _lib.ptr(trace), _lib.ptr(neq), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
+            _lib.check(rc, 'hla_s2g_lm_solve (reach fallback)')
+        self.last_reach_flag = flag
         # Error behaviour of the reference, which costs a host sync and is therefore only reproduced (a) under the ablation
         # flags that can make H + damping*D exactly singular (use_hessian / zero damping) and (b) when strict error checking
         # is asked for (args.strict_errors).  With the default flags the forward has no host sync;
@@ -609,8 +651,9 @@ class S2GPBase(nn.Module):
         self.last_search = dict(cost=cost, sums=sums, start_index=start_index, traces=traces, final_cost=final_cost, best=best)
         return pose
 
-    def _features(self, sat_map, grd_img, want_conf, return_confs):
-        """Both extractors of the inference path: (sat_feats, sat_inv, grd_feats, grd_confs, grd_inv), normalisation deferred."""
+    def _features(self, sat_map, grd_img, want_conf, return_confs, sat_c32=0, col_state=None):
+        """Both extractors of the inference path: (sat_feats, sat_inv, grd_feats, grd_confs, grd_inv), normalisation deferred.
+        ``sat_c32`` / ``col_state``: the satellite extractor's first_col32 and the dict that receives its fix-up state."""
         # Reduced-precision inference modes: the LM loop reads fp16 feature maps (written saturating by the three feature
         # layers' epilogues; also in bf16 mode: bf16's 8 significand bits moved the worst golden seed's pose 23x, fp16's 11
         # move it 1.6x).  With the gather loop written on channel PAIRS (lm_solve.hip) the accumulate kernels are VALU-bound on
@@ -637,7 +680,8 @@ class S2GPBase(nn.Module):
         if (not small and not want_conf and self.level != 4 and bool(getattr(self.args, 'pair_extractor_launches', 1))
                 and self.GrdFeatureNet.precision == self.SatFeatureNet.precision):
             (sat_feats, sat_inv), (grd_feats, grd_inv), _ = vgg_forward_pair_nhwc(
-                (self.SatFeatureNet, self.GrdFeatureNet), (sat_map, grd_in), first_row8=(0, f8), feat16=f16)
+                (self.SatFeatureNet, self.GrdFeatureNet), (sat_map, grd_in), first_row8=(0, f8), feat16=f16,
+                first_col32=(sat_c32, 0), col_state=col_state)
             L = self._levels
             return L(sat_feats), L(sat_inv), L(grd_feats), L([None] * 3), L(grd_inv)
         if small:
@@ -645,16 +689,20 @@ class S2GPBase(nn.Module):
             side = _side_stream(sat_map.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16)
+                sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16,
+                                                         first_col32=sat_c32, col_state=col_state)
             sat_map.record_stream(side)
         else:
-            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16)
+            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, feat16=f16,
+                                                     first_col32=sat_c32, col_state=col_state)
         grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_in, want_conf=want_conf, defer_norm=True,
                                                          first_row8=f8, feat16=f16)
         if small:
             cur.wait_stream(side)
             for t in list(sat_feats) + [sat_inv]:        # allocated on the side stream, consumed (LM loop) on this one
                 t.record_stream(cur)
+            if col_state:                                # (so is the workspace the fix-up pass works in)
+                col_state['ws'].record_stream(cur)
         L = self._levels
         return L(sat_feats), L(sat_inv), L(grd_feats), L(grd_confs), L(grd_inv)
 
@@ -682,9 +730,21 @@ class S2GPBase(nn.Module):
             out = _LocaliseFn.apply(self, names, sat_map, grd_img, want_conf, extra, level_first, init_pose, gt_depth, *params)
             return out[0], list(out[1:]) if want_conf else [None] * self.level
         # (the two dense extractor passes on two streams measured 2 % slower than back to back: DESIGN.md 3.1)
-        sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, want_conf, return_confs)
+        # args.sat_reach_crop: the satellite extractor skips the columns the configured pose range cannot reach;
+        # the loop checks that on the device, and a sample that left the reach is completed and run again (lm_solve, `reach`)
+        a = self.args
+        c32 = 0
+        if (bool(getattr(a, 'sat_reach_crop', 1)) and not return_confs and not want_conf and gt_depth is None and not self.ford
+                and not self.polar and self.level == 3 and getattr(a, 'Optimizer', 'LM') == 'LM'
+                and not getattr(a, 'strict_errors', 0) and self.SatFeatureNet.precision != 'fp16x3'):
+            c32 = self.sat_first_col32(sat_map.shape[-1], grd_img.shape[-2], grd_img.shape[-1])
+        state = {} if c32 else None
+        sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, want_conf, return_confs, c32, state)
+        reach = (promised_cols(c32), lambda flag: vgg_fixup_nhwc(state, flag)) if c32 else None
         trace = self.lm_solve(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], extra, level_first, init_pose,
-                              sat_inv, grd_inv, gt_depth=gt_depth)
+                              sat_inv, grd_inv, gt_depth=gt_depth, reach=reach)
+        if self.keep_features:
+            self.last_features = (sat_feats, sat_inv, grd_feats, grd_inv)
         return trace, grd_confs
 
 
@@ -781,6 +841,61 @@ def _side_stream(device) -> 'torch.cuda.Stream':
     if st is None:
         st = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=idx)
     return st
+
+
+def sat_reach(tables, sizes, mpp, shift_range_lat, shift_range_lon, rotation_range, n: int = 5):
+    """Per level, the smallest satellite-map column any bilinear tap of the LM loop reads while the pose stays inside the box
+    [-1, 1]^3 of (shift_u, shift_v, theta): floor(u) over the ground pixels the loop reads (rows h/2.., ground mask z > 0) that
+    land inside the map, with the coefficient formulas of the loop itself (csrc/lm_common.h, lm_coefficients: KITTI chain), in
+    fp64, over an n x n x n lattice of the box (n odd: corners and centres included).  ``tables[l]`` [h,w,3] ground-plane table,
+    ``sizes[l]`` = A_l, ``mpp[l]`` metres per pixel.  A level nothing of which is in view gets A_l.  The camera looks towards +u,
+    so the left part of every map is out of reach; the result only decides how often the exact fallback runs."""
+    axis = np.linspace(-1.0, 1.0, n)
+    out = []
+    for t, A, m in zip(tables, sizes, mpp):
+        t = np.asarray(t, dtype=np.float64)
+        h = t.shape[0]
+        P = t[h // 2:].reshape(-1, 3)
+        P = P[P[:, 2] > 0]
+        X, Z = P[:, 0], P[:, 2]
+        best, im, ctr = float(A), 1.0 / m, A / 2.0
+        for th in axis:
+            ang = th * rotation_range / 180.0 * np.pi
+            c, s = np.cos(ang), np.sin(ang)
+            for su in axis * shift_range_lon:
+                for sv in axis * shift_range_lat:
+                    u = s * im * X + c * im * Z + (c * su - s * sv) * im + ctr
+                    v = c * im * X - s * im * Z + (-c * sv - s * su) * im + ctr
+                    ok = (u >= 0) & (u <= A - 1) & (v >= 0) & (v <= A - 1)
+                    if ok.any():
+                        best = min(best, float(np.floor(u[ok].min())))
+        out.append(int(best))
+    return out
+
+
+def reach_walk(p0: int, p1: int, p2: int) -> dict:
+    """First column each map / layer of VGGUnet.forward has to hold when the loop reads x15 / x18 / x21 from columns p0 / p1 / p2
+    on (the column twin of ``dead_ground_rows``' walk): a 3x3 conv needs one more column of its input, a 2x up-sampling halves,
+    a 2x2 pool doubles.  Keys: maps 'x3', 'x8', 'x15', 'x18', 'x21'; layers by their own output resolution."""
+    x18 = min(p1, (p2 - 2) >> 1)              # dec2.1 [p2-1..] reads up(x18) from p2-2
+    x15 = min(p0, (x18 - 2) >> 1)             # dec1.1 [x18-1..] reads up(x15) from x18-2
+    x8 = min(2 * x15 - 3, x18 - 2)            # conv10 [2 x15 - 2..]; dec1.1's skip input
+    x3 = min(2 * x8 - 2, p2 - 2)              # conv5 [2 x8 - 1..]; dec2.1's skip input
+    return {'x21': p2, 'dec2.1': p2 - 1, 'x18': x18, 'dec1.1': x18 - 1, 'x15': x15, 'conv14': 2 * x15, 'conv12': 2 * x15 - 1,
+            'conv10': 2 * x15 - 2, 'x8': x8, 'conv7': 2 * x8, 'conv5': 2 * x8 - 1, 'x3': x3, 'conv2': 2 * x3}
+
+
+# columns per H/4 tile column at each layer's own resolution: a start that keeps the pools and the 32-pixel tiles aligned
+_REACH_QUANTUM = {'x21': 64, 'dec2.1': 64, 'x18': 32, 'dec1.1': 32, 'x15': 16, 'conv14': 32, 'conv12': 32, 'conv10': 32, 'x8': 32,
+                  'conv7': 64, 'conv5': 64, 'x3': 64, 'conv2': 128}
+
+
+def first_col32_of_reach(cols, A: int) -> int:
+    """The largest c for which every layer may start at its tile column c / 2c / 4c (hla_vgg_forward's first_col32) when the loop
+    reads the three maps from columns ``cols`` on; at least one column of the maps stays (128 c < A)."""
+    need = reach_walk(*[int(x) for x in cols])
+    c = min(max(v, 0) // _REACH_QUANTUM[k] for k, v in need.items())
+    return max(0, min(c, (A - 1) // 128))
 
 
 def dead_ground_rows(H: int) -> int:

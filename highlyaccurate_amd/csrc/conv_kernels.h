@@ -239,6 +239,12 @@ struct ConvArgs {
   int tiles_x, tiles_y;
   int row_begin;      // first output row this launch computes (even for POOL); rows above it are left untouched.  The halo row
                       // row_begin-1 of the sources is read as it lies in memory (the caller guarantees it was written)
+  int col_begin;      // first 32-pixel tile column this launch computes (hla_vgg_forward's first_col32): the tile decode adds it,
+                      // the halo loaders read every source column left of 32 * col_begin as zero (the producer started at the same
+                      // column of this resolution and never wrote them) and a sum-of-squares slot keeps the place it has in a
+                      // launch over the whole width (the slots of the skipped tile columns are written as zero)
+  int col_tiles;      // host only (conv_plan): tile columns the launch computes, 0 = up to the map's right edge
+  const int* gate;    // [B] or null: a workgroup whose sample has gate[b] == 0 returns at once (the per-sample fix-up pass)
   int src_row_lo;     // source rows above this one (in THIS launch's full-resolution row coordinates) read as zero: the
                       // backward's gradient maps are exactly zero -- and unwritten -- above their first row
   int add_row_lo;     // likewise for add_src, in output row coordinates
@@ -698,9 +704,16 @@ __device__ __forceinline__ void conv_epilogue(typename AccMap<SHAPE>::Tile (&acc
     if (tid == 0) {
       if (has_sumsq) {
         // the remapped id is (b * tiles + tile) * gy + cout block (conv_block_map): its remainder is the slot tile * gy + cout block
-        const int np = a.tiles_x * a.tiles_y * conv_cout_blocks<NT>(a);
-        const int tile = xcd_contiguous(blk, nblk) % np;
-        a.sumsq[(size_t)b * np + tile] = ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]);
+        // The slot is (tile row, tile column of the WHOLE map, cout block) -- what the remapped workgroup id's remainder is in a
+        // launch over the whole width -- also when the launch covers a column range (col_begin, tiles_x): a sample's slots are the
+        // same whichever launches filled them.  The tile at col_begin also clears the slots of the tile columns left of it.
+        // (thread 0 sits in wave (0, 0): yrow0 is the tile's first row, cb the first channel of the workgroup's block)
+        const int gyb = conv_cout_blocks<NT>(a), txf = (a.W + 31) >> 5;
+        const int ty = (yrow0 - a.row_begin) / (2 * MT), txg = x0 >> 5, cblk = cb / (64 * NT);
+        double* row = a.sumsq + ((size_t)b * a.tiles_y + ty) * (txf * gyb) + cblk;
+        row[txg * gyb] = ((double)red[0] + (double)red[1]) + ((double)red[2] + (double)red[3]);
+        if (txg == a.col_begin)
+          for (int k = 0; k < txg; ++k) row[k * gyb] = 0.0;
       }
       if (want_max) {    // non-negative floats order like their bit patterns; the plain read only filters (a stale value costs one
         const unsigned mb = __float_as_uint(fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));      // redundant atomic, never a missed one)
@@ -1049,7 +1062,8 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   // column interval of the source per halo row class: top halo row / the tile's own rows / bottom halo row
   // (six scalars, not arrays: once the halo row of a piece is a run-time value the compiler turns a select over array elements
   // into an indexed load from a stack copy of the array)
-  struct { int lo0, lo1, lo2, hi0, hi1, hi2; } sb = {0, 0, 0, a.W, a.W, a.W};
+  const int clo = a.col_begin * 32;
+  struct { int lo0, lo1, lo2, hi0, hi1, hi2; } sb = {clo, clo, clo, a.W, a.W, a.W};
   if (a.dyn) {                              // kernel-uniform; everything below is scalar loads
     // Only the live tiles are enumerated, by the FIRST workgroups of the grid; the rest exit.  (Launching every tile and
     // returning from the dead ones is not enough: workgroup ids go round-robin to the shader engines, so a dead / live
@@ -1075,10 +1089,11 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
     const ConvBlock m = conv_block_map(blk, nblk, gy);
     int bid = m.tile;
     cblk = m.cb;
-    tx = bid % a.tiles_x; bid /= a.tiles_x;
+    tx = bid % a.tiles_x + a.col_begin; bid /= a.tiles_x;
     ty = bid % a.tiles_y;
     b = bid / a.tiles_y;
   }
+  if (a.gate && a.gate[b] == 0) return;      // workgroup-uniform, ahead of the first barrier
   const int y0 = a.row_begin + ty * TH, x0 = tx * 32;
   const int nstage = (a.C1 + a.C2) / KC;
   const int part = t & 3, pbase = t >> 2;   // 256 % 4 == 0: a thread always moves the same 16-B part of a pixel
@@ -1381,6 +1396,7 @@ __device__ __forceinline__ void pair_inference_args(ConvArgs& a) {
   a.src1 = pair_global(a.src1); a.src2 = pair_global(a.src2); a.wpk = pair_global(a.wpk); a.bias = pair_global(a.bias);
   a.out_act = pair_global(a.out_act); a.out_raw = pair_global(a.out_raw); a.sumsq = pair_global(a.sumsq);
   a.amax1 = pair_global(a.amax1); a.amax2 = pair_global(a.amax2); a.amax_out = pair_global(a.amax_out); a.wscale = pair_global(a.wscale);
+  a.gate = nullptr; a.col_tiles = 0;       // (col_begin stays a run-time value: the satellite segment of the trimmed forward)
   a.dyn = nullptr; a.dyn_desc = 0; a.src_row_lo = 0; a.add_row_lo = 0; a.unpool_idx = nullptr; a.mask_act = nullptr; a.add_src = nullptr;
   a.idx_out = nullptr; a.pool_sum = 0; a.wg0_x = nullptr; a.wg0_x_plane = 0; a.wg0_part = nullptr;
 #if HLA_CONV_STAMPS
@@ -1412,6 +1428,9 @@ struct Conv02Args {
   void* a2_out;        // level 4: NHWC T [B,H,W,64] = relu(conv2) before the pool (the skip input of conv_dec3), or null
   int B, H, W, tiles_x, tiles_y;
   int row_begin;       // first conv2 output row (full resolution, even) this launch computes; see ConvArgs::row_begin
+  int col_begin;       // first 32-pixel tile column this launch computes (tiles_x counts from it).  conv0's halo is computed from the
+                       // image itself, so the outputs are the full run's from the first computed column on
+  const int* gate;     // [B] or null: see ConvArgs::gate
   // --- split-fp16 mode ---
   const float* wtail;      // the packer's tail: [l] = power-of-two scale of layer l's packed weights, [16] = max_cout sum_k |w0|
   unsigned* amax_out;      // [B] atomicMax target: max of out_act per sample
@@ -1455,9 +1474,10 @@ __device__ __forceinline__ void conv02_body(const Conv02Args& a0, const int blk)
 
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6), wm = wv / WN, wn = wv % WN;
   int bid = blk;                           // (the XCD-contiguous order measured 2-3 % slower for this kernel)
-  const int tx = bid % a0.tiles_x; bid /= a0.tiles_x;
+  const int tx = bid % a0.tiles_x + a0.col_begin; bid /= a0.tiles_x;
   const int ty = bid % a0.tiles_y;
   const int b = bid / a0.tiles_y;
+  if (a0.gate && a0.gate[b] == 0) return;      // workgroup-uniform, ahead of the first barrier
   const int y0 = a0.row_begin + ty * TH, x0 = tx * 32;
   const int x = lane & 31, g = lane >> 5;
 
@@ -1750,6 +1770,7 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_pair_kerne
   a0.x = pair_global(a0.x); a0.w0 = pair_global(a0.w0); a0.b0 = pair_global(a0.b0); a0.w2 = pair_global(a0.w2); a0.b2 = pair_global(a0.b2);
   a0.out_act = pair_global(a0.out_act); a0.wtail = pair_global(a0.wtail); a0.amax_out = pair_global(a0.amax_out);
   a0.a0_out = nullptr; a0.idx_out = nullptr; a0.a2_out = nullptr; a0.amax_a2_out = nullptr; a0.amax_a0_out = nullptr;      // (inference, level 3)
+  a0.gate = nullptr;
 #if HLA_CONV_STAMPS
   a0.stamps = nullptr;
 #endif
@@ -1987,10 +2008,11 @@ static __global__ __launch_bounds__(256) void inv_norm_kernel(const double* __re
 }
 // all levels of a network (or of two) in one launch: blockIdx.y = row
 // (rows = levels x networks: a paired forward normalises both networks' maps with one launch; inv[row] = that row's [B] outputs)
-struct InvNormArgs { const double* ss[8]; int np[8]; double* inv[8]; };
+struct InvNormArgs { const double* ss[8]; int np[8]; double* inv[8]; const int* gate; };      // gate: see ConvArgs::gate
 static __global__ __launch_bounds__(256) void inv_norm_multi_kernel(InvNormArgs a) {
   __shared__ double sh[4];
   const int b = blockIdx.x, l = blockIdx.y, np = a.np[l];
+  if (a.gate && a.gate[b] == 0) return;
   const double* sumsq = a.ss[l];
   double s = 0.0;
   for (int i = threadIdx.x; i < np; i += 256) s += sumsq[(size_t)b * np + i];
@@ -2034,13 +2056,16 @@ template <typename T, bool BWD> constexpr int conv_shape(int cls) { return (size
 struct ConvPlan { bool small; int gx, gy, kid; double flops, bytes; };
 template <typename T, bool BWD>
 static ConvPlan conv_plan(ConvArgs& a, bool pool) {
-  a.tiles_x = (a.W + 31) / 32;
+  const int txf = (a.W + 31) / 32;
+  a.tiles_x = a.col_tiles ? a.col_tiles : txf - a.col_begin;
+  if (a.col_begin + a.tiles_x > txf) a.tiles_x = txf - a.col_begin;
   a.tiles_y = (a.H - a.row_begin + 7) / 8;
+  const int Wc = (a.col_begin + a.tiles_x == txf ? a.W : (a.col_begin + a.tiles_x) * 32) - a.col_begin * 32;      // computed columns
   // (the 64-channel block at three workgroups per CU for the Cout >= 128 layers as well: 259 against 244 us per launch, same-box A/B)
   const bool big = a.Cout >= 128;
   ConvPlan p{};
   p.gy = big ? a.Cout / 128 : 1;
-  const size_t es = sizeof(T), P = (size_t)a.B * (a.H - a.row_begin) * a.W, Po = pool ? P / 4 : P;
+  const size_t es = sizeof(T), P = (size_t)a.B * (a.H - a.row_begin) * Wc, Po = pool ? P / 4 : P;
   p.flops = 2.0 * 9.0 * (a.C1 + a.C2) * a.Cout * (double)P + (a.wg0_part ? 2.0 * 27 * 64 * (double)P : 0.0);
   p.bytes = (double)P * ((a.up1 ? a.C1 / 4.0 : a.C1) + a.C2) * es + (double)Po * a.Cout * ((a.out_act ? es : 0) + (a.out_raw ? 4 : 0));
   p.kid = big ? (pool ? K_CONV_NT2_POOL : K_CONV_NT2) : (pool ? K_CONV_NT1_POOL : K_CONV_NT1);

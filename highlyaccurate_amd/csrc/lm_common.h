@@ -95,8 +95,13 @@ __device__ __forceinline__ bool lm_point(const LmPoints& S, int b, int r, int c,
 
 // One ground pixel: satellite coordinates in fp64 from the sample's projection coefficients and the pixel's fp32 point and
 // ground mask (lm_point); clamped-corner bilinear weights with the hard in-bounds mask of jacobian.py:146-177.
+// col0 > 0 (hla_s2g_config.reach_mode = 1): the map holds valid values from column col0 on only.  A pixel that takes part and has
+// a tap left of col0 reports it through *reach (a plain store of 1: every writer stores the same value); a pixel whose weights
+// are all zero reads its taps at (row 0, column col0) instead of (0, 0) -- finite values times zero either way, so no sum changes
+// a bit, but column 0 may be unwritten memory and 0 x NaN is NaN.
 template <int C>
-__device__ __forceinline__ PixParam lm_pixel(const double* cf, const float* q, bool gm, int A, float conf_w) {
+__device__ __forceinline__ PixParam lm_pixel(const double* cf, const float* q, bool gm, int A, float conf_w, int col0 = 0,
+                                             int* reach = nullptr) {
   const double X = q[0], Y = q[1], Z = q[2];
   const double u = cf[0] * X + cf[1] * Y + cf[2] * Z + cf[3];
   const double v = cf[4] * X + cf[5] * Y + cf[6] * Z + cf[7];
@@ -111,6 +116,7 @@ __device__ __forceinline__ PixParam lm_pixel(const double* cf, const float* q, b
     o.wx0 = (float)(x1 - u); o.wx1 = (float)(u - x0);
     o.wy0 = (float)(y1 - v); o.wy1 = (float)(v - y0);
     const int ix0 = (int)x0, iy0 = (int)y0;
+    if (reach && u < (double)col0) *reach = 1;      // (floor(u) < col0)
     o.off = (iy0 * A + ix0) * C;
     o.dxo = ((int)x1 - ix0) * C;
     o.dyo = ((int)y1 - iy0) * A * C;
@@ -120,7 +126,8 @@ __device__ __forceinline__ PixParam lm_pixel(const double* cf, const float* q, b
     o.m = 1.f;
   } else {
     o.wx0 = o.wx1 = o.wy0 = o.wy1 = 0.f;
-    o.off = o.dxo = o.dyo = 0;
+    o.off = col0 * C;
+    o.dxo = o.dyo = 0;
     o.j2u = o.j2v = 0.f;
     o.m = 0.f;
   }

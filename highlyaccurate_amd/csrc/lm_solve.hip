@@ -13,6 +13,7 @@
 //                deterministic), 3x3/2x2/1x1 damped solve, pose update + re-initialisation rule,
 //                and the projection coefficients of the NEXT step (so no extra launch for them).
 #include "lm_common.h"
+#include <cstring>
 #include <mutex>
 
 struct SolveArgs {
@@ -38,6 +39,8 @@ struct SolveArgs {
   // init launch only (part == null): what used to be two hipMemsetAsync launches in front of every forward
   unsigned* zero_ticket; // [steps][B] arrival counters of all steps, or null
   int zero_steps, zero_pose;   // zero_pose: no initial pose was given, start from 0
+  int* reach_clear;      // init launch, hla_s2g_config.reach_mode = 1: [B] reach flags to clear, or null
+  const int* gate;       // reach_mode = 2: [B] reach flags; the launches leave a sample whose flag is 0 alone.  Else null
 };
 
 // One wave closes a step for sample b.  COHERENT: the tile partials were written by OTHER workgroups of the same launch
@@ -46,6 +49,7 @@ template <bool COHERENT>
 __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, int b, int lane) {
   float su = a.pose[b * 3 + 0], sv = a.pose[b * 3 + 1], th = a.pose[b * 3 + 2];
   if (!a.part) {          // the init launch also clears this sample's arrival counters and, without an initial pose, its pose
+    if (a.reach_clear && lane == 0) a.reach_clear[b] = 0;
     if (a.zero_ticket)
       for (int k = lane; k < a.zero_steps; k += 64) a.zero_ticket[(size_t)k * a.B + b] = 0u;
     if (a.zero_pose) {
@@ -113,7 +117,10 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, int b, int lan
 }
 
 // stand-alone launch: the coefficients of step 0 (part == null)
-__global__ __launch_bounds__(64) void lm_solve(SolveArgs a) { lm_solve_body<false>(a, blockIdx.x, threadIdx.x); }
+__global__ __launch_bounds__(64) void lm_solve(SolveArgs a) {
+  if (a.gate && a.gate[blockIdx.x] == 0) return;      // (nothing of a skipped sample is cleared or written)
+  lm_solve_body<false>(a, blockIdx.x, threadIdx.x);
+}
 
 struct AccumArgs {
   const void* sat;    // [B,A,A,C]  F elements (fp32, or bf16 / fp16 in the reduced-precision inference modes)
@@ -128,6 +135,9 @@ struct AccumArgs {
   int hs, rskip;      // stored rows of grd/conf (h - grd_row_skip) and the skip itself
   const unsigned char* keep;   // dropout: [npix] of this step, 1 = pixel takes part; or null
   unsigned* ticket;   // [B] arrival counters of this step (zeroed before the loop): the LAST tile of a sample closes the step
+  int col0;           // reach_mode = 1: first valid column of sat at this level, and
+  int* reach_flag;    //   [B] flags a sample's pixels set when they read left of it (lm_pixel); else 0 / null
+  const int* gate;    // reach_mode = 2: see SolveArgs::gate
 };
 
 // channel pair ep (compile-time after unrolling) of a 16-byte vector of F, as two fp32 in ADJACENT registers: the gather loop is
@@ -180,6 +190,7 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
   __shared__ double redd[14];
   int b, tile;
   if (!lm_block_map(a.xcd_affine, a.nt, a.nb, b, tile, a.b0)) return;
+  if (a.gate && a.gate[b] == 0) return;      // workgroup-uniform, ahead of the first barrier
   const int t = threadIdx.x;
   const int p0 = tile * a.TP;
   const int np = min(a.TP, a.npix - p0);
@@ -191,9 +202,10 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
     const float cw = USE_W ? a.conf[((size_t)b * a.hs + (r - a.rskip)) * a.w + c] : 1.f;
     float q[3];
     const bool gm = lm_point(a.pts, b, r, c, a.w, q);
-    PixParam P = lm_pixel<C>(cf, q, gm, a.A, cw);
-    if (a.keep && !a.keep[p]) {          // dropped by args.dropout: the pixel leaves every sum (models_kitti.py:968-974)
-      P.wx0 = P.wx1 = P.wy0 = P.wy1 = 0.f; P.off = P.dxo = P.dyo = 0; P.j2u = P.j2v = 0.f; P.gm = P.wt = P.m = 0.f;
+    const bool kept = !a.keep || a.keep[p];
+    PixParam P = lm_pixel<C>(cf, q, gm, a.A, cw, a.col0, (a.reach_flag && kept) ? a.reach_flag + b : nullptr);
+    if (!kept) {          // dropped by args.dropout: the pixel leaves every sum (models_kitti.py:968-974)
+      P.wx0 = P.wx1 = P.wy0 = P.wy1 = 0.f; P.off = a.col0 * C; P.dxo = P.dyo = 0; P.j2u = P.j2v = 0.f; P.gm = P.wt = P.m = 0.f;
     }
     pp[tt] = P;
   }
@@ -366,6 +378,8 @@ int hla_s2g_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_l
   HLA_REQUIRE(cfg->dof >= 1 && cfg->dof <= 3, "%s: dof must be 1..3", who);
   HLA_REQUIRE(cfg->proj == 0, "%s: cfg->proj selects the projection of hla_g2s_* only (must be 0 here)", who);
   HLA_REQUIRE(!cfg->ford || (R_FL && T_FL), "%s: Ford mode needs R_FL and T_FL", who);
+  HLA_REQUIRE(cfg->reach_mode == 0 || (!strcmp(who, "hla_s2g_lm_solve") && cfg->reach_mode >= 1 && cfg->reach_mode <= 2 && cfg->reach_flag),
+              "%s: cfg->reach_mode is 0, or 1 / 2 with reach_flag in hla_s2g_lm_solve", who);
   for (int l = 0; l < cfg->n_levels; ++l) {
     const int C = lv[l].C;
     HLA_REQUIRE(C == 256 || C == 128 || C == 64 || C == 16, "%s: unsupported channel count %d", who, C);
@@ -376,6 +390,8 @@ int hla_s2g_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_l
     HLA_REQUIRE(lv[l].row0 >= 0 && lv[l].row0 < lv[l].h, "%s: bad row0", who);
     HLA_REQUIRE(lv[l].grd_row_skip >= 0 && lv[l].grd_row_skip <= lv[l].row0, "%s: grd_row_skip must be in [0,row0]", who);
     HLA_REQUIRE((size_t)lv[l].A * lv[l].A * C < (1u << 31), "%s: satellite map too large", who);
+    HLA_REQUIRE(cfg->reach_mode != 1 || (cfg->reach_col0[l] >= 0 && cfg->reach_col0[l] < lv[l].A),
+                "%s: cfg->reach_col0[%d] must be in [0, A)", who, l);
     if (lv[l].depth) {      // args.use_gt_depth (hla.h): KITTI chain only, all of the depth fields together
       HLA_REQUIRE(!cfg->ford, "%s: level %d: a depth map is not supported with cfg->ford = 1 (models_ford.py has no gt_depth)", who, l);
       HLA_REQUIRE(lv[l].ray && lv[l].depth_row && lv[l].depth_col && lv[l].depth_h > 0 && lv[l].depth_w > 0,
@@ -492,8 +508,11 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   // init launch: coefficients of step 0
   sa.part = nullptr; sa.next = geom(step_level(0));
   sa.zero_ticket = ticket; sa.zero_steps = steps; sa.zero_pose = pose0 ? 0 : 1;
+  // (reach_mode 2: the arrival counters and the pose of a skipped sample are never looked at, so they need no care)
+  sa.reach_clear = cfg->reach_mode == 1 ? cfg->reach_flag : nullptr;
+  sa.gate = cfg->reach_mode == 2 ? cfg->reach_flag : nullptr;
   hipLaunchKernelGGL(lm_solve, dim3(B), dim3(64), 0, st, sa);
-  sa.zero_ticket = nullptr; sa.zero_steps = 0; sa.zero_pose = 0;
+  sa.zero_ticket = nullptr; sa.zero_steps = 0; sa.zero_pose = 0; sa.reach_clear = nullptr;
 
   // Sample ranges of the stream groups (comment above LM_GROUPS).  One group -- today's loop on the caller's stream -- for a
   // small batch, under the event profiler (its event pairs sit on the launch stream, and a per-kernel time must stay the time
@@ -501,7 +520,7 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   int ng = 1, gb0[LM_GROUPS + 1] = {0};
   LmSideStreams* side = nullptr;
   std::unique_lock<std::mutex> side_lock;
-  if (B >= LM_SPLIT_MIN && !hla_prof_on()) {
+  if (B >= LM_SPLIT_MIN && !hla_prof_on() && cfg->reach_mode != 2) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     int d = -1;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess || hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = -1; }
@@ -542,6 +561,8 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
     aa.TP = lm_pick_tile_fwd(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.part_ld = part_ld;
     aa.xcd_affine = (B >= 8) ? 1 : 0;
     aa.ticket = ticket + (size_t)k * B;
+    if (cfg->reach_mode == 1) { aa.col0 = cfg->reach_col0[l]; aa.reach_flag = cfg->reach_flag; }
+    aa.gate = sa.gate;
     // the step's closing solve runs inside the same launch (last tile of each sample): its arguments
     sa.t = k;
     sa.part = part; sa.nt = aa.nt; sa.sat_inv = v.sat_inv_norm; sa.grd_inv = v.grd_inv_norm;

@@ -54,7 +54,8 @@ struct VggConvSet {
 };
 template <typename T>
 static void vgg_build_convs(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                            bool want_conf, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, VggConvSet& S) {
+                            bool want_conf, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
+                            const int* col_gate, VggConvSet& S) {
   const bool level4 = pl.x2r != 0;
   // HLA_VGG_FOLD_DECODER (VGGUnet_G2S, VGG.py:278-310): the maps behind the encoder are read as [2h, w/2].  On NHWC storage
   // that is the same buffer, so only the geometry the decoder launches are given changes: dH(d), dW(d) for the 1/d maps.
@@ -68,6 +69,19 @@ static void vgg_build_convs(const float* x, size_t x_plane, const hla_vgg_params
   unsigned* amax = (unsigned*)(w + pl.amax);                                           // split mode: [slot][B]
   auto AM = [&](int slot) { return (SPLIT && slot >= 0) ? amax + (size_t)slot * B : (unsigned*)nullptr; };
   const bool train = flags & HLA_VGG_SAVE_FOR_BACKWARD;
+  // first_col32 = c > 0 (hla_vgg_forward has checked that nothing else reads the maps): every layer starts at tile column c, 2c or
+  // 4c of its own resolution -- the same COLUMN of the image at every resolution, so the three 2x2 pools and the 32-pixel tiles
+  // stay aligned.  A layer's left halo column was then never written by its producer and is read as zero (ConvArgs::col_begin),
+  // so its first columns are not the full run's: with conv2 exact from its first column (it computes conv0's halo itself) the
+  // first exact column is 64c (x3), 64c+1 (conv5), 64c+2 (conv7) -> 32c+1 (x8), 32c+2 / +3 / +4 (conv10 / 12 / 14) -> 16c+2 (x15),
+  // 32c+5 / +6 (dec1.1 / dec1.3 = x18), 64c+13 / +14 (dec2.1 / dec2.3 = x21).
+  // col_gate (the fix-up pass): the same layers over the columns that pass left wrong -- the skipped strip and, but for conv2, the
+  // tile column behind it -- for the samples whose gate is set.  Every map is then the full run's in every column.
+  const int c = first_col32;
+  auto cols = [&](int scale, bool exact_from_start, int& begin, int& tiles) {
+    begin = col_gate ? 0 : c * scale;
+    tiles = col_gate ? c * scale + (exact_from_start ? 0 : 1) : 0;
+  };
   S = VggConvSet{};
   S.ok = true;
   for (int l = 0; l < 4; ++l) S.np_used[l] = pl.np[l];
@@ -87,7 +101,11 @@ static void vgg_build_convs(const float* x, size_t x_plane, const hla_vgg_params
     // (first_row8, see below: x3 is needed from row 4f-16 on = conv2 row 8f-32)
     const int f0 = (level4 || train) ? 0 : first_row8;
     a.row_begin = f0 ? 8 * f0 - 32 : 0;
-    a.B = B; a.H = H; a.W = W; a.tiles_x = (W + 31) / 32; a.tiles_y = (H - a.row_begin + 7) / 8;
+    int ct;
+    cols(4, true, a.col_begin, ct);
+    a.gate = col_gate;
+    const int txf = (W + 31) / 32;
+    a.B = B; a.H = H; a.W = W; a.tiles_x = ct ? (ct < txf ? ct : txf) : txf - a.col_begin; a.tiles_y = (H - a.row_begin + 7) / 8;
   }
   auto conv = [&](int l, const void* s1, int C1, int H_, int W_h, void* act, int relu, bool pool, const void* s2 = nullptr,
                   int C2 = 0, int up1 = 0, void* raw = nullptr, double* ss = nullptr, unsigned char* idx = nullptr,
@@ -102,6 +120,8 @@ static void vgg_build_convs(const float* x, size_t x_plane, const hla_vgg_params
     S.used[l] = true; S.pool[l] = pool;
     a.raw16 = (raw && (flags & HLA_VGG_FEAT16)) ? 1 : 0;
     a.row_begin = row_begin < 0 ? 0 : row_begin;
+    cols(c ? W_h / (W / 4) : 1, false, a.col_begin, a.col_tiles);      // (c > 0: never the folded or the level-4 geometry)
+    a.gate = col_gate;
     a.idx_out = train ? idx : nullptr;
     a.src1 = s1; a.src2 = s2;
     a.C1 = C1; a.C2 = C2; a.up1 = up1; a.wpk = W_(l);
@@ -167,7 +187,10 @@ static int launch_conv02(hipStream_t st, Conv02Args a, const Conv02Args* a1) {
     g_hla_stamp.grid_x = a.tiles_x * a.tiles_y * a.B; g_hla_stamp.grid_y = 1;
   }
 #endif
-  auto P = [](const Conv02Args& c) { return (double)c.B * (c.H - c.row_begin) * c.W; };
+  auto P = [](const Conv02Args& c) {
+    const int x1 = (c.col_begin + c.tiles_x) * 32;
+    return (double)c.B * (c.H - c.row_begin) * ((x1 < c.W ? x1 : c.W) - c.col_begin * 32);
+  };
   const double Pt = P(a) + (a1 ? P(*a1) : 0.0);
   if (a1) {
     static HlaPerDeviceOnce attr_once;
@@ -196,8 +219,9 @@ static int launch_conv02(hipStream_t st, Conv02Args a, const Conv02Args* a1) {
 // L2 normalisation: 1/||x|| per sample (always) for the NL levels of `nb` networks in one launch, then the in-place scaling unless
 // the caller folds it downstream
 struct VggNormNet { const VggConvSet* S; char* ws; const VggPlan* pl; double* inv_norm; void* const* feat; int H, W; };
-static int vgg_norms(hipStream_t st, int nb, const VggNormNet* net, int B, int NL, int flags) {
+static int vgg_norms(hipStream_t st, int nb, const VggNormNet* net, int B, int NL, int flags, const int* gate = nullptr) {
   InvNormArgs ia{};
+  ia.gate = gate;
   double bytes = 0;
   for (int k = 0; k < nb; ++k)
     for (int l = 0; l < NL; ++l) {
@@ -227,7 +251,7 @@ static int vgg_norms(hipStream_t st, int nb, const VggNormNet* net, int B, int N
 template <typename T>
 int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
                          float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
-                         int flags, int first_row8, hipStream_t st) {
+                         int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st) {
   const bool level4 = pl.x2r != 0;
   const int NL = level4 ? 4 : 3;
   const bool fold = (flags & HLA_VGG_FOLD_DECODER) != 0;
@@ -238,7 +262,7 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   if (SPLIT) HLA_CHECK_HIP(hipMemsetAsync(w + pl.amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
   const bool want_conf = (flags & HLA_VGG_WANT_CONF) && conf;
   VggConvSet S;
-  vgg_build_convs<T>(x, x_plane, prm, packed, dtype, feat, want_conf, ws, pl, B, H, W, flags, first_row8, S);
+  vgg_build_convs<T>(x, x_plane, prm, packed, dtype, feat, want_conf, ws, pl, B, H, W, flags, first_row8, first_col32, col_gate, S);
   if (!S.ok) return HLA_ERR_ARG;
   if (const int rc = launch_conv02<T>(st, S.c02, nullptr)) return rc;
   bool launch_ok = true;
@@ -263,7 +287,7 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   }
   {
     const VggNormNet net{&S, ws, &pl, inv_norm, feat, H, W};
-    if (const int rc = vgg_norms(st, 1, &net, B, NL, flags)) return rc;
+    if (const int rc = vgg_norms(st, 1, &net, B, NL, flags, col_gate)) return rc;
   }
   HLA_CHECK_HIP(hipGetLastError());
   return launch_ok ? HLA_OK : HLA_ERR_ARG;
@@ -273,13 +297,21 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
 // two segments.  The caller (hla_vgg_forward_pair) has checked the flags; returns HLA_PAIR_FALLBACK with nothing launched when a
 // layer's two segments would not take the same kernel instantiation (the two sides of CONV_SMALL_GRID).
 constexpr int HLA_PAIR_FALLBACK = -1000;
+// Where first_col32 applies (include/hla.h); 0 elsewhere.  Not in split-fp16 mode: there every layer scales its operands by the
+// per-sample maximum of the WHOLE source map, which a trimmed forward does not know.
+static inline int vgg_first_col32(int first_col32, int level, int dtype, int flags) {
+  const bool ok = level == 3 && dtype != HLA_F16X3 && (flags & HLA_VGG_DEFER_NORM) &&
+                  !(flags & (HLA_VGG_SAVE_FOR_BACKWARD | HLA_VGG_FOLD_DECODER | HLA_VGG_WANT_CONF));
+  return ok ? first_col32 : 0;
+}
+static inline int pair_first_col32(const hla_vgg_branch& b, int dtype, int flags) { return vgg_first_col32(b.first_col32, 3, dtype, flags); }
 template <typename T>
 int vgg_forward_pair_t(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st) {
   constexpr bool SPLIT = Prec<T>::SPLIT;
   VggConvSet S[2];
   for (int k = 0; k < 2; ++k) {
     vgg_build_convs<T>(br[k].x, br[k].x_plane, br[k].params, (const char*)br[k].packed_weights, dtype, br[k].feat, false,
-                       (char*)br[k].workspace, pl[k], B, br[k].H, br[k].W, flags, br[k].first_row8, S[k]);
+                       (char*)br[k].workspace, pl[k], B, br[k].H, br[k].W, flags, br[k].first_row8, pair_first_col32(br[k], dtype, flags), nullptr, S[k]);
     if (!S[k].ok) return HLA_ERR_ARG;
   }
   for (int l = 2; l < kAllLayers; ++l) {
@@ -308,12 +340,12 @@ int vgg_forward_pair_t(const hla_vgg_branch br[2], const VggPlan pl[2], int B, i
 template void vgg_pack_all<TuT>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st);
 template int vgg_forward_t<TuT>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
-                              int flags, int first_row8, hipStream_t st);
+                              int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st);
 template int vgg_forward_pair_t<TuT>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
 #else
 #define HLA_EXTERN_T(T) \
   extern template void vgg_pack_all<T>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st); \
-  extern template int vgg_forward_t<T>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,                               int flags, int first_row8, hipStream_t st);
+  extern template int vgg_forward_t<T>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,                               int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st);
 HLA_EXTERN_T(float) HLA_EXTERN_T(bf16) HLA_EXTERN_T(f16) HLA_EXTERN_T(split32)
 #define HLA_EXTERN_PAIR_T(T) \
   extern template int vgg_forward_pair_t<T>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
@@ -351,6 +383,14 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
                                void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
                                size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
                                int first_row8, hla_stream_t stream) {
+  return hla_vgg_forward_cols(x, x_plane, params, packed_weights, feat, conf, inv_norm, workspace, workspace_bytes, B, H, W, level, dtype,
+                              flags, first_row8, 0, nullptr, stream);
+}
+
+extern "C" int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
+                                    void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
+                                    size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
+                                    int first_row8, int first_col32, const int* col_gate, hla_stream_t stream) {
   HLA_REQUIRE(x && params && packed_weights && feat && workspace, "hla_vgg_forward: null argument");
   HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_forward: dtype must be HLA_F32, HLA_BF16, HLA_F16 or HLA_F16X3 (got %d)", dtype);
   HLA_REQUIRE(B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, "hla_vgg_forward: H and W must be multiples of 8");
@@ -373,6 +413,11 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
   HLA_REQUIRE(!(flags & HLA_VGG_FOLD_DECODER) || (W % 16 == 0 && first_row8 == 0 && !(flags & HLA_VGG_FEAT16)),
               "hla_vgg_forward: HLA_VGG_FOLD_DECODER needs W %% 16 == 0 (folded maps are W/16, W/8, W/4 wide), first_row8 == 0 and no "
               "HLA_VGG_FEAT16 (got W = %d, first_row8 = %d)", W, first_row8);
+  HLA_REQUIRE(first_col32 >= 0 && (first_col32 == 0 || 128 * first_col32 < W),
+              "hla_vgg_forward_cols: first_col32 must be 0 or leave a column of the map (128 * first_col32 < W; got %d, W = %d)", first_col32, W);
+  HLA_REQUIRE(!col_gate || first_col32 > 0, "hla_vgg_forward_cols: col_gate is the fix-up pass of a forward made with first_col32 > 0");
+  first_col32 = vgg_first_col32(first_col32, level, dtype, flags);
+  if (col_gate && !first_col32) return HLA_OK;      // that forward computed every column: nothing to fix
   VggPlan pl;
   vgg_plan(B, H, W, dtype, (flags & HLA_VGG_SAVE_FOR_BACKWARD) != 0, &pl, level == 4, (flags & HLA_VGG_FOLD_DECODER) != 0);
   if (workspace_bytes < pl.total) {
@@ -381,15 +426,15 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
   }
   if (dtype == HLA_BF16)
     return vgg_forward_t<bf16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                               B, H, W, flags, first_row8, (hipStream_t)stream);
+                               B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
   if (dtype == HLA_F16)
     return vgg_forward_t<f16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                              B, H, W, flags, first_row8, (hipStream_t)stream);
+                              B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
   if (dtype == HLA_F16X3)
     return vgg_forward_t<split32>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                                  B, H, W, flags, first_row8, (hipStream_t)stream);
+                                  B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
   return vgg_forward_t<float>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                              B, H, W, flags, first_row8, (hipStream_t)stream);
+                              B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
 }
 
 extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level, int dtype, int flags, int* paired_out, hla_stream_t stream) {
@@ -397,8 +442,9 @@ extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level
   if (paired_out) *paired_out = 0;
   auto plain = [&]() -> int {
     for (int k = 0; k < 2; ++k)
-      if (const int rc = hla_vgg_forward(br[k].x, br[k].x_plane, br[k].params, br[k].packed_weights, br[k].feat, br[k].conf, br[k].inv_norm,
-                                         br[k].workspace, br[k].workspace_bytes, B, br[k].H, br[k].W, level, dtype, flags, br[k].first_row8, stream))
+      if (const int rc = hla_vgg_forward_cols(br[k].x, br[k].x_plane, br[k].params, br[k].packed_weights, br[k].feat, br[k].conf, br[k].inv_norm,
+                                         br[k].workspace, br[k].workspace_bytes, B, br[k].H, br[k].W, level, dtype, flags, br[k].first_row8,
+                                         br[k].first_col32, nullptr, stream))
         return rc;
     return HLA_OK;
   };
@@ -411,7 +457,8 @@ extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level
                     (b.x_plane == 0 || b.x_plane >= (size_t)b.H * b.W) && (size_t)b.H * b.W * 64 * 4 < ((size_t)1 << 31) &&
                     b.feat[0] && b.feat[1] && b.feat[2] && (!(flags & HLA_VGG_DEFER_NORM) || b.inv_norm) &&
                     (!(flags & HLA_VGG_FEAT16) || ((dtype == HLA_BF16 || dtype == HLA_F16) && (flags & HLA_VGG_DEFER_NORM))) &&
-                    (b.first_row8 == 0 || (b.first_row8 >= 4 && b.first_row8 < b.H / 8));
+                    (b.first_row8 == 0 || (b.first_row8 >= 4 && b.first_row8 < b.H / 8)) &&
+                    b.first_col32 >= 0 && (b.first_col32 == 0 || 128 * b.first_col32 < b.W);
     if (!ok) return plain();
     vgg_plan(B, b.H, b.W, dtype, false, &pl[k], false, false);
     if (b.workspace_bytes < pl[k].total) return plain();

@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 28
+#define HLA_ABI_VERSION 29
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -144,6 +144,24 @@ int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_params* params
                     float* const conf[4], double* inv_norm, void* workspace, size_t workspace_bytes, int B, int H,
                     int W, int level, int dtype, int flags, int first_row8, hla_stream_t stream);
 
+/* hla_vgg_forward with a first COLUMN as well (hla_vgg_forward is this call with first_col32 = 0, col_gate = NULL).
+ * first_col32  0, or c >= 1 with 128 c < W, the column twin of first_row8: a promise that the caller reads feat[0] / feat[1] /
+ *          feat[2] only from columns 16c+2 / 32c+6 / 64c+14 on.  Every layer then starts at its 32-pixel tile column c (the H/4
+ *          layers), 2c (H/2) or 4c (conv0 + conv2) and reads the source columns left of it as zero: columns 16c / 32c / 64c up to
+ *          the promised ones are written but are NOT the full forward's values, the columns left of them stay unwritten, the
+ *          promised ones are the full forward's bit for bit; inv_norm covers the written columns.  Applies at level 3 with
+ *          HLA_VGG_DEFER_NORM and a dtype other than HLA_F16X3, without HLA_VGG_SAVE_FOR_BACKWARD / HLA_VGG_FOLD_DECODER /
+ *          HLA_VGG_WANT_CONF; treated as 0 otherwise (the whole map is computed).
+ * col_gate  NULL, or [B] int32 on the device: the FIX-UP pass of an earlier call with the same arguments and first_col32 > 0,
+ *          on the same buffers (workspace included, untouched in between).  For every sample with col_gate[b] != 0 the layers
+ *          are computed again over the columns that call left unwritten or wrong, and inv_norm again: that sample's maps,
+ *          sum-of-squares partials and inv_norm are then what a call with first_col32 = 0 leaves, bit for bit.  A sample with
+ *          col_gate[b] == 0 is not touched (its workgroups return at once).  hla_s2g_lm_solve sets such flags (reach_flag). */
+int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
+                         void* const feat[4], float* const conf[4], double* inv_norm, void* workspace, size_t workspace_bytes,
+                         int B, int H, int W, int level, int dtype, int flags, int first_row8, int first_col32,
+                         const int* col_gate, hla_stream_t stream);
+
 /* One network of hla_vgg_forward_pair: the per-network arguments of hla_vgg_forward, with the same meaning. */
 typedef struct hla_vgg_branch {
   const float* x;
@@ -156,6 +174,7 @@ typedef struct hla_vgg_branch {
   void* workspace;
   size_t workspace_bytes;
   int H, W, first_row8;
+  int first_col32;
 } hla_vgg_branch;
 
 /* The inference forward of TWO networks on batches of one size B (the satellite and the ground extractor of LM_S2GP): computes
@@ -361,6 +380,19 @@ typedef struct hla_s2g_config {
                              workspace, its memset and the closing pass */
   int proj;               /* hla_g2s_* only.  0: proj == 'geo', the camera chain.  1: proj == 'nn', the
                              in-plane similarity warp of the (folded) ground map (models_kitti.py:289-332).  hla_s2g_* require 0 */
+  int reach_mode;         /* hla_s2g_lm_solve only (0 elsewhere).  0: off.
+                             1, DETECT: the loop runs on satellite maps that are valid from column reach_col0[l] on.  The init
+                                launch clears reach_flag[b]; a pixel that takes part in a step (in view, ground mask set) and has a
+                                bilinear tap left of that column sets reach_flag[b] = 1.  A pixel whose contribution is masked to zero
+                                reads its (zero-weighted) taps at that column instead of column 0.  A sample whose flag stays 0
+                                has read only valid columns: its trace and normal_eq are those of the loop on the whole maps; a
+                                flagged sample's are not meaningful.
+                             2, GATED: the whole loop again for the samples with reach_flag[b] != 0 only (reach_col0 is ignored: the
+                                maps are whole, see hla_vgg_forward's col_gate); every workgroup of a sample whose flag is 0 returns
+                                at once and that sample's trace / normal_eq entries are left as they are.  Runs on `stream` alone. */
+  int* reach_flag;        /* [B] int32 on the device; required iff reach_mode != 0 */
+  int reach_col0[4];      /* reach_mode 1: per level, the first column of levels[l].sat_feat that holds valid values, in [0, A_l) (maps
+                             made with hla_vgg_forward_cols' first_col32: 16c+2 / 32c+6 / 64c+14); 0 = the whole map */
 } hla_s2g_config;
 
 size_t hla_s2g_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B);
