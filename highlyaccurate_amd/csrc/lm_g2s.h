@@ -159,6 +159,7 @@ static inline G2sGeom g2s_geom_of(const hla_s2g_config* cfg, const hla_s2g_level
 static inline int g2s_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_level* lv, const float* camera_k, int ori_h,
                                int ori_w, bool need_camera = true) {
   HLA_REQUIRE(cfg->proj == 0 || cfg->proj == 1, "%s: cfg->proj must be 0 (geo) or 1 (in-plane), got %d", who, cfg->proj);
+  HLA_REQUIRE(cfg->reach_mode == 0, "%s: cfg->reach_mode belongs to hla_s2g_lm_solve (must be 0 here)", who);
   if (cfg->proj == 0) HLA_REQUIRE(!need_camera || (camera_k && ori_h > 0 && ori_w > 0), "%s: proj 0 needs camera_k and the ground image size", who);
   else HLA_REQUIRE(!cfg->using_weight, "%s: proj 1 has no weighted variant (using_weight must be 0)", who);
   for (int l = 0; l < cfg->n_levels; ++l) {

@@ -1,5 +1,6 @@
 """fp64-capable reference of ONE step of the satellite->ground LM pose loop with free geometry, and the seeded inputs of
-``tests/test_lm_kernel_ref_cpu.py`` / ``tests/test_lm_kernels_vs_fp64.py``.
+``tests/test_lm_kernel_ref_cpu.py`` / ``tests/test_lm_kernels_vs_fp64.py``; at the end, the rule of the reach flag and the inputs of
+``tests/test_lm_reach_ref_cpu.py`` / ``tests/test_lm_reach_vs_fp64.py``.
 
 ``oracle.ref_cpu`` derives the satellite map's metres-per-pixel and centre from its side A and takes the ground points from the
 camera model; the C ABI (``hla_s2g_lm_solve`` / ``hla_s2g_lm_solve_bwd``) takes any ``h, w, row0, grd_row_skip, A, C,
@@ -312,3 +313,230 @@ def drop_sample(geom, levels, p0, rand_uv, b):
         o.sat, o.grd, o.conf = lv.sat[sel].contiguous(), lv.grd[sel].contiguous(), lv.conf[sel].contiguous()
         lvs.append(o)
     return g, lvs, p0[sel].contiguous(), rand_uv[:, :, sel].contiguous()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the reach flag (hla_s2g_config.reach_mode = 1): the rule, and inputs with pixels exactly on the column border
+# ----------------------------------------------------------------------------------------------------------------------
+def reach_pixels(geom, lv, pose, keep=None):
+    """The pixels of one step that can set the flag, and their u: rows >= row0, kept, table z > 0, inside the map.
+    pose = (su, sv, th), each [B,1], in the precision to compute in; keep [(h - row0) * w] or None.  -> part, u: [B, (h - row0) * w]."""
+    uv, _, mask = level_uv(cast_geom(geom, pose[0].dtype), lv, pose)
+    u, v = uv[:, lv.row0:, :, 0], uv[:, lv.row0:, :, 1]
+    lim = lv.A - 1
+    part = (u >= 0) & (u <= lim) & (v >= 0) & (v <= lim) & (mask[:, lv.row0:] > 0)
+    if keep is not None:
+        part = part & torch.as_tensor(keep).bool().reshape(1, lv.h - lv.row0, lv.w)
+    B = u.shape[0]
+    return part.reshape(B, -1), u.reshape(B, -1)
+
+
+def _step_keep(keep, k, lv):
+    return None if keep is None else keep[k, :(lv.h - lv.row0) * lv.w]
+
+
+def reach_flags(geom, levels, poses_per_step, col0, keep=None):
+    """flag[b] = 1 iff in some step a pixel that is read (rows >= row0), kept by that step's dropout mask, has table z > 0 and lies
+    inside the map has u < col0[level].  A pixel with zero confidence counts (its taps are read all the same).
+    poses_per_step: [(level index, (su, sv, th))] in execution order, the pose every sample has when the step starts;
+    keep [steps, max npix] or None.  -> int32 [B]."""
+    flag = None
+    for k, (l, pose) in enumerate(poses_per_step):
+        part, u = reach_pixels(geom, levels[l], pose, _step_keep(keep, k, levels[l]))
+        hit = (part & (u < col0[l])).any(1)
+        flag = hit if flag is None else flag | hit
+    return flag.to(torch.int32)
+
+
+def reach_margin(geom, levels, poses_per_step, col0, keep=None):
+    """min |u - col0[level]| over the steps and the pixels ``reach_flags`` looks at, per sample [B] (inf: no such pixel)."""
+    best = None
+    for k, (l, pose) in enumerate(poses_per_step):
+        part, u = reach_pixels(geom, levels[l], pose, _step_keep(keep, k, levels[l]))
+        d = torch.where(part, (u - col0[l]).abs().double(), torch.full_like(u, float('inf'), dtype=torch.float64)).min(1).values
+        best = d if best is None else torch.minimum(best, d)
+    return best
+
+
+# KITTI chain, A = 16, mpp = 0.5: the ground mask z > 0 is u > A / 2 = 8 at theta = 0, so a pixel that takes part AND lies left of
+# the first valid column needs that column right of the centre.
+REACH_A, REACH_COL0 = 16, 10
+REACH_LEFT = (-EPS, -1.0, -1.0 + EPS)          # offsets from col0 of the targets that must set the flag
+# Samples differ by pose only.  At theta = 0 a dyadic shift_u = s moves every u by exactly 12 s px (lon = 6 m, mpp = 0.5) and
+# leaves v alone; shift_v = 0.25 moves every v by exactly -3 px and leaves u alone (fp32 and fp64 alike).
+REACH_SHIFT = 2.0 ** -14                       # 3 EPS in u
+REACH_POSES = ((0.0, 0.0, 0.0), (-REACH_SHIFT, 0.0, 0.0), (REACH_SHIFT, 0.0, 0.0), (0.0, 0.25, 0.0))
+
+
+def reach_table(h, w, row0, seed, col0=REACH_COL0, A=REACH_A, extra=(), mpp=0.5):
+    """-> (table [h,w,3] fp32, target u [h,w], target v [h,w]) of a KITTI level whose smallest u among the pixels that take part at
+    pose 0 is EXACTLY col0.  From the first pixel read, (row0, 0), on:
+      {col0, col0 + EPS} x the ten border classes of v                                  (in view: on / just right of the column)
+      {col0 - EPS, col0 - 1, col0 - 1 + EPS} x {-EPS, A - 1 + EPS} in v                 (left of it, but outside the map in v)
+      {A / 2, A / 2 - 1.5, -EPS} x {A / 2, 1.25} in v                                   (left of it, but z <= 0; the last one u < 0 too)
+    then random targets right of the column: u in [col0 + 2^-10, A + 1], v in [-2, A + 1], on a 2^-10 grid.
+    extra: ((row, column), u, v) targets written over that list afterwards."""
+    centre = centre_of(0, A)
+    vals = border_values(A)
+    tu = [col0 + d for d in (0.0, EPS) for _ in vals] + [col0 + d for d in REACH_LEFT for _ in range(2)] + \
+         [x for x in (A / 2, A / 2 - 1.5, -EPS) for _ in range(2)]
+    tv = vals * 2 + [-EPS, A - 1 + EPS] * 3 + [A / 2, 1.25] * 3
+    n, m = h * w, len(tu)
+    rs = np.random.RandomState(seed)
+    fu = np.round(rs.uniform(col0 + 2.0 ** -10, A + 1.0, size=n - m) * 1024) / 1024
+    fv = np.round(rs.uniform(-2.0, A + 1.0, size=n - m) * 1024) / 1024
+    pos = (row0 * w + np.arange(n)) % n
+    U, V = np.empty(n), np.empty(n)
+    U[pos], V[pos] = np.concatenate([tu, fu]), np.concatenate([tv, fv])
+    U, V = U.reshape(h, w), V.reshape(h, w)
+    for (r, c), eu, ev in extra:
+        U[r, c], V[r, c] = eu, ev
+    return torch.from_numpy(table_from_targets(0, U, V, mpp, centre)), U, V
+
+
+def make_reach_level(shape, C, B, seed, extra=(), dtype=torch.float32, col0=REACH_COL0, A=REACH_A, mpp=0.5):
+    """``make_level``'s maps on a ``reach_table``."""
+    lv = make_level(0, shape, C, A, B, seed, mpp, dtype)
+    lv.table, lv.tu, lv.tv = reach_table(lv.h, lv.w, lv.row0, seed, col0, A, extra, mpp)
+    lv.ku = lv.kv = None
+    return lv
+
+
+def nan_strip(lv, col0):
+    """The level with the satellite map's columns left of col0 set to NaN: what a trimmed extractor leaves there at worst."""
+    o = SimpleNamespace(**vars(lv))
+    o.sat = lv.sat.clone()
+    o.sat[..., :col0] = float('nan')
+    return o
+
+
+def reach_poses(idx):
+    """pose0 [B,3] fp32 from indices into REACH_POSES."""
+    return torch.tensor([REACH_POSES[i] for i in idx], dtype=torch.float32)
+
+
+# The moving-pose cases: two levels that differ in C, shape, A, mpp AND first valid column, 2 iterations.  Per level six pixels sit
+# REACH2_GAP px right of the column, in a band of v of their own, and every other pixel at least half a pixel further right: so
+# whether a sample crosses at a level is decided by how far its shift_u travels (12 px / 8 px per unit at the two levels) and by
+# whether its shift_v has moved that level's six out of the map (shift_v = -0.25: +3 px / +2 px in v).
+#                 shape    C    A   mpp  col0  v band of the six
+REACH2_LEVELS = (('ragged', 128, 16, 0.5, 10, (12.5, 14.5)), ('mid', 16, 13, 0.75, 8, (2.0, 6.0)))
+REACH2_COL0 = tuple(v[4] for v in REACH2_LEVELS)
+REACH2_GAP = 0.5
+
+
+def reach2_table(h, w, row0, seed, col0, A, mpp, band):
+    """Six pixels among the rows read AT u = col0 + REACH2_GAP, v spread over ``band``; random targets for the others: u in
+    [col0 + REACH2_GAP + 0.5, A + 1], v in [-2, A + 1] (2^-10 grid), every eighth of them masked (u <= A / 2)."""
+    n = h * w
+    rs = np.random.RandomState(seed)
+    U = np.round(rs.uniform(col0 + REACH2_GAP + 0.5, A + 1.0, size=n) * 1024) / 1024
+    V = np.round(rs.uniform(-2.0, A + 1.0, size=n) * 1024) / 1024
+    U[::8] = np.round(rs.uniform(-2.0, A / 2, size=len(U[::8])) * 1024) / 1024
+    near = row0 * w + 5 + 29 * np.arange(6)
+    U[near], V[near] = col0 + REACH2_GAP, np.linspace(band[0], band[1], 6)
+    U, V = U.reshape(h, w), V.reshape(h, w)
+    return torch.from_numpy(table_from_targets(0, U, V, mpp, centre_of(0, A))), U, V
+
+
+def make_reach2_case(seed, p0):
+    """-> (geom, levels, pose0 [B,3] fp32, rand_uv [4,2,B] fp32, keep [4, max npix] uint8) of the moving-pose cases (KITTI)."""
+    p0 = torch.tensor(p0, dtype=torch.float32)
+    B = p0.shape[0]
+    levels = []
+    for l, (s, C, A, mpp, col0, band) in enumerate(REACH2_LEVELS):
+        lv = make_level(0, s, C, A, B, seed + 10 * l, mpp)
+        lv.table, lv.tu, lv.tv = reach2_table(lv.h, lv.w, lv.row0, seed + 10 * l + 5, col0, A, mpp, band)
+        lv.ku = lv.kv = None
+        levels.append(lv)
+    rs = np.random.RandomState(seed + 77)
+    rand_uv = rs.uniform(-1, 1, size=(4, 2, B)).astype(np.float32)
+    npix = [(lv.h - lv.row0) * lv.w for lv in levels]
+    keep = (rs.uniform(size=(4, max(npix))) < 0.5).astype(np.uint8)
+    return make_geom(0, B), levels, p0, torch.from_numpy(rand_uv), torch.from_numpy(keep)
+
+
+def trajectory(geom, levels, p0, rand_uv, N, level_first, using_weight, keep, dt):
+    """The reference's own trajectory in ``dt``: [(level, pose at the start of the step)], and the pose after the last step."""
+    args = update_args()
+    g, lvs = cast_geom(geom, dt), [cast_level(lv, dt) for lv in levels]
+    pose = pose_cols(p0, dt)
+    out = []
+    for k, (i, l) in enumerate(step_order(len(levels), N, level_first)):
+        out.append((l, pose))
+        kp = _step_keep(keep, k, lvs[l])
+        pose = level_step(args, g, lvs[l], pose, using_weight, tuple(rand_uv[k, j][:, None].to(dt) for j in range(2)),
+                          keep=None if kp is None else kp.bool())
+    return out, pose
+
+
+# level_first -> (dropout keep masks, pose0).  Sample 0 never crosses (though at level 1 it reads left of col0[0] = 10 all the time);
+# sample 1 crosses under col0[0] at level 0 and never under col0[1]; sample 2 (a whole map's width to the left) in every step;
+# sample 3 -- shift_v = -0.25 has moved level 0's six pixels out of the map -- only at level 1 and only in iteration 2, when its
+# shift_u has drifted past -REACH2_GAP / 8.  Found by sweeping shift_u over the fp64 reference's own trajectory for the largest
+# distance from the column (tests/test_lm_reach_ref_cpu.py asserts the pattern and the margin).
+REACH2_CASES = {
+    0: (0, [[0.05, 0.01, -0.02], [-0.046, 0.0, 0.0], [-1.0, 0.0, 0.0], [-481 / 8192, -0.25, 0.0]]),
+    1: (1, [[0.05, 0.01, -0.02], [-0.0435, 0.0, 0.0], [-1.0, 0.0, 0.0], [-371 / 8192, -0.25, 0.0]]),
+}
+REACH2_STEP_FLAGS = {      # [sample][step in execution order], level_first 0: levels 0 1 0 1, level_first 1: levels 0 0 1 1
+    0: [[0, 0, 0, 0], [1, 0, 1, 0], [1, 1, 1, 1], [0, 0, 0, 1]],
+    1: [[0, 0, 0, 0], [1, 1, 0, 0], [1, 1, 1, 1], [0, 0, 0, 1]],
+}
+
+
+def reach2_case(level_first):
+    use_keep, p0 = REACH2_CASES[level_first]
+    geom, levels, p0, rand_uv, keep = make_reach2_case(case_seed('reach2', level_first), p0)
+    return geom, levels, p0, rand_uv, (keep if use_keep else None)
+
+
+def pose_allowance_px(levels, p64, p32, tol_pose=1e-6):
+    """The largest pixel displacement at any of ``levels`` that the pose gate of tests/test_lm_kernels_vs_fp64.py --
+    max(tol_pose, 2 |ref32 - ref64|) per component -- lets a pose error cause: (lon / mpp) d_su + (lat / mpp) d_sv + rotation x radius,
+    with the map's side A as a (generous) radius.  p64 / p32: the pose after one step in the two precisions, (su, sv, th) of [B,1]."""
+    lat, lon, rot = RANGES
+    a, b = torch.cat(p64, 1).double(), torch.cat(p32, 1).double()
+    allow = torch.clamp(2 * (a - b).abs(), min=tol_pose)
+    return max(float((lon / lv.mpp * allow[:, 0] + lat / lv.mpp * allow[:, 1] + rot / 180 * np.pi * allow[:, 2] * lv.A).max())
+               for lv in levels)
+
+
+# The one-level reach cases: name -> (shape, crossing pixel or None, indices into REACH_POSES of the samples, special).  The crossing
+# pixel is ((row, column) -- negative values count from the end --, offset of u from col0, v); special: 'drop' -- a dropout mask
+# that drops it (and every second other pixel), 'conf0' -- its confidence is zero.
+_V = dict(zip(BORDER_CLASSES, border_values(REACH_A)))
+REACH_CASES = {
+    'clean': ('ragged', None, (0, 1, 2, 3), None),
+    'first': ('ragged', (('row0', 0), REACH_LEFT[0], _V['on0']), (0, 2, 1), None),             # the first pixel read
+    'last': ('ragged', ((-1, -1), REACH_LEFT[2], _V['onlim']), (0, 2, 1), None),               # the last pixel of the 3-px last tile
+    'many_last': ('many', ((-1, -2), REACH_LEFT[1], _V['texel']), (0, 2), None),               # in the last of 65 tiles
+    'not_read': ('skip', (('row0-1', 5), REACH_LEFT[0], _V['mid']), (0, 2), None),             # a stored row above row0
+    'dropped': ('ragged', (('row0', 0), REACH_LEFT[0], _V['half']), (0, 2, 1), 'drop'),
+    'conf0': ('ragged', (('row0', 0), REACH_LEFT[0], _V['farcell']), (0, 2, 1), 'conf0'),
+    'idle_blocks': ('octet', None, (0, 2, 0, 2, 0, 2, 0, 2, 1), None),                         # B = 9, the crossing sample last
+    'two_groups': ('octet', None, (1, 0, 2, 0, 2, 0, 2, 0, 2, 0, 2, 0, 2, 0, 2, 1, 1), None),  # B = 17: 0, 15 | 16 cross
+}
+
+
+def reach_case(name, C=64, dtype=torch.float32):
+    """-> (geom, level, pose0 [B,3] fp32, keep [1, npix] uint8 or None, (row, column) of the crossing pixel or None)."""
+    shape, cross, idx, special = REACH_CASES[name]
+    h, w, row0, _ = SHAPES[shape]
+    B = len(idx)
+    seed = case_seed('reach', name)
+    extra, rc = (), None
+    if cross is not None:
+        (r, c), du, v = cross
+        r = {'row0': row0, 'row0-1': row0 - 1}.get(r, r)
+        rc = (r % h, c % w)
+        extra = ((rc, REACH_COL0 + du, v),)
+    lv = make_reach_level(shape, C, B, seed, extra, dtype)
+    keep = None
+    if special == 'drop':
+        keep = (np.random.RandomState(seed + 5).uniform(size=(1, (h - row0) * w)) < 0.5).astype(np.uint8)
+        keep[0, (rc[0] - row0) * w + rc[1]] = 0
+        keep = torch.from_numpy(keep)
+    if special == 'conf0':
+        lv.conf[:, 0, rc[0], rc[1]] = 0
+    return make_geom(0, B), lv, reach_poses(idx), keep, rc

@@ -43,7 +43,8 @@ class _Call:
     """Structs of one hla_s2g_lm_solve / _bwd call and the device tensors they point to."""
 
     def __init__(self, geom, levels, N=1, level_first=0, using_weight=0, use_hessian=0, dof=3, damping=(1.0, 1.0, 1.0), keep=None,
-                 inv_norm=None):
+                 inv_norm=None, reach_mode=0, reach_flag=None, reach_col0=None):
+        """reach_mode / reach_flag (int32 [B] on the device) / reach_col0 (per level): the fields of the same name of hla_s2g_config."""
         from highlyaccurate_amd import _lib
         self.lib, self._lib = _lib.load(), _lib
         d = self.dev = _dev()
@@ -82,23 +83,34 @@ class _Call:
                 s.sat_inv_norm, s.grd_inv_norm = iv[0].data_ptr(), iv[1].data_ptr()
         self.R_FL = geom.R_FL.float().contiguous().to(d) if geom.ford else None
         self.T_FL = geom.T_FL.float().contiguous().to(d) if geom.ford else None
+        self.reach_flag = reach_flag
+        cfg.reach_mode = int(reach_mode)
+        cfg.reach_flag = reach_flag.data_ptr() if reach_flag is not None else None
+        for l, c0 in enumerate(reach_col0 or ()):
+            cfg.reach_col0[l] = int(c0)
 
-    def forward(self, p0, rand_uv):
-        """-> trace [B,N,L,3] fp32, normal_eq [steps,B,16] fp64 (CPU tensors)."""
+    def forward(self, p0, rand_uv, out=None):
+        """-> trace [B,N,L,3] fp32, normal_eq [steps,B,16] fp64 (CPU tensors).  out = (trace, normal_eq, workspace) device tensors
+        to run on (a second call of the reach protocol); NaN-filled fresh ones otherwise.  They are kept in self.trace / .neq / .ws
+        from before the call on, so that a call that fails validation can be shown to have left them alone."""
         d, lib, _lib = self.dev, self.lib, self._lib
         steps = self.L * self.N
         self.p0 = p0.float().contiguous().to(d)
         ruv = rand_uv.float().contiguous().to(d)
         assert tuple(self.p0.shape) == (self.B, 3) and tuple(ruv.shape) == (steps, 2, self.B)
-        trace = torch.full((self.B, self.N, self.L, 3), float('nan'), device=d, dtype=F32)
-        neq = torch.full((steps, self.B, 16), float('nan'), device=d, dtype=F64)
         nbytes = lib.hla_s2g_workspace_bytes(C.byref(self.cfg), self.lv, self.B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        if out is None:
+            trace = torch.full((self.B, self.N, self.L, 3), float('nan'), device=d, dtype=F32)
+            neq = torch.full((steps, self.B, 16), float('nan'), device=d, dtype=F64)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        else:
+            trace, neq, ws = out
+            assert trace.shape == (self.B, self.N, self.L, 3) and neq.shape == (steps, self.B, 16) and ws.numel() == nbytes
+        self.trace, self.neq, self.ws = trace, neq, ws
         rc = lib.hla_s2g_lm_solve(C.byref(self.cfg), self.lv, _lib.ptr(self.R_FL), _lib.ptr(self.T_FL), _lib.ptr(self.p0), _lib.ptr(ruv),
                                   _lib.ptr(trace), _lib.ptr(neq), _lib.ptr(ws), nbytes, self.B, _lib.stream_ptr())
         _lib.check(rc, 'hla_s2g_lm_solve')
         torch.cuda.synchronize()
-        self.trace, self.neq = trace, neq
         return trace.cpu(), neq.cpu()
 
     def backward(self, d_trace, overwrite=1, deterministic=0):

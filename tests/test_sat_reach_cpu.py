@@ -16,6 +16,7 @@ from oracle import ref_cpu as O
 from highlyaccurate_amd import _s2gp
 from highlyaccurate_amd.VGG import promised_cols
 from highlyaccurate_amd.models_kitti import LM_S2GP
+import sat_reach_cases as SC
 
 
 def _brute_force_reach(A, grd_hw, lat, lon, rot, n=5):
@@ -114,3 +115,27 @@ def test_promised_columns_against_the_oracle_extractor():
         assert torch.equal(got[l][..., cols[l]:], ref[l][..., cols[l]:]), l
         assert not torch.equal(got[l][..., cols[l] - 1:], ref[l][..., cols[l] - 1:]), l      # the promise is tight
         assert not torch.equal(moved[l][..., cols[l]:], ref[l][..., cols[l]:]), l
+
+
+def test_trim_cases_of_the_gpu_suite():
+    """tests/test_sat_reach_gpu.py's cases: legal trims, c = 1, 2 and 3, ragged last tiles at every resolution, at most 64
+    sum-of-squares slots per sample and level -- so that a lost or stale slot (about 1 / slots of the sum) cannot hide inside
+    either inv_norm gate --, and where the promised columns lie beyond the map."""
+    assert {c for *_, c in SC.TRIM_CASES} == {1, 2, 3}
+    assert 1.0 / SC.MAX_SLOTS > 4 * SC.TOL_INV_FP16 > SC.TOL_INV_FP32
+    assert SC.TOL_INV_FP16 == 2 * 2.0 ** -10
+    vacuous = set()
+    for precision, feat16, B, H, W, c in SC.TRIM_CASES:
+        assert 128 * c < W and W % 8 == 0 and H % 8 == 0, (W, c)
+        assert not feat16 or precision in ('bf16', 'fp16')
+        slots = SC.slot_counts(H, W)
+        assert all(1 <= n <= SC.MAX_SLOTS for n in slots), (H, W, slots)
+        for l, (strip, first) in enumerate(zip(SC.strip_cols(c), promised_cols(c))):
+            width = W >> (3 - l)
+            assert strip < width and strip < first                 # something is computed, and its first columns are not promised
+            if first >= width:
+                vacuous.add((W, c, l))
+    assert vacuous == {(W, c, l) for W, c in ((264, 2), (392, 3)) for l in range(3)}      # (392 / 8 = 49 < 16 * 3 + 2)
+    for W in (264, 296, 392):
+        assert all((W >> s) % 32 for s in (1, 2, 3)), W             # ragged last tile at H/2, H/4 and on the pooled H/8 map
+    assert max(SC.slot_counts(128, 512)) == SC.MAX_SLOTS
