@@ -45,16 +45,18 @@ struct SolveArgs {
 
 // One wave closes a step for sample b.  COHERENT: the tile partials were written by OTHER workgroups of the same launch
 // (the fused accumulate + solve kernel): read them with agent-scope (sc1) loads, which bypass this CU's L1.
-template <bool COHERENT>
-__device__ __forceinline__ void lm_solve_body(const SolveArgs& a, int b, int lane) {
-  float su = a.pose[b * 3 + 0], sv = a.pose[b * 3 + 1], th = a.pose[b * 3 + 2];
+// LOCAL (lm_repair_loop): the step reads its pose from lpose [3] and leaves the new pose there and the next step's coefficients in
+// lcoef [COEF_N] (null: there is no next step) -- shared memory -- instead of the sample's rows of a.pose / a.coef.
+template <bool COHERENT, bool LOCAL = false>
+__device__ __forceinline__ void lm_solve_body(const SolveArgs& a, int b, int lane, float* lpose = nullptr, double* lcoef = nullptr) {
+  float su = LOCAL ? lpose[0] : a.pose[b * 3 + 0], sv = LOCAL ? lpose[1] : a.pose[b * 3 + 1], th = LOCAL ? lpose[2] : a.pose[b * 3 + 2];
   if (!a.part) {          // the init launch also clears this sample's arrival counters and, without an initial pose, its pose
     if (a.reach_clear && lane == 0) a.reach_clear[b] = 0;
     if (a.zero_ticket)
       for (int k = lane; k < a.zero_steps; k += 64) a.zero_ticket[(size_t)k * a.B + b] = 0u;
     if (a.zero_pose) {
       su = sv = th = 0.f;
-      if (lane < 3) a.pose[b * 3 + lane] = 0.f;
+      if (lane < 3) (LOCAL ? lpose[lane] : a.pose[b * 3 + lane]) = 0.f;
     }
   }
 
@@ -106,14 +108,15 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, int b, int lan
         su = (su > -2.5f && su < 2.5f) ? su : ru;
         sv = (sv > -2.5f && sv < 2.5f) ? sv : rv;
       }
-      a.pose[b * 3 + 0] = su; a.pose[b * 3 + 1] = sv; a.pose[b * 3 + 2] = th;
+      if (LOCAL) { lpose[0] = su; lpose[1] = sv; lpose[2] = th; }
+      else { a.pose[b * 3 + 0] = su; a.pose[b * 3 + 1] = sv; a.pose[b * 3 + 2] = th; }
       float* tr = a.trace_out + (size_t)b * a.trace_stride;
       tr[0] = su; tr[1] = sv; tr[2] = th;
     }
   }
-  if (a.coef && lane == 0)
+  if ((LOCAL ? lcoef : a.coef) && lane == 0)
     lm_coefficients(a.next, su, sv, th, a.R_FL ? a.R_FL + (size_t)b * 9 : nullptr, a.T_FL ? a.T_FL + (size_t)b * 3 : nullptr,
-                    a.coef + (size_t)b * COEF_N);
+                    LOCAL ? lcoef : a.coef + (size_t)b * COEF_N);
 }
 
 // stand-alone launch: the coefficients of step 0 (part == null)
@@ -144,6 +147,8 @@ struct AccumArgs {
 // written on such pairs so that it compiles to v_pk_{mul,add,fma}_f32 without operand shuffling.  (Left to itself the SLP
 // vectoriser paired unrelated scalars: a third of the loop was v_mov_b32, and the kernel is VALU-issue-bound -- 80 % VALU busy.)
 typedef float lm_f2 __attribute__((ext_vector_type(2)));
+// w * x + y as ONE fused multiply-add per element, w a scalar
+__device__ __forceinline__ lm_f2 lm_fma2(float w, lm_f2 x, lm_f2 y) { return __builtin_elementwise_fma(lm_f2{w, w}, x, y); }
 template <typename F> __device__ __forceinline__ lm_f2 lm_pair(const uint4& v, int ep);
 template <> __device__ __forceinline__ lm_f2 lm_pair<float>(const uint4& v, int ep) {
   lm_f2 r;
@@ -183,6 +188,7 @@ template <> __device__ __forceinline__ lm_f2 lm_pair<_Float16>(const uint4& v, i
 // (measured on one box against 256 / 128 / 64: lm_accum<64> 72.3 -> 70.8 us, <128> 45.3 -> 41.7, <256> 30.8 -> 29.5; with 512 / 512 / 256
 // the two coarse levels lose 10-30 %)
 static inline int lm_pick_tile_fwd(int npix) { return npix >= 16384 ? 512 : (npix >= 4096 ? 256 : 128); }
+
 template <int C, bool USE_W, typename F>
 __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs sa) {
   __shared__ PixParam pp[FWD_MAX_TP];
@@ -192,119 +198,126 @@ __global__ __launch_bounds__(256, LM_OCC) void lm_accum(AccumArgs a, SolveArgs s
   if (!lm_block_map(a.xcd_affine, a.nt, a.nb, b, tile, a.b0)) return;
   if (a.gate && a.gate[b] == 0) return;      // workgroup-uniform, ahead of the first barrier
   const int t = threadIdx.x;
-  const int p0 = tile * a.TP;
-  const int np = min(a.TP, a.npix - p0);
-  const double* cf = a.coef + (size_t)b * COEF_N;
-
-  for (int tt = t; tt < np; tt += 256) {
-    const int p = p0 + tt;
-    const int r = a.row0 + p / a.w, c = p % a.w;
-    const float cw = USE_W ? a.conf[((size_t)b * a.hs + (r - a.rskip)) * a.w + c] : 1.f;
-    float q[3];
-    const bool gm = lm_point(a.pts, b, r, c, a.w, q);
-    const bool kept = !a.keep || a.keep[p];
-    PixParam P = lm_pixel<C>(cf, q, gm, a.A, cw, a.col0, (a.reach_flag && kept) ? a.reach_flag + b : nullptr);
-    if (!kept) {          // dropped by args.dropout: the pixel leaves every sum (models_kitti.py:968-974)
-      P.wx0 = P.wx1 = P.wy0 = P.wy1 = 0.f; P.off = a.col0 * C; P.dxo = P.dyo = 0; P.j2u = P.j2v = 0.f; P.gm = P.wt = P.m = 0.f;
-    }
-    pp[tt] = P;
-  }
-  __syncthreads();
-
-  const float j0u = (float)cf[8], j0v = (float)cf[9], j1u = (float)cf[10], j1v = (float)cf[11];
-  constexpr int EPL = 16 / (int)sizeof(F);   // channels per lane (16 B)
-  constexpr int LPP = C / EPL;        // lanes per pixel
-  constexpr int PPW = 64 / LPP;       // pixels per wave-iteration
-  const int lane = t & 63, wave = t >> 6;
-  const int sub = lane / LPP, cl = (lane % LPP) * EPL;
-  const F* satb = (const F*)a.sat + (size_t)b * a.A * a.A * C + cl;
-  const F* grdb = (const F*)a.grd + ((size_t)b * a.hs * a.w + (size_t)(a.row0 - a.rskip) * a.w + p0) * C + cl;
-
-  // With J_a = dsx*a_u + dsy*a_v (a = u, v, theta) and only the theta row's (a_u, a_v) = (j2u, j2v) varying per pixel, every
-  // normal-equation sum is a combination of CHANNEL sums of a pixel -- Sxx = sum dsx^2, Sxy, Syy, Sxs = sum dsx*s, Sys, Sxg, Syg --
-  // with per-pixel (j2u, j2v, weight) or per-sample (j0*, j1*) coefficients.  So the inner loop only forms those nine channel
-  // sums (9 FMAs per element instead of 6 for the J's + 14), the per-pixel step folds in what varies per pixel, and the
-  // per-sample coefficients are applied once per block, in fp64, after the reduction:
-  //   T1..3 = sum w (Sxx, Sxy, Syy)        B1 = sum w (j2u Sxx + j2v Sxy)   B2 = sum w (j2u Sxy + j2v Syy)
-  //   Q = sum (j2u b1 + j2v b2) = H22      U1,2 = sum w (Sxs, Sys)   U3 = sum w (j2u Sxs + j2v Sys)   V likewise with g
-  float aS = 0, aG = 0, T1 = 0, T2 = 0, T3 = 0, B1 = 0, B2 = 0, Q = 0, U1 = 0, U2 = 0, U3 = 0, V1 = 0, V2 = 0, V3 = 0;
-
-  constexpr int UNR = LM_UNROLL(F);
-#pragma unroll UNR
-  // (measured with the gather loop compiled out: a launch's FIXED cost -- the fp64 pixel set-up, the reductions, the published
-  // partials, the ticket round trip, the closing solve -- is 31 / 20 / 13 us of the 73 / 43 / 30 us at C = 64 / 128 / 256)
-  for (int i = wave * PPW + sub; i < np; i += 4 * PPW) {
-    const PixParam P = pp[i];
-    const uint4 t00 = *(const uint4*)(satb + P.off);
-    const uint4 t01 = *(const uint4*)(satb + P.off + P.dxo);
-    const uint4 t10 = *(const uint4*)(satb + P.off + P.dyo);
-    const uint4 t11 = *(const uint4*)(satb + P.off + P.dyo + P.dxo);
-    const uint4 gg = *(const uint4*)(grdb + (size_t)i * C);
-    lm_f2 xx = {0.f, 0.f}, xy = xx, yy = xx, xs = xx, ys = xx, xg = xx, yg = xx, ss2 = xx, gg2 = xx;
-#pragma unroll
-    for (int ep = 0; ep < EPL / 2; ++ep) {
-      const lm_f2 c00 = lm_pair<F>(t00, ep), c01 = lm_pair<F>(t01, ep), c10 = lm_pair<F>(t10, ep), c11 = lm_pair<F>(t11, ep);
-      const lm_f2 top = P.wx0 * c00 + P.wx1 * c01;
-      const lm_f2 bot = P.wx0 * c10 + P.wx1 * c11;
-      const lm_f2 s = P.wy0 * top + P.wy1 * bot;
-      const lm_f2 dsy = bot - top;
-      const lm_f2 dsx = P.wy0 * (c01 - c00) + P.wy1 * (c11 - c10);
-      const lm_f2 g = lm_pair<F>(gg, ep) * P.gm;
-      xx += dsx * dsx; xy += dsx * dsy; yy += dsy * dsy;
-      xs += dsx * s; ys += dsy * s; xg += dsx * g; yg += dsy * g;
-      ss2 += s * s; gg2 += g * g;
-    }
-    float Sxx = xx.x + xx.y, Sxy = xy.x + xy.y, Syy = yy.x + yy.y, Sxs = xs.x + xs.y, Sys = ys.x + ys.y;
-    float Sxg = xg.x + xg.y, Syg = yg.x + yg.y;
-    const float Sss = ss2.x + ss2.y, Sgg = gg2.x + gg2.y;
-    aS += Sss; aG += Sgg;
-    if (USE_W) { Sxx *= P.wt; Sxy *= P.wt; Syy *= P.wt; Sxs *= P.wt; Sys *= P.wt; Sxg *= P.wt; Syg *= P.wt; }
-    T1 += Sxx; T2 += Sxy; T3 += Syy;
-    const float b1 = P.j2u * Sxx + P.j2v * Sxy, b2 = P.j2u * Sxy + P.j2v * Syy;
-    B1 += b1; B2 += b2;
-    Q += P.j2u * b1 + P.j2v * b2;
-    U1 += Sxs; U2 += Sys; U3 += P.j2u * Sxs + P.j2v * Sys;
-    V1 += Sxg; V2 += Syg; V3 += P.j2u * Sxg + P.j2v * Syg;
-  }
-
-  float acc[14] = {aS, aG, T1, T2, T3, B1, B2, Q, U1, U2, U3, V1, V2, V3};
-#pragma unroll
-  for (int k = 0; k < 14; ++k) acc[k] = wave_sum_f32(acc[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 14; ++k) red[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (t < 14) redd[t] = ((double)red[0][t] + (double)red[1][t]) + ((double)red[2][t] + (double)red[3][t]);
-  __syncthreads();
-  if (wave != 0) return;
-  if (t < PART_N) {
-    // the per-sample rows of d(uv)/d(pose): fp32 values (the gather used to apply them in fp32), combined in fp64
-    const double au = (double)j0u, av = (double)j0v, bu = (double)j1u, bv = (double)j1v;
-    const double t1 = redd[2], t2 = redd[3], t3 = redd[4], b1 = redd[5], b2 = redd[6];
-    double v = 0.0;
-    switch (t) {
-      case 0: v = redd[0]; break;                                             // sum s^2
-      case 1: v = redd[1]; break;                                             // sum g^2
-      case 2: v = au * au * t1 + 2.0 * au * av * t2 + av * av * t3; break;    // H00
-      case 3: v = au * bu * t1 + (au * bv + av * bu) * t2 + av * bv * t3; break;   // H01
-      case 4: v = au * b1 + av * b2; break;                                   // H02
-      case 5: v = bu * bu * t1 + 2.0 * bu * bv * t2 + bv * bv * t3; break;    // H11
-      case 6: v = bu * b1 + bv * b2; break;                                   // H12
-      case 7: v = redd[7]; break;                                             // H22
-      case 8: v = au * redd[8] + av * redd[9]; break;                         // J^T W s
-      case 9: v = bu * redd[8] + bv * redd[9]; break;
-      case 10: v = redd[10]; break;
-      case 11: v = au * redd[11] + av * redd[12]; break;                      // J^T W g
-      case 12: v = bu * redd[11] + bv * redd[12]; break;
-      case 13: v = redd[13]; break;
-      default: break;
-    }
-    __hip_atomic_store(a.part + ((size_t)b * a.part_ld + tile) * PART_N + t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  constexpr bool active = true;
+#define LM_TILE_COEF (a.coef + (size_t)b * COEF_N)
+#define LM_TILE_BEFORE_PUBLISH if (wave != 0) return;
+#include "lm_tile_body.h"      // (declares lane and wave)
+#undef LM_TILE_COEF
+#undef LM_TILE_BEFORE_PUBLISH
   const unsigned old = lm_draw_ticket(a.ticket + b, lane);      // (publication recipe: lm_common.h)
   if (old + 1 != (unsigned)a.nt) return;
   lm_solve_body<true>(sa, b, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// hla_s2g_config.reach_mode = 2: the whole loop of a flagged sample in ONE launch.  The multi-launch loop needs a launch per step
+// because a step's tiles are spread over the chip and hand their sums over grid-wide; here a sample is one workgroup, so the
+// hand-over is a barrier and nothing of one workgroup ever waits on another (no ticket, no spinning: an unflagged sample's
+// workgroup returns at once, and a flagged one depends on nobody).  1024 threads = four 256-thread groups, each with the shared
+// arrays of one lm_accum workgroup; group v runs the tile body (lm_tile_body.h) on tiles v, v + 4, ... of the step with its thread id t & 255, so a
+// tile's 14 partials are bit for bit what lm_accum publishes, and wave 0 then closes the step with lm_solve_body<true> like
+// lm_accum's last arriver: same fixed-order reduction over the tiles, same draws, same keep masks, same trace / normal_eq rows.
+// What one step leaves for the next inside the launch:
+//   * pose and coefficients live in SHARED MEMORY (s_pose, s_cf) for the whole launch -- a block-uniform const double* in the
+//     workspace would be read through the scalar cache, a plain vector load through this CU's L1, and neither sees a store made
+//     earlier in the same launch; the final pose is copied to the workspace at the end, where the multi-launch loop leaves it;
+//   * the tile partials go through the workspace rows of the sample exactly as in lm_accum: agent-scope (sc1) stores, s_waitcnt
+//     vmcnt(0), the barrier, agent-scope loads in lm_solve_body<true> (the recipe of lm_draw_ticket with the barrier in the
+//     ticket's place).
+struct RepairLevel {
+  const void* sat; const void* grd;
+  LmPoints pts;
+  const double* sat_inv; const double* grd_inv;
+  int A, h, w, row0, npix, TP, nt, hs, rskip, C;
+  double mpp, ctr;
+};
+struct RepairArgs {
+  RepairLevel lv[4];
+  SolveArgs sa;          // what every step shares; .gate = the reach flags, .next holds the level-independent part of the geometry
+  double* part;
+  const unsigned char* keep; size_t keep_stride;
+  float* trace; const float* rand_uv; double* normal_eq;
+  int L, N, level_first;
+};
+#define LM_REPAIR_GROUPS 4
+
+template <typename F>
+__global__ __launch_bounds__(256 * LM_REPAIR_GROUPS) void lm_repair_loop(RepairArgs ra) {
+  __shared__ PixParam s_pp[LM_REPAIR_GROUPS][FWD_MAX_TP];
+  __shared__ float s_red[LM_REPAIR_GROUPS][4][14];
+  __shared__ double s_redd[LM_REPAIR_GROUPS][14];
+  __shared__ double s_cf[COEF_N];
+  __shared__ float s_pose[3];
+  const int b = blockIdx.x;
+  if (ra.sa.gate[b] == 0) return;      // workgroup-uniform, ahead of the first barrier
+  const int wt = threadIdx.x, vg = wt >> 8, vt = wt & 255;      // thread of the workgroup, its 256-thread group, its id in it
+  const int L = ra.L, N = ra.N, steps = L * N;
+  auto step_level = [&](int k) { return ra.level_first ? k / N : k % L; };
+
+  // the init step: the start pose (the workspace holds pose0 when one was given) and the coefficients of step 0
+  if (wt < 3) s_pose[wt] = ra.sa.pose[b * 3 + wt];
+  __syncthreads();      // wave 0's 64 lanes read what its lanes 0-2 wrote
+  if (wt < 64) {
+    SolveArgs sa = ra.sa;
+    const RepairLevel& n = ra.lv[step_level(0)];
+    sa.part = nullptr; sa.next.mpp = n.mpp; sa.next.ctr = n.ctr;
+    lm_solve_body<false, true>(sa, b, wt, s_pose, s_cf);
+  }
+  __syncthreads();
+
+  for (int k = 0; k < steps; ++k) {
+    const int l = step_level(k), it = ra.level_first ? k % N : k / L;
+    const RepairLevel& lv = ra.lv[l];
+    AccumArgs a{};
+    a.sat = lv.sat; a.grd = lv.grd; a.pts = lv.pts; a.part = ra.part;
+    a.A = lv.A; a.h = lv.h; a.w = lv.w; a.row0 = lv.row0; a.npix = lv.npix; a.TP = lv.TP; a.nt = lv.nt; a.part_ld = ra.sa.part_ld;
+    a.hs = lv.hs; a.rskip = lv.rskip;
+    a.keep = ra.keep ? ra.keep + (size_t)k * ra.keep_stride : nullptr;
+    for (int tile0 = 0; tile0 < lv.nt; tile0 += LM_REPAIR_GROUPS) {
+      const int tile = tile0 + vg;
+      const bool active = tile < lv.nt;
+      constexpr bool USE_W = false;
+      const int t = vt;
+      PixParam* const pp = s_pp[vg];
+      float (*const red)[14] = s_red[vg];
+      double* const redd = s_redd[vg];
+#define LM_TILE_COEF s_cf
+#define LM_TILE_BEFORE_PUBLISH
+      switch (lv.C) {
+        case 256: {
+          constexpr int C = 256;
+#include "lm_tile_body.h"
+        } break;
+        case 128: {
+          constexpr int C = 128;
+#include "lm_tile_body.h"
+        } break;
+        default: {
+          constexpr int C = 64;
+#include "lm_tile_body.h"
+        } break;
+      }
+#undef LM_TILE_COEF
+#undef LM_TILE_BEFORE_PUBLISH
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the partials have left this CU before the barrier lets wave 0 read them
+    __syncthreads();
+    if (wt < 64) {
+      SolveArgs sa = ra.sa;
+      sa.t = k;
+      sa.part = ra.part; sa.nt = lv.nt; sa.sat_inv = lv.sat_inv; sa.grd_inv = lv.grd_inv;
+      sa.trace_out = ra.trace + ((size_t)it * L + l) * 3; sa.trace_stride = N * L * 3;
+      sa.rand_uv = ra.sa.reinit ? ra.rand_uv + (size_t)k * 2 * ra.sa.B : nullptr;
+      sa.normal_eq = ra.normal_eq ? ra.normal_eq + (size_t)k * ra.sa.B * 16 : nullptr;
+      if (k + 1 < steps) {
+        const RepairLevel& n = ra.lv[step_level(k + 1)];
+        sa.next.mpp = n.mpp; sa.next.ctr = n.ctr;
+      }
+      lm_solve_body<true, true>(sa, b, wt, s_pose, k + 1 < steps ? s_cf : nullptr);
+    }
+    __syncthreads();      // the next step's coefficients are in s_cf (and every read of this step's is behind us)
+  }
+  if (wt < 3) ra.sa.pose[b * 3 + wt] = s_pose[wt];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -504,6 +517,41 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   sa.cfg.dof = cfg->dof; sa.cfg.use_hessian = sa.cfg.gn ? 0 : cfg->use_hessian;
   for (int i = 0; i < 3; ++i) sa.cfg.lam[i] = sa.cfg.gn ? 0.0 : cfg->damping[i];     // GN_update: delta = -H^-1 J^T W r
   sa.coef = coef;
+
+  // reach_mode 2: the init step and all steps of the flagged samples as one launch of lm_repair_loop, a workgroup per sample.
+  // Outside what that kernel is built for -- confidence weights, count_in_view (its counting launches read each step's
+  // coefficients from the workspace), SGD / ADAM, 16 channels, levels of different map types, fp32 maps -- the gated multi-launch
+  // loop below does the same work, bit for bit.  (fp32 maps: built and measured -- in that kernel the optimiser leaves the
+  // operands of three a * b + c * d adds of the fp32 gather the other way round than in lm_accum<C, false, float>, so the other
+  // product is fused: normal_eq entries 1e-7 relative off.  The instructions: EXPERIMENTS.md, "Repair loop as one launch".)
+  bool repair = cfg->reach_mode == 2 && newton && !cfg->using_weight && !count && lv[0].feat_dtype != HLA_F32;
+  for (int l = 0; l < L && repair; ++l) repair = lv[l].C != 16 && lv[l].feat_dtype == lv[0].feat_dtype;
+  if (repair) {
+    RepairArgs ra{};
+    for (int l = 0; l < L; ++l) {
+      const hla_s2g_level& v = lv[l];
+      RepairLevel& r = ra.lv[l];
+      r.sat = v.sat_feat; r.grd = v.grd_feat; r.pts = lm_points_of(v); r.sat_inv = v.sat_inv_norm; r.grd_inv = v.grd_inv_norm;
+      r.A = v.A; r.h = v.h; r.w = v.w; r.row0 = v.row0; r.npix = (v.h - v.row0) * v.w;
+      r.TP = lm_pick_tile_fwd(r.npix); r.nt = (r.npix + r.TP - 1) / r.TP;
+      r.hs = v.h - v.grd_row_skip; r.rskip = v.grd_row_skip; r.C = v.C;
+      r.mpp = v.meter_per_pixel; r.ctr = v.centre;
+    }
+    ra.sa = sa;
+    ra.sa.next = geom(0);      // (mpp and ctr are set per step, from the level the next step runs on)
+    ra.sa.zero_pose = pose0 ? 0 : 1;
+    ra.sa.gate = cfg->reach_flag;
+    ra.part = part;
+    ra.keep = cfg->keep; ra.keep_stride = (size_t)cfg->keep_stride;
+    ra.trace = trace; ra.rand_uv = rand_uv; ra.normal_eq = normal_eq;
+    ra.L = L; ra.N = N; ra.level_first = cfg->level_first;
+    hla_prof_begin(K_LMREPAIR, 0, 0, st);
+    if (lv[0].feat_dtype == HLA_BF16) hipLaunchKernelGGL(lm_repair_loop<__bf16>, dim3(B), dim3(256 * LM_REPAIR_GROUPS), 0, st, ra);
+    else hipLaunchKernelGGL(lm_repair_loop<_Float16>, dim3(B), dim3(256 * LM_REPAIR_GROUPS), 0, st, ra);
+    hla_prof_end(st);
+    HLA_CHECK_HIP(hipGetLastError());
+    return HLA_OK;
+  }
 
   // init launch: coefficients of step 0
   sa.part = nullptr; sa.next = geom(step_level(0));

@@ -389,7 +389,11 @@ typedef struct hla_s2g_config {
                                 flagged sample's are not meaningful.
                              2, GATED: the whole loop again for the samples with reach_flag[b] != 0 only (reach_col0 is ignored: the
                                 maps are whole, see hla_vgg_forward's col_gate); every workgroup of a sample whose flag is 0 returns
-                                at once and that sample's trace / normal_eq entries are left as they are.  Runs on `stream` alone. */
+                                at once and that sample's trace / normal_eq entries are left as they are.  Runs on `stream` alone,
+                                as ONE launch with a workgroup per sample (the init step and all steps of a flagged sample on one
+                                CU: slower per flagged sample than the loop of launches, nothing to pay when no flag is set) with
+                                optimizer 0 / 3, using_weight = 0, count_in_view = 0, C = 64 / 128 / 256 and HLA_BF16 or HLA_F16
+                                maps on all levels; otherwise as the gated loop of launches.  The results are the same bits either way. */
   int* reach_flag;        /* [B] int32 on the device; required iff reach_mode != 0 */
   int reach_col0[4];      /* reach_mode 1: per level, the first column of levels[l].sat_feat that holds valid values, in [0, A_l) (maps
                              made with hla_vgg_forward_cols' first_col32: 16c+2 / 32c+6 / 64c+14); 0 = the whole map */
@@ -624,7 +628,7 @@ int hla_orien_triplet_loss_bwd(const float* corr, const float* gt_heading, long 
  * When enabled, every kernel launch of the entry points above is bracketed by two hipEvents
  * on its own stream; hla_prof_fetch synchronises them and returns one record per launch.
  * ------------------------------------------------------------------------- */
-#define HLA_PROF_NKERNELS 17
+#define HLA_PROF_NKERNELS 18 /* (17 before lm_repair_loop got an id of its own: a caller that sizes a table by it recompiles) */
 typedef struct hla_prof_record {
   int kernel_id;  /* index for hla_prof_kernel_name */
   float ms;       /* event-to-event duration on the launch stream */
