@@ -19,6 +19,7 @@
 // The tile size follows from C alone, and a hypothesis never shares an accumulator with another one: sums and cost of (b, k) do
 // not depend, bit for bit, on the other hypotheses, on k, on K, on B or on repeats.
 #include "lm_g2s.h"
+#include "lm_host.h"
 
 constexpr int GPS_KC = 32;        // hypotheses per block
 constexpr int GPS_NPL = 4;        // pixels per lane (their satellite vectors live in registers)
@@ -44,6 +45,7 @@ struct GpsArgs {
 
 // pixels per block: GPS_NPL wave-iterations of g2s_accum's lane layout.  16 (C = 256) .. 256 (C = 16)
 static inline int gps_tile(int C) { return 4 * (64 / (C / 4)) * GPS_NPL; }
+static LmTiling gps_tiling(const hla_s2g_level& v) { return lm_tiling(lm_npix_g2s(v), [&](int) { return gps_tile(v.C); }); }
 
 // The loop's pixel set-up without its Jacobian columns.  In view <=> in bounds, which the loop's records show as a nonzero weight
 // or, for the one in-bounds point whose four clamped-corner weights vanish (u = w-1 and v = h-1 exactly), a nonzero offset.
@@ -199,12 +201,9 @@ __global__ __launch_bounds__(64) void gps_close(const float* __restrict__ part, 
 
 template <bool W, int PROJ>
 static void gps_launch(int C, dim3 grid, hipStream_t st, const GpsArgs& a) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((gps_accum<256, W, PROJ>), grid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((gps_accum<128, W, PROJ>), grid, dim3(256), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((gps_accum<64, W, PROJ>), grid, dim3(256), 0, st, a); break;
-    case 16: if constexpr (PROJ == 1) hipLaunchKernelGGL((gps_accum<16, false, 1>), grid, dim3(256), 0, st, a); break;
-  }
+  auto go = [&](auto c) { hipLaunchKernelGGL((gps_accum<decltype(c)::value, W, PROJ>), grid, dim3(256), 0, st, a); };
+  if constexpr (PROJ == 1) lm_dispatch_c<256, 128, 64, 16>(C, go);      // (16 channels exist under proj 1 only, g2s_validate)
+  else lm_dispatch_c<256, 128, 64>(C, go);
 }
 
 static int gps_check(const char* who, const hla_s2g_config* cfg, const hla_s2g_level* v, const float* camera_k, int ori_h,
@@ -222,16 +221,17 @@ static int gps_check(const char* who, const hla_s2g_config* cfg, const hla_s2g_l
   HLA_REQUIRE(!v->depth, "%s: a depth map belongs to hla_s2g_* (LM_G2SP ignores gt_depth)", who);
   HLA_REQUIRE((long long)v->h * v->w >= 2, "%s: a 1 x 1 ground map is not supported", who);
   HLA_REQUIRE((size_t)v->A * v->A * v->C < (1u << 31), "%s: satellite map too large", who);
-  const long long npix = (long long)v->A * v->A, tp = gps_tile(v->C), nt = (npix + tp - 1) / tp;
-  const long long blocks = (long long)(8 * ((B + 7) / 8)) * nt * ((K + GPS_KC - 1) / GPS_KC);
+  const long long blocks = (long long)lm_grid_blocks(1, B, 1) * gps_tiling(*v).nt * ((K + GPS_KC - 1) / GPS_KC);
   HLA_REQUIRE(blocks < (1LL << 31) && (long long)B * K < (1LL << 31), "%s: B * K too large for one launch", who);
   return HLA_OK;
 }
 
+// the one region: the tile partials [B,K,nt,GPS_NS]
+static size_t gps_ws_bytes(int B, int K, const LmTiling& t) { return lm_one_region_bytes((size_t)B * K * t.nt * GPS_NS * sizeof(float)); }
+
 extern "C" size_t hla_g2s_pose_score_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K) {
   if (gps_check("hla_g2s_pose_score_workspace_bytes", cfg, level, nullptr, 0, 0, B, K, false)) return 0;
-  const int npix = level->A * level->A, tp = gps_tile(level->C), nt = (npix + tp - 1) / tp;
-  return hla_align_up((size_t)B * K * nt * GPS_NS * sizeof(float), 256);
+  return gps_ws_bytes(B, K, gps_tiling(*level));
 }
 
 extern "C" int hla_g2s_pose_score(const hla_s2g_config* cfg, const hla_s2g_level* level, const float* camera_k, int ori_h, int ori_w,
@@ -244,21 +244,16 @@ extern "C" int hla_g2s_pose_score(const hla_s2g_config* cfg, const hla_s2g_level
   GpsArgs a{};
   a.grd = (const float*)v.grd_feat; a.sat = (const float*)v.sat_feat; a.conf = v.grd_conf;
   a.poses = poses; a.camera_k = camera_k; a.geom = g2s_geom_of(cfg, v, ori_h, ori_w);
-  a.A = v.A; a.h = v.h; a.w = v.w; a.ctr = v.A / 2; a.npix = v.A * v.A;
-  const int tp = gps_tile(v.C);
-  a.nt = (a.npix + tp - 1) / tp; a.nch = (K + GPS_KC - 1) / GPS_KC;
-  a.K = K; a.B = B; a.xcd_affine = B >= 8 ? 1 : 0;
-  const size_t need = hla_align_up((size_t)B * K * a.nt * GPS_NS * sizeof(float), 256);
-  if (workspace_bytes < need) {
-    hla_set_error("hla_g2s_pose_score: workspace %zu < %zu", workspace_bytes, need);
-    return HLA_ERR_WORKSPACE;
-  }
+  const LmTiling til = gps_tiling(v);
+  lm_fill_g2s_dims(a, v, til);
+  a.nch = (K + GPS_KC - 1) / GPS_KC;
+  a.K = K; a.B = B; a.xcd_affine = lm_xcd_affine(B);
+  const size_t need = gps_ws_bytes(B, K, til);
+  if (workspace_bytes < need) return lm_workspace_short("hla_g2s_pose_score", workspace_bytes, need);
   a.part = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  const int per = a.nt * a.nch;
-  const int nblk = a.xcd_affine ? 8 * ((B + 7) / 8) * per : B * per;
-  hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
-                 (double)B * ((double)v.h * v.w + (double)a.npix * a.nch) * v.C * 4.0, st);
+  const int nblk = lm_grid_blocks(a.xcd_affine, B, a.nt * a.nch);
+  hla_prof_begin(lm_prof_id(v.C), 0, (double)B * ((double)v.h * v.w + (double)a.npix * a.nch) * v.C * 4.0, st);
   if (cfg->proj) gps_launch<false, 1>(v.C, dim3(nblk), st, a);
   else if (cfg->using_weight) gps_launch<true, 0>(v.C, dim3(nblk), st, a);
   else gps_launch<false, 0>(v.C, dim3(nblk), st, a);

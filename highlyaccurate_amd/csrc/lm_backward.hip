@@ -13,7 +13,7 @@
 // Gradients are w.r.t. the L2-NORMALISED maps (inv_norm * stored map); hla_vgg_backward applies the
 // normalisation Jacobian.  d/d(sat) accumulation order is not deterministic (fp32 atomics) unless cfg->deterministic, which
 // accumulates it in 64-bit fixed point (integer atomics commute: any order gives the same bits), see DetScale below.
-#include "lm_common.h"
+#include "lm_host.h"
 #include <math.h>
 
 int hla_s2g_validate(const char* who, const hla_s2g_config* cfg, const hla_s2g_level* lv, const float* R_FL,
@@ -451,34 +451,28 @@ __global__ __launch_bounds__(256, USE_W ? 3 : 4) void lm_bwd_accum(BwdAccumArgs 
 static inline int lm_pick_tile_bwd(int npix) { return npix >= 16384 ? 256 : (npix >= 4096 ? 256 : 128); }
 
 // ---------------------------------------------------------------------------------------------
-// off[0..5]: coef, adj, gid, part, ADAM adjoints, tickets; off[6]: dlam [B,4]; off[7]: qexp [L,B]; off[8 + l]: level l's 64-bit
-// fixed-point d(loss)/d(sat) accumulators (cfg->deterministic only)
-static size_t bwd_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B, size_t off[12]) {
-  int max_nt = 1;
-  for (int l = 0; l < cfg->n_levels; ++l) {
-    const int npix = (lv[l].h - lv[l].row0) * lv[l].w;
-    const int tp = lm_pick_tile_bwd(npix);
-    max_nt = max(max_nt, (npix + tp - 1) / tp);
-  }
-  size_t o = 0;
-  off[0] = o; o += hla_align_up((size_t)B * COEF_N * sizeof(double), 256);          // coef
-  off[1] = o; o += hla_align_up((size_t)B * 16 * sizeof(double), 256);              // adj
-  off[2] = o; o += hla_align_up((size_t)B * 3 * sizeof(double), 256);               // gid
-  off[3] = o; o += hla_align_up((size_t)B * max_nt * PART_N * sizeof(double), 256); // part
-  off[4] = o; o += hla_align_up((size_t)B * 6 * sizeof(double), 256);               // ADAM moment adjoints
-  off[5] = o; o += hla_align_up((size_t)B * cfg->n_levels * cfg->n_iters * sizeof(unsigned), 256);   // arrival tickets [steps][B]
-  off[6] = o; o += hla_align_up((size_t)B * 4 * sizeof(double), 256);               // per-sample d_lambda sums + range counter
-  off[7] = o; o += hla_align_up((size_t)B * 4 * sizeof(int), 256);                  // fixed-point exponents [4 levels][B]
-  for (int l = 0; l < 4; ++l) {
-    off[8 + l] = o;
-    if (cfg->deterministic && l < cfg->n_levels) o += hla_align_up((size_t)B * lv[l].A * lv[l].A * lv[l].C * sizeof(long long), 256);
-  }
-  return o;
+static LmTiling bwd_tiling(const hla_s2g_level& v) { return lm_tiling(lm_npix_s2g(v), lm_pick_tile_bwd); }
+// fix[l]: level l's 64-bit fixed-point d(loss)/d(sat) accumulators (cfg->deterministic only; else empty, all at `total`)
+struct BwdWs { size_t coef, adj, gid, part, adam_adj, ticket, dlam, qexp, fix[4], total; };
+static BwdWs bwd_ws(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B) {
+  BwdWs W{};
+  LmBump ws;
+  W.coef = ws.take((size_t)B * COEF_N * sizeof(double));
+  W.adj = ws.take((size_t)B * 16 * sizeof(double));
+  W.gid = ws.take((size_t)B * 3 * sizeof(double));
+  W.part = ws.take((size_t)B * lm_max_nt(cfg, lv, bwd_tiling) * PART_N * sizeof(double));
+  W.adam_adj = ws.take((size_t)B * 6 * sizeof(double));             // ADAM moment adjoints
+  W.ticket = ws.take((size_t)B * cfg->n_levels * cfg->n_iters * sizeof(unsigned));   // arrival tickets [steps][B]
+  W.dlam = ws.take((size_t)B * 4 * sizeof(double));                 // per-sample d_lambda sums + range counter
+  W.qexp = ws.take((size_t)B * 4 * sizeof(int));                    // fixed-point exponents [4 levels][B]
+  for (int l = 0; l < 4; ++l)
+    W.fix[l] = ws.take(cfg->deterministic && l < cfg->n_levels ? (size_t)B * lv[l].A * lv[l].A * lv[l].C * sizeof(long long) : 0);
+  W.total = ws.o;
+  return W;
 }
 
 extern "C" size_t hla_s2g_bwd_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B) {
-  size_t off[12];
-  return bwd_layout(cfg, levels, B, off);
+  return bwd_ws(cfg, levels, B).total;
 }
 
 // cfg->deterministic: the fixed-point sums -> the caller's fp32 d_sat_feat buffers (every element written: no zero-fill needed there)
@@ -498,12 +492,7 @@ static __global__ __launch_bounds__(256) void det_convert_kernel(DetConvertArgs 
 
 template <bool W, bool DET>
 static void launch_bwd_accum(int C, dim3 grid, hipStream_t st, const BwdAccumArgs& a, const BwdSolveArgs& sa) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((lm_bwd_accum<256, W, DET>), grid, dim3(256), 0, st, a, sa); break;
-    case 128: hipLaunchKernelGGL((lm_bwd_accum<128, W, DET>), grid, dim3(256), 0, st, a, sa); break;
-    case 64: hipLaunchKernelGGL((lm_bwd_accum<64, W, DET>), grid, dim3(256), 0, st, a, sa); break;
-    case 16: hipLaunchKernelGGL((lm_bwd_accum<16, W, DET>), grid, dim3(256), 0, st, a, sa); break;
-  }
+  lm_dispatch_c<256, 128, 64, 16>(C, [&](auto c) { hipLaunchKernelGGL((lm_bwd_accum<decltype(c)::value, W, DET>), grid, dim3(256), 0, st, a, sa); });
 }
 
 extern "C" int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_level* lv, const hla_s2g_level_grad* gr,
@@ -518,74 +507,52 @@ extern "C" int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
     HLA_REQUIRE(gr[l].d_sat_feat && gr[l].d_grd_feat, "hla_s2g_lm_solve_bwd: level %d gradient buffers missing", l);
     HLA_REQUIRE(lv[l].feat_dtype == HLA_F32, "hla_s2g_lm_solve_bwd: level %d: the backward needs fp32 feature maps", l);
   }
-  size_t off[12];
-  const size_t need = bwd_layout(cfg, lv, B, off);
-  if (workspace_bytes < need) {
-    hla_set_error("hla_s2g_lm_solve_bwd: workspace %zu < %zu", workspace_bytes, need);
-    return HLA_ERR_WORKSPACE;
-  }
+  const BwdWs W = bwd_ws(cfg, lv, B);
+  if (workspace_bytes < W.total) return lm_workspace_short("hla_s2g_lm_solve_bwd", workspace_bytes, W.total);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  double* coef = (double*)(ws + off[0]);
-  double* adj = (double*)(ws + off[1]);
-  double* gid = (double*)(ws + off[2]);
-  double* part = (double*)(ws + off[3]);
+  double* coef = (double*)(ws + W.coef);
+  double* adj = (double*)(ws + W.adj);
+  double* gid = (double*)(ws + W.gid);
+  double* part = (double*)(ws + W.part);
   // (tickets, ADAM adjoints and the d_lambda sums are zeroed by the first launch, lm_bwd_solve: no memset launches here)
-  double* adam_adj = (double*)(ws + off[4]);
-  unsigned* tickets = (unsigned*)(ws + off[5]);
-  double* dlam = (double*)(ws + off[6]);
-  int* qexp = (int*)(ws + off[7]);
+  double* adam_adj = (double*)(ws + W.adam_adj);
+  unsigned* tickets = (unsigned*)(ws + W.ticket);
+  double* dlam = (double*)(ws + W.dlam);
+  int* qexp = (int*)(ws + W.qexp);
   const bool det = cfg->deterministic != 0;
-  HLA_REQUIRE(cfg->n_levels <= 4, "hla_s2g_lm_solve_bwd: at most 4 levels");
-  if (det) {      // the fixed-point accumulators of all levels are one contiguous region
-    const size_t bytes = need - off[8];
-    HLA_CHECK_HIP(hipMemsetAsync(ws + off[8], 0, bytes, st));
-  }
+  // the fixed-point accumulators of all levels are one contiguous region
+  if (det) HLA_CHECK_HIP(hipMemsetAsync(ws + W.fix[0], 0, W.total - W.fix[0], st));
 
-  const bool newton = cfg->optimizer == 0 || cfg->optimizer == 3;
-  const bool reinit = (cfg->ford || cfg->dof == 3) && newton;
-  const int L = cfg->n_levels, N = cfg->n_iters, steps = L * N, tstride = N * L * 3;
-  auto step_level = [&](int k) { return cfg->level_first ? k / N : k % L; };
-  auto step_iter = [&](int k) { return cfg->level_first ? k % N : k / L; };
-  auto slot = [&](int k) { return ((size_t)step_iter(k) * L + step_level(k)) * 3; };
-  auto geom = [&](int l) {
-    LmGeom g{};
-    g.ford = cfg->ford; g.lat = cfg->shift_range_lat; g.lon = cfg->shift_range_lon; g.rot = cfg->rotation_range;
-    g.mpp = lv[l].meter_per_pixel; g.ctr = lv[l].centre;
-    return g;
-  };
+  const bool newton = lm_newton(cfg);
+  const LmPlan plan = lm_plan_of(cfg);
+  const int L = plan.L, steps = plan.steps(), tstride = plan.trace_stride();
 
   // One launch per step: lm_bwd_accum(k), whose last-arriving tile of every sample closes with the solve of step k - 1 (the
   // pose adjoint pulled back through step k's coefficients, step k - 1's damped system re-solved -> its 14 sum adjoints).  Only
   // the solve of the LAST forward step, which has nothing to close, is a launch of its own.
-  auto nt_of = [&](int l) {
-    const int npix = (lv[l].h - lv[l].row0) * lv[l].w;
-    const int tp = lm_pick_tile_bwd(npix);
-    return (npix + tp - 1) / tp;
-  };
   auto solve_args = [&](int k) {
     BwdSolveArgs sa{};
-    const int l = step_level(k);
+    const int l = plan.level(k);
     sa.first = (k == steps - 1) ? 1 : 0;
-    if (!sa.first) { sa.part_next = part; sa.nt_next = nt_of(step_level(k + 1)); sa.geom_next = geom(step_level(k + 1)); }
+    if (!sa.first) {
+      const hla_s2g_level& vn = lv[plan.level(k + 1)];
+      sa.part_next = part; sa.nt_next = bwd_tiling(vn).nt; sa.geom_next = lm_geom_of(cfg, vn);
+    }
     sa.normal_eq = normal_eq + (size_t)k * B * 16;
-    if (k > 0) { sa.pose_in = trace + slot(k - 1); sa.pose_in_stride = tstride; }
+    if (k > 0) { sa.pose_in = trace + plan.slot(k - 1); sa.pose_in_stride = tstride; }
     else { sa.pose_in = pose0; sa.pose_in_stride = 3; }
-    sa.pose_out = trace + slot(k); sa.d_trace = d_trace + slot(k); sa.trace_stride = tstride;
+    sa.pose_out = trace + plan.slot(k); sa.d_trace = d_trace + plan.slot(k); sa.trace_stride = tstride;
     sa.gid = gid; sa.adj = adj; sa.coef = coef; sa.dlam = dlam;
-    if (det) {       // is step k the first visit of its level in the reversed loop?
-      bool first_visit = true;
-      for (int j = k + 1; j < steps; ++j) if (step_level(j) == l) first_visit = false;
-      sa.qexp = qexp + (size_t)l * B; sa.q_first = first_visit ? 1 : 0; sa.A = lv[l].A;
+    if (det) {
+      sa.qexp = qexp + (size_t)l * B; sa.q_first = plan.first_visit_reversed(k) ? 1 : 0; sa.A = lv[l].A;
       sa.det_p = cfg->deterministic == 1 ? DET_P_DEFAULT : (cfg->deterministic < DET_P_MIN ? DET_P_MIN : (cfg->deterministic > DET_P_MAX ? DET_P_MAX : cfg->deterministic));
     }
-    sa.R_FL = R_FL; sa.T_FL = T_FL; sa.B = B; sa.reinit = reinit ? 1 : 0;
-    sa.cfg.gn = cfg->optimizer == 3 ? 1 : 0;
-    sa.cfg.dof = cfg->dof; sa.cfg.use_hessian = sa.cfg.gn ? 0 : cfg->use_hessian;
-    for (int i = 0; i < 3; ++i) sa.cfg.lam[i] = sa.cfg.gn ? 0.0 : cfg->damping[i];
+    sa.R_FL = R_FL; sa.T_FL = T_FL; sa.B = B; sa.reinit = lm_reinit(cfg) ? 1 : 0;
+    sa.cfg = lm_solve_cfg_of(cfg);
     sa.optimizer = cfg->optimizer; sa.t = k; sa.beta1 = cfg->beta1; sa.beta2 = cfg->beta2;
     sa.neq_all = normal_eq; sa.adam_adj = adam_adj;
-    sa.geom = geom(l);
+    sa.geom = lm_geom_of(cfg, lv[l]);
     return sa;
   };
   {
@@ -597,25 +564,23 @@ extern "C" int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
   }
   unsigned visited = 0;       // levels whose d_grd rows this call has written already (cfg->grd_grad_overwrite)
   for (int k = steps - 1; k >= 0; --k) {
-    const int l = step_level(k);
+    const int l = plan.level(k);
     const hla_s2g_level& v = lv[l];
     BwdAccumArgs aa{};
     aa.sat = (const float*)v.sat_feat; aa.grd = (const float*)v.grd_feat; aa.conf = v.grd_conf; aa.pts = lm_points_of(v); aa.coef = coef; aa.adj = adj;
     aa.sat_inv = v.sat_inv_norm; aa.grd_inv = v.grd_inv_norm;
     aa.d_sat = gr[l].d_sat_feat; aa.d_grd = gr[l].d_grd_feat; aa.d_conf = gr[l].d_grd_conf; aa.part = part;
-    aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.row0 = v.row0; aa.npix = (v.h - v.row0) * v.w;
-    aa.hs = v.h - v.grd_row_skip; aa.rskip = v.grd_row_skip;
+    lm_fill_s2g_dims(aa, v, bwd_tiling(v));
     aa.keep = cfg->keep ? cfg->keep + (size_t)k * cfg->keep_stride : nullptr;
     aa.grd_assign = (cfg->grd_grad_overwrite && !((visited >> l) & 1u)) ? 1 : 0;
     visited |= 1u << l;
-    aa.TP = lm_pick_tile_bwd(aa.npix); aa.nt = nt_of(l); aa.B = B;
-    aa.xcd_affine = (B >= 8) ? 1 : 0;
+    aa.B = B; aa.xcd_affine = lm_xcd_affine(B);
     // step 0 has no earlier step to solve for: no ticket, no closing
     aa.ticket = k > 0 ? tickets + (size_t)k * B : nullptr;
     const BwdSolveArgs sa = k > 0 ? solve_args(k - 1) : BwdSolveArgs{};
-    if (det) { aa.d_sat_fix = (long long*)(ws + off[8 + l]); aa.qexp = qexp + (size_t)l * B; }
+    if (det) { aa.d_sat_fix = (long long*)(ws + W.fix[l]); aa.qexp = qexp + (size_t)l * B; }
     if (k == 0) { aa.dlam_final = dlam; aa.d_damping_out = d_damping; }
-    const int nblk = aa.xcd_affine ? 8 * ((B + 7) / 8) * aa.nt : B * aa.nt;
+    const int nblk = lm_grid_blocks(aa.xcd_affine, B, aa.nt);
     hla_prof_begin(K_LMBWD, 0, (double)B * (5.0 * (double)v.A * v.A + 3.0 * (double)aa.npix) * v.C * 4.0, st);
     const bool w = cfg->using_weight && newton;
     if (det) { if (w) launch_bwd_accum<true, true>(v.C, dim3(nblk), st, aa, sa); else launch_bwd_accum<false, true>(v.C, dim3(nblk), st, aa, sa); }
@@ -626,7 +591,7 @@ extern "C" int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
     DetConvertArgs ca{};
     size_t maxper = 0;
     for (int l = 0; l < L; ++l) {
-      ca.fix[l] = (const long long*)(ws + off[8 + l]); ca.out[l] = gr[l].d_sat_feat;
+      ca.fix[l] = (const long long*)(ws + W.fix[l]); ca.out[l] = gr[l].d_sat_feat;
       ca.per[l] = (size_t)lv[l].A * lv[l].A * lv[l].C;
       maxper = ca.per[l] > maxper ? ca.per[l] : maxper;
     }

@@ -11,6 +11,7 @@
 //   g2s_ip_accum<C>  its own accumulate kernel (smaller pixel record, constants folded in after the reduction)
 // The solve kernels and the backward's element loop are shared; they branch on the projection outside the hot loops.
 #include "lm_g2s.h"
+#include "lm_host.h"
 
 struct G2sAccumArgs {
   const float* src;   // ground feature map [B,h,w,C] (gathered)
@@ -207,40 +208,29 @@ __global__ __launch_bounds__(64) void g2s_solve(G2sSolveArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-static size_t g2s_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B, size_t* oc, size_t* op, size_t* opart) {
-  int max_nt = 1;
-  for (int l = 0; l < cfg->n_levels; ++l) {
-    const int npix = lv[l].A * lv[l].A, tp = lm_pick_tile(npix);
-    max_nt = max(max_nt, (npix + tp - 1) / tp);
-  }
-  size_t o = 0;
-  *oc = o; o += hla_align_up((size_t)B * G2S_COEF_N * sizeof(double), 256);
-  *op = o; o += hla_align_up((size_t)B * 3 * sizeof(float), 256);
-  *opart = o; o += hla_align_up((size_t)B * max_nt * PART_N * sizeof(double), 256);
-  return o;
+static LmTiling g2s_tiling(const hla_s2g_level& v) { return lm_tiling(lm_npix_g2s(v), lm_pick_tile); }
+struct G2sWs { size_t coef, pose, part, total; };
+static G2sWs g2s_ws(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B) {
+  G2sWs W{};
+  LmBump ws;
+  W.coef = ws.take((size_t)B * G2S_COEF_N * sizeof(double));
+  W.pose = ws.take((size_t)B * 3 * sizeof(float));
+  W.part = ws.take((size_t)B * lm_max_nt(cfg, lv, g2s_tiling) * PART_N * sizeof(double));
+  W.total = ws.o;
+  return W;
 }
 
 extern "C" size_t hla_g2s_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B) {
-  size_t a, b, c;
-  return g2s_layout(cfg, levels, B, &a, &b, &c);
+  return g2s_ws(cfg, levels, B).total;
 }
 
-template <bool W>
+template <bool W>      // (no 16-channel instance: 16 channels exist under proj 1 only, g2s_validate)
 static void launch_g2s(int C, dim3 grid, hipStream_t st, const G2sAccumArgs& a) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((g2s_accum<256, W>), grid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((g2s_accum<128, W>), grid, dim3(256), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((g2s_accum<64, W>), grid, dim3(256), 0, st, a); break;
-  }
+  lm_dispatch_c<256, 128, 64>(C, [&](auto c) { hipLaunchKernelGGL((g2s_accum<decltype(c)::value, W>), grid, dim3(256), 0, st, a); });
 }
 
 static void launch_g2s_ip(int C, dim3 grid, hipStream_t st, const G2sAccumArgs& a) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((g2s_ip_accum<256>), grid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((g2s_ip_accum<128>), grid, dim3(256), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((g2s_ip_accum<64>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((g2s_ip_accum<16>), grid, dim3(256), 0, st, a); break;
-  }
+  lm_dispatch_c<256, 128, 64, 16>(C, [&](auto c) { hipLaunchKernelGGL((g2s_ip_accum<decltype(c)::value>), grid, dim3(256), 0, st, a); });
 }
 
 extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* lv, const float* camera_k, int ori_h,
@@ -258,21 +248,18 @@ extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
     HLA_REQUIRE(lv[l].grd_row_skip == 0, "hla_g2s_lm_solve: the whole ground map is sampled (grd_row_skip must be 0)");
     HLA_REQUIRE(!lv[l].depth, "hla_g2s_lm_solve: level %d: a depth map belongs to hla_s2g_* (LM_G2SP ignores gt_depth)", l);
   }
-  size_t oc, op, opart;
-  const size_t need = g2s_layout(cfg, lv, B, &oc, &op, &opart);
-  if (workspace_bytes < need) {
-    hla_set_error("hla_g2s_lm_solve: workspace %zu < %zu", workspace_bytes, need);
-    return HLA_ERR_WORKSPACE;
-  }
+  const G2sWs W = g2s_ws(cfg, lv, B);
+  if (workspace_bytes < W.total) return lm_workspace_short("hla_g2s_lm_solve", workspace_bytes, W.total);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  double* coef = (double*)(ws + oc);
-  float* pose = (float*)(ws + op);
-  double* part = (double*)(ws + opart);
+  double* coef = (double*)(ws + W.coef);
+  float* pose = (float*)(ws + W.pose);
+  double* part = (double*)(ws + W.part);
   if (pose0) HLA_CHECK_HIP(hipMemcpyAsync(pose, pose0, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   else HLA_CHECK_HIP(hipMemsetAsync(pose, 0, (size_t)B * 3 * sizeof(float), st));
 
-  const int L = cfg->n_levels, N = cfg->n_iters, steps = L * N;
+  const LmPlan plan = lm_plan_of(cfg);      // (level_first = 0: required above)
+  const int steps = plan.steps();
   auto geom = [&](int l) { return g2s_geom_of(cfg, lv[l], ori_h, ori_w); };
   G2sSolveArgs sa{};
   sa.pose = pose; sa.B = B; sa.camera_k = camera_k; sa.cfg.dof = 3; sa.cfg.use_hessian = 0;
@@ -280,24 +267,22 @@ extern "C" int hla_g2s_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   sa.coef = coef; sa.part = nullptr; sa.next = geom(0);
   hipLaunchKernelGGL(g2s_solve, dim3(B), dim3(64), 0, st, sa);
   for (int k = 0; k < steps; ++k) {
-    const int l = k % L, it = k / L;
-    const hla_s2g_level& v = lv[l];
+    const hla_s2g_level& v = lv[plan.level(k)];
+    const LmTiling til = g2s_tiling(v);
     G2sAccumArgs aa{};
     aa.src = (const float*)v.grd_feat; aa.fix = (const float*)v.sat_feat; aa.conf = v.grd_conf; aa.coef = coef; aa.part = part;
-    aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.ctr = v.A / 2; aa.npix = v.A * v.A;
-    aa.TP = lm_pick_tile(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.B = B;
-    aa.xcd_affine = (B >= 8) ? 1 : 0;
-    const int nblk = aa.xcd_affine ? 8 * ((B + 7) / 8) * aa.nt : B * aa.nt;
-    hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
-                   (double)B * ((double)v.h * v.w + (double)aa.npix) * v.C * 4.0, st);
+    lm_fill_g2s_dims(aa, v, til);
+    aa.TP = til.TP; aa.B = B; aa.xcd_affine = lm_xcd_affine(B);
+    const int nblk = lm_grid_blocks(aa.xcd_affine, B, aa.nt);
+    hla_prof_begin(lm_prof_id(v.C), 0, (double)B * ((double)v.h * v.w + (double)aa.npix) * v.C * 4.0, st);
     if (cfg->proj) launch_g2s_ip(v.C, dim3(nblk), st, aa);
     else if (cfg->using_weight) launch_g2s<true>(v.C, dim3(nblk), st, aa);
     else launch_g2s<false>(v.C, dim3(nblk), st, aa);
     hla_prof_end(st);
     sa.part = part; sa.nt = aa.nt; sa.src_inv = v.grd_inv_norm; sa.fix_inv = v.sat_inv_norm;
-    sa.trace_out = trace + ((size_t)it * L + l) * 3; sa.trace_stride = N * L * 3;
+    sa.trace_out = trace + plan.slot(k); sa.trace_stride = plan.trace_stride();
     sa.normal_eq = normal_eq ? normal_eq + (size_t)k * B * 16 : nullptr;
-    if (k + 1 < steps) { sa.coef = coef; sa.next = geom((k + 1) % L); }
+    if (k + 1 < steps) { sa.coef = coef; sa.next = geom(plan.level(k + 1)); }
     else sa.coef = nullptr;
     hla_prof_begin(K_LMSOLVE, 0, (double)B * aa.nt * PART_N * 8.0, st);
     hipLaunchKernelGGL(g2s_solve, dim3(B), dim3(64), 0, st, sa);
@@ -610,42 +595,29 @@ __global__ __launch_bounds__(64) void g2s_bwd_solve(G2sBwdSolveArgs a) {
   else g2s_coefficients(a.geom, pin[0], pin[1], pin[2], K9, a.coef + (size_t)b * G2S_COEF_N);
 }
 
-static size_t g2s_bwd_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B, size_t off[5]) {
-  int max_nt = 1;
-  for (int l = 0; l < cfg->n_levels; ++l) {
-    const int npix = lv[l].A * lv[l].A, tp = lm_pick_tile(npix);
-    max_nt = max(max_nt, (npix + tp - 1) / tp);
-  }
-  size_t o = 0;
-  off[0] = o; o += hla_align_up((size_t)B * G2S_COEF_N * sizeof(double), 256);
-  off[1] = o; o += hla_align_up((size_t)B * 16 * sizeof(double), 256);
-  off[2] = o; o += hla_align_up((size_t)B * 3 * sizeof(double), 256);
-  off[3] = o; o += hla_align_up((size_t)B * max_nt * G2S_PART_N * sizeof(double), 256);
-  off[4] = o;
-  return o;
+struct G2sBwdWs { size_t coef, adj, gid, part, total; };
+static G2sBwdWs g2s_bwd_ws(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B) {
+  G2sBwdWs W{};
+  LmBump ws;
+  W.coef = ws.take((size_t)B * G2S_COEF_N * sizeof(double));
+  W.adj = ws.take((size_t)B * 16 * sizeof(double));
+  W.gid = ws.take((size_t)B * 3 * sizeof(double));
+  W.part = ws.take((size_t)B * lm_max_nt(cfg, lv, g2s_tiling) * G2S_PART_N * sizeof(double));
+  W.total = ws.o;
+  return W;
 }
 
 extern "C" size_t hla_g2s_bwd_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B) {
-  size_t off[5];
-  return g2s_bwd_layout(cfg, levels, B, off);
+  return g2s_bwd_ws(cfg, levels, B).total;
 }
 
-template <bool W>
+template <bool W>      // (PROJ = 0 has no 16-channel instance)
 static void launch_g2s_bwd(int C, dim3 grid, hipStream_t st, const G2sBwdAccumArgs& a) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((g2s_bwd_accum<256, W>), grid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((g2s_bwd_accum<128, W>), grid, dim3(256), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((g2s_bwd_accum<64, W>), grid, dim3(256), 0, st, a); break;
-  }
+  lm_dispatch_c<256, 128, 64>(C, [&](auto c) { hipLaunchKernelGGL((g2s_bwd_accum<decltype(c)::value, W>), grid, dim3(256), 0, st, a); });
 }
 
 static void launch_g2s_ip_bwd(int C, dim3 grid, hipStream_t st, const G2sBwdAccumArgs& a) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((g2s_bwd_accum<256, false, 1>), grid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((g2s_bwd_accum<128, false, 1>), grid, dim3(256), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((g2s_bwd_accum<64, false, 1>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((g2s_bwd_accum<16, false, 1>), grid, dim3(256), 0, st, a); break;
-  }
+  lm_dispatch_c<256, 128, 64, 16>(C, [&](auto c) { hipLaunchKernelGGL((g2s_bwd_accum<decltype(c)::value, false, 1>), grid, dim3(256), 0, st, a); });
 }
 
 extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_level* lv, const hla_s2g_level_grad* gr,
@@ -662,33 +634,29 @@ extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
     HLA_REQUIRE(lv[l].sat_feat && lv[l].grd_feat && gr[l].d_sat_feat && gr[l].d_grd_feat, "hla_g2s_lm_solve_bwd: level %d buffers missing", l);
     HLA_REQUIRE(!cfg->using_weight || lv[l].grd_conf, "hla_g2s_lm_solve_bwd: using_weight needs grd_conf");
   }
-  size_t off[5];
-  const size_t need = g2s_bwd_layout(cfg, lv, B, off);
-  if (workspace_bytes < need) {
-    hla_set_error("hla_g2s_lm_solve_bwd: workspace %zu < %zu", workspace_bytes, need);
-    return HLA_ERR_WORKSPACE;
-  }
+  const G2sBwdWs W = g2s_bwd_ws(cfg, lv, B);
+  if (workspace_bytes < W.total) return lm_workspace_short("hla_g2s_lm_solve_bwd", workspace_bytes, W.total);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  double* coef = (double*)(ws + off[0]);
-  double* adj = (double*)(ws + off[1]);
-  double* gid = (double*)(ws + off[2]);
-  double* part = (double*)(ws + off[3]);
+  double* coef = (double*)(ws + W.coef);
+  double* adj = (double*)(ws + W.adj);
+  double* gid = (double*)(ws + W.gid);
+  double* part = (double*)(ws + W.part);
   HLA_CHECK_HIP(hipMemsetAsync(d_damping, 0, 3 * sizeof(double), st));
-  const int L = cfg->n_levels, N = cfg->n_iters, steps = L * N, tstride = N * L * 3;
-  auto slot = [&](int k) { return ((size_t)(k / L) * L + (k % L)) * 3; };
+  const LmPlan plan = lm_plan_of(cfg);      // (level_first = 0: required above)
+  const int steps = plan.steps(), tstride = plan.trace_stride();
   auto geom = [&](int l) { return g2s_geom_of(cfg, lv[l], ori_h, ori_w); };
   int nt_prev = 0;
   for (int k = steps - 1; k >= 0; --k) {
-    const int l = k % L;
+    const int l = plan.level(k);
     const hla_s2g_level& v = lv[l];
     G2sBwdSolveArgs sa{};
     sa.first = (k == steps - 1) ? 1 : 0;
-    if (!sa.first) { sa.part_next = part; sa.nt_next = nt_prev; sa.geom_next = geom((k + 1) % L); }
+    if (!sa.first) { sa.part_next = part; sa.nt_next = nt_prev; sa.geom_next = geom(plan.level(k + 1)); }
     sa.normal_eq = normal_eq + (size_t)k * B * 16;
-    if (k > 0) { sa.pose_in = trace + slot(k - 1); sa.pose_in_stride = tstride; }
+    if (k > 0) { sa.pose_in = trace + plan.slot(k - 1); sa.pose_in_stride = tstride; }
     else { sa.pose_in = pose0; sa.pose_in_stride = 3; }
-    sa.pose_out = trace + slot(k); sa.d_trace = d_trace + slot(k); sa.trace_stride = tstride;
+    sa.pose_out = trace + plan.slot(k); sa.d_trace = d_trace + plan.slot(k); sa.trace_stride = tstride;
     sa.gid = gid; sa.adj = adj; sa.coef = coef; sa.d_lambda = d_damping; sa.camera_k = camera_k; sa.B = B;
     sa.cfg.dof = 3; sa.cfg.use_hessian = 0;
     for (int i = 0; i < 3; ++i) sa.cfg.lam[i] = cfg->damping[i];
@@ -701,10 +669,10 @@ extern "C" int hla_g2s_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_lev
     aa.src = (const float*)v.grd_feat; aa.fix = (const float*)v.sat_feat; aa.conf = v.grd_conf; aa.coef = coef; aa.adj = adj;
     aa.src_inv = v.grd_inv_norm; aa.fix_inv = v.sat_inv_norm;
     aa.d_src = gr[l].d_grd_feat; aa.d_fix = gr[l].d_sat_feat; aa.d_conf = gr[l].d_grd_conf; aa.part = part;
-    aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.ctr = v.A / 2; aa.npix = v.A * v.A;
-    aa.TP = lm_pick_tile(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.B = B;
-    aa.xcd_affine = (B >= 8) ? 1 : 0;
-    const int nblk = aa.xcd_affine ? 8 * ((B + 7) / 8) * aa.nt : B * aa.nt;
+    const LmTiling til = g2s_tiling(v);
+    lm_fill_g2s_dims(aa, v, til);
+    aa.TP = til.TP; aa.B = B; aa.xcd_affine = lm_xcd_affine(B);
+    const int nblk = lm_grid_blocks(aa.xcd_affine, B, aa.nt);
     hla_prof_begin(K_LMBWD, 0, (double)B * (5.0 * (double)v.h * v.w + 3.0 * (double)aa.npix) * v.C * 4.0, st);
     if (cfg->proj) launch_g2s_ip_bwd(v.C, dim3(nblk), st, aa);
     else if (cfg->using_weight) launch_g2s_bwd<true>(v.C, dim3(nblk), st, aa);

@@ -12,7 +12,7 @@
 //   lm_solve     one wave per sample: fixed-order fp64 reduction of the tile partials (bitwise
 //                deterministic), 3x3/2x2/1x1 damped solve, pose update + re-initialisation rule,
 //                and the projection coefficients of the NEXT step (so no extra launch for them).
-#include "lm_common.h"
+#include "lm_host.h"
 #include <cstring>
 #include <mutex>
 
@@ -343,39 +343,30 @@ __global__ __launch_bounds__(256) void lm_inview_kernel(const double* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
-static size_t ws_layout(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B, size_t* off_coef, size_t* off_pose,
-                        size_t* off_part, int* part_ld) {
-  int max_nt = 1;
-  for (int l = 0; l < cfg->n_levels; ++l) {
-    const int npix = (lv[l].h - lv[l].row0) * lv[l].w;
-    const int tp = lm_pick_tile_fwd(npix);
-    max_nt = max(max_nt, (npix + tp - 1) / tp);
-  }
-  *part_ld = max_nt;
-  size_t o = 0;
-  *off_coef = o; o += hla_align_up((size_t)B * COEF_N * sizeof(double), 256);
-  *off_pose = o; o += hla_align_up((size_t)B * 3 * sizeof(float), 256);
-  *off_part = o; o += hla_align_up((size_t)B * max_nt * PART_N * sizeof(double), 256);
-  o += hla_align_up((size_t)B * cfg->n_levels * cfg->n_iters * sizeof(unsigned), 256);   // arrival tickets, one per step and sample
-  o += hla_align_up((size_t)B * cfg->n_levels * cfg->n_iters * sizeof(int), 256);   // in-view counts (count_in_view)
-  o += hla_align_up((size_t)B * 6 * sizeof(double), 256);      // ADAM moments (last region)
-  return o;
+static LmTiling fwd_tiling(const hla_s2g_level& v) { return lm_tiling(lm_npix_s2g(v), lm_pick_tile_fwd); }
+struct FwdWs { size_t coef, pose, part, ticket, in_view, adam, total; int part_ld; };
+static FwdWs fwd_ws(const hla_s2g_config* cfg, const hla_s2g_level* lv, int B) {
+  FwdWs W{};
+  W.part_ld = lm_max_nt(cfg, lv, fwd_tiling);
+  const size_t per_step = (size_t)B * cfg->n_levels * cfg->n_iters;
+  LmBump ws;
+  W.coef = ws.take((size_t)B * COEF_N * sizeof(double));
+  W.pose = ws.take((size_t)B * 3 * sizeof(float));
+  W.part = ws.take((size_t)B * W.part_ld * PART_N * sizeof(double));
+  W.ticket = ws.take(per_step * sizeof(unsigned));      // arrival tickets, one per step and sample
+  W.in_view = ws.take(per_step * sizeof(int));          // in-view counts (count_in_view)
+  W.adam = ws.take((size_t)B * 6 * sizeof(double));     // ADAM moments
+  W.total = ws.o;
+  return W;
 }
 
 extern "C" size_t hla_s2g_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B) {
-  size_t a, b, c;
-  int ld;
-  return ws_layout(cfg, levels, B, &a, &b, &c, &ld);
+  return fwd_ws(cfg, levels, B).total;
 }
 
 template <bool W, typename F>
 static void launch_accum_f(int C, dim3 grid, hipStream_t st, const AccumArgs& a, const SolveArgs& sa) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((lm_accum<256, W, F>), grid, dim3(256), 0, st, a, sa); break;
-    case 128: hipLaunchKernelGGL((lm_accum<128, W, F>), grid, dim3(256), 0, st, a, sa); break;
-    case 64: hipLaunchKernelGGL((lm_accum<64, W, F>), grid, dim3(256), 0, st, a, sa); break;
-    case 16: hipLaunchKernelGGL((lm_accum<16, W, F>), grid, dim3(256), 0, st, a, sa); break;
-  }
+  lm_dispatch_c<256, 128, 64, 16>(C, [&](auto c) { hipLaunchKernelGGL((lm_accum<decltype(c)::value, W, F>), grid, dim3(256), 0, st, a, sa); });
 }
 template <bool W>
 static void launch_accum(int C, int feat_dtype, dim3 grid, hipStream_t st, const AccumArgs& a, const SolveArgs& sa) {
@@ -475,47 +466,31 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   HLA_REQUIRE(cfg->optimizer >= 0 && cfg->optimizer <= 3, "hla_s2g_lm_solve: optimizer must be 0 (LM), 1 (SGD), 2 (ADAM) or 3 (GN)");
   HLA_REQUIRE(cfg->optimizer == 0 || !cfg->level_first, "hla_s2g_lm_solve: SGD / ADAM / GN exist for the iteration-first loop only");
   HLA_REQUIRE(cfg->optimizer != 3 || cfg->ford, "hla_s2g_lm_solve: GN_update exists in the Ford model only");
-  const bool newton = cfg->optimizer == 0 || cfg->optimizer == 3;
-  const bool reinit = (cfg->ford || cfg->dof == 3) && newton;     // SGD_update / ADAM_update never re-initialise
+  const bool newton = lm_newton(cfg), reinit = lm_reinit(cfg);
   HLA_REQUIRE(!reinit || rand_uv, "hla_s2g_lm_solve: rand_uv required");
-  size_t oc, op, opart;
-  int part_ld;
-  const size_t need = ws_layout(cfg, lv, B, &oc, &op, &opart, &part_ld);
-  if (workspace_bytes < need) {
-    hla_set_error("hla_s2g_lm_solve: workspace %zu < %zu", workspace_bytes, need);
-    return HLA_ERR_WORKSPACE;
-  }
+  const FwdWs W = fwd_ws(cfg, lv, B);
+  if (workspace_bytes < W.total) return lm_workspace_short("hla_s2g_lm_solve", workspace_bytes, W.total);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  double* coef = (double*)(ws + oc);
-  float* pose = (float*)(ws + op);
-  double* part = (double*)(ws + opart);
+  double* coef = (double*)(ws + W.coef);
+  float* pose = (float*)(ws + W.pose);
+  double* part = (double*)(ws + W.part);
+  unsigned* ticket = (unsigned*)(ws + W.ticket);
+  int* in_view = (int*)(ws + W.in_view);
+  double* adam = (double*)(ws + W.adam);
 
   if (pose0) HLA_CHECK_HIP(hipMemcpyAsync(pose, pose0, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   // (otherwise the init launch below starts the pose at zero; it also clears the arrival counters: two memset launches less)
 
-  const int L = cfg->n_levels, N = cfg->n_iters, steps = L * N;
-  auto step_level = [&](int k) { return cfg->level_first ? k / N : k % L; };
-  auto step_iter = [&](int k) { return cfg->level_first ? k % N : k / L; };
-  auto geom = [&](int l) {
-    LmGeom g{};
-    g.ford = cfg->ford; g.lat = cfg->shift_range_lat; g.lon = cfg->shift_range_lon; g.rot = cfg->rotation_range;
-    g.mpp = lv[l].meter_per_pixel; g.ctr = lv[l].centre;
-    return g;
-  };
-
-  double* adam = (double*)(ws + need - hla_align_up((size_t)B * 6 * sizeof(double), 256));
-  int* in_view = (int*)((char*)adam - hla_align_up((size_t)B * steps * sizeof(int), 256));
-  unsigned* ticket = (unsigned*)((char*)in_view - hla_align_up((size_t)B * steps * sizeof(unsigned), 256));
+  const LmPlan plan = lm_plan_of(cfg);
+  const int L = plan.L, steps = plan.steps();
   const bool count = cfg->count_in_view && normal_eq;
   if (count) HLA_CHECK_HIP(hipMemsetAsync(in_view, 0, (size_t)B * steps * sizeof(int), st));
   if (cfg->optimizer == 2) HLA_CHECK_HIP(hipMemsetAsync(adam, 0, (size_t)B * 6 * sizeof(double), st));
   SolveArgs sa{};
   sa.optimizer = cfg->optimizer; sa.beta1 = cfg->beta1; sa.beta2 = cfg->beta2; sa.adam = adam;
-  sa.pose = pose; sa.B = B; sa.part_ld = part_ld; sa.reinit = reinit ? 1 : 0; sa.R_FL = R_FL; sa.T_FL = T_FL;
-  sa.cfg.gn = cfg->optimizer == 3 ? 1 : 0;
-  sa.cfg.dof = cfg->dof; sa.cfg.use_hessian = sa.cfg.gn ? 0 : cfg->use_hessian;
-  for (int i = 0; i < 3; ++i) sa.cfg.lam[i] = sa.cfg.gn ? 0.0 : cfg->damping[i];     // GN_update: delta = -H^-1 J^T W r
+  sa.pose = pose; sa.B = B; sa.part_ld = W.part_ld; sa.reinit = reinit ? 1 : 0; sa.R_FL = R_FL; sa.T_FL = T_FL;
+  sa.cfg = lm_solve_cfg_of(cfg);
   sa.coef = coef;
 
   // reach_mode 2: the init step and all steps of the flagged samples as one launch of lm_repair_loop, a workgroup per sample.
@@ -532,19 +507,17 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
       const hla_s2g_level& v = lv[l];
       RepairLevel& r = ra.lv[l];
       r.sat = v.sat_feat; r.grd = v.grd_feat; r.pts = lm_points_of(v); r.sat_inv = v.sat_inv_norm; r.grd_inv = v.grd_inv_norm;
-      r.A = v.A; r.h = v.h; r.w = v.w; r.row0 = v.row0; r.npix = (v.h - v.row0) * v.w;
-      r.TP = lm_pick_tile_fwd(r.npix); r.nt = (r.npix + r.TP - 1) / r.TP;
-      r.hs = v.h - v.grd_row_skip; r.rskip = v.grd_row_skip; r.C = v.C;
-      r.mpp = v.meter_per_pixel; r.ctr = v.centre;
+      lm_fill_s2g_dims(r, v, fwd_tiling(v));
+      r.C = v.C; r.mpp = v.meter_per_pixel; r.ctr = v.centre;
     }
     ra.sa = sa;
-    ra.sa.next = geom(0);      // (mpp and ctr are set per step, from the level the next step runs on)
+    ra.sa.next = lm_geom_of(cfg, lv[0]);      // (mpp and ctr are set per step, from the level the next step runs on)
     ra.sa.zero_pose = pose0 ? 0 : 1;
     ra.sa.gate = cfg->reach_flag;
     ra.part = part;
     ra.keep = cfg->keep; ra.keep_stride = (size_t)cfg->keep_stride;
     ra.trace = trace; ra.rand_uv = rand_uv; ra.normal_eq = normal_eq;
-    ra.L = L; ra.N = N; ra.level_first = cfg->level_first;
+    ra.L = L; ra.N = plan.N; ra.level_first = plan.level_first;
     hla_prof_begin(K_LMREPAIR, 0, 0, st);
     if (lv[0].feat_dtype == HLA_BF16) hipLaunchKernelGGL(lm_repair_loop<__bf16>, dim3(B), dim3(256 * LM_REPAIR_GROUPS), 0, st, ra);
     else hipLaunchKernelGGL(lm_repair_loop<_Float16>, dim3(B), dim3(256 * LM_REPAIR_GROUPS), 0, st, ra);
@@ -554,7 +527,7 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
   }
 
   // init launch: coefficients of step 0
-  sa.part = nullptr; sa.next = geom(step_level(0));
+  sa.part = nullptr; sa.next = lm_geom_of(cfg, lv[plan.level(0)]);
   sa.zero_ticket = ticket; sa.zero_steps = steps; sa.zero_pose = pose0 ? 0 : 1;
   // (reach_mode 2: the arrival counters and the pose of a skipped sample are never looked at, so they need no care)
   sa.reach_clear = cfg->reach_mode == 1 ? cfg->reach_flag : nullptr;
@@ -599,26 +572,24 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
 
   // steps interleaved over the groups: each group's launches stay in order on its own stream
   for (int k = 0; k < steps && err == hipSuccess; ++k) {
-    const int l = step_level(k), it = step_iter(k);
+    const int l = plan.level(k);
     const hla_s2g_level& v = lv[l];
     AccumArgs aa{};
     aa.sat = v.sat_feat; aa.grd = v.grd_feat; aa.conf = v.grd_conf; aa.pts = lm_points_of(v); aa.coef = coef; aa.part = part;
-    aa.A = v.A; aa.h = v.h; aa.w = v.w; aa.row0 = v.row0; aa.npix = (v.h - v.row0) * v.w;
-    aa.hs = v.h - v.grd_row_skip; aa.rskip = v.grd_row_skip;
+    lm_fill_s2g_dims(aa, v, fwd_tiling(v));
     aa.keep = cfg->keep ? cfg->keep + (size_t)k * cfg->keep_stride : nullptr;
-    aa.TP = lm_pick_tile_fwd(aa.npix); aa.nt = (aa.npix + aa.TP - 1) / aa.TP; aa.part_ld = part_ld;
-    aa.xcd_affine = (B >= 8) ? 1 : 0;
+    aa.part_ld = W.part_ld; aa.xcd_affine = lm_xcd_affine(B);
     aa.ticket = ticket + (size_t)k * B;
     if (cfg->reach_mode == 1) { aa.col0 = cfg->reach_col0[l]; aa.reach_flag = cfg->reach_flag; }
     aa.gate = sa.gate;
     // the step's closing solve runs inside the same launch (last tile of each sample): its arguments
     sa.t = k;
     sa.part = part; sa.nt = aa.nt; sa.sat_inv = v.sat_inv_norm; sa.grd_inv = v.grd_inv_norm;
-    sa.trace_out = trace + ((size_t)it * L + l) * 3; sa.trace_stride = N * L * 3;
+    sa.trace_out = trace + plan.slot(k); sa.trace_stride = plan.trace_stride();
     sa.rand_uv = reinit ? rand_uv + (size_t)k * 2 * B : nullptr;
     sa.normal_eq = normal_eq ? normal_eq + (size_t)k * B * 16 : nullptr;
     sa.in_view = count ? in_view + (size_t)k * B : nullptr;
-    if (k + 1 < steps) { sa.coef = coef; sa.next = geom(step_level(k + 1)); }
+    if (k + 1 < steps) { sa.coef = coef; sa.next = lm_geom_of(cfg, lv[plan.level(k + 1)]); }
     else sa.coef = nullptr;
     const double esz = v.feat_dtype == HLA_F32 ? 4.0 : 2.0;
     for (int g = 0; g < ng; ++g) {
@@ -627,9 +598,8 @@ extern "C" int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* 
       if (count)
         hipLaunchKernelGGL(lm_inview_kernel, dim3((v.h * v.w + 255) / 256, aa.nb), dim3(256), 0, gs, coef, aa.pts, v.w, v.A, v.h * v.w,
                            in_view + (size_t)k * B, aa.b0);
-      const int nblk = aa.xcd_affine ? 8 * ((aa.nb + 7) / 8) * aa.nt : aa.nb * aa.nt;
-      hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
-                     (double)aa.nb * ((double)v.A * v.A + (double)aa.npix) * v.C * esz, gs);
+      const int nblk = lm_grid_blocks(aa.xcd_affine, aa.nb, aa.nt);
+      hla_prof_begin(lm_prof_id(v.C), 0, (double)aa.nb * ((double)v.A * v.A + (double)aa.npix) * v.C * esz, gs);
       if (cfg->using_weight && newton) launch_accum<true>(v.C, v.feat_dtype, dim3(nblk), gs, aa, sa);   // SGD / ADAM ignore the confidence
       else launch_accum<false>(v.C, v.feat_dtype, dim3(nblk), gs, aa, sa);
       hla_prof_end(gs);

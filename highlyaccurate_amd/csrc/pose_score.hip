@@ -14,7 +14,7 @@
 //             the cost.
 // The tile size follows from the level alone (C and the element type), and a hypothesis never shares an accumulator with
 // another one: sums and cost of (b, k) do not depend, bit for bit, on the other hypotheses, on k, on K, on B or on repeats.
-#include "lm_common.h"
+#include "lm_host.h"
 
 constexpr int PS_KC = 32;        // hypotheses per block
 constexpr int PS_NPL = 4;        // pixels per lane (their ground vectors live in registers)
@@ -66,6 +66,7 @@ static inline int ps_tile(int C, int feat_dtype) {
   const int epl = feat_dtype == HLA_F32 ? 4 : 8;
   return 4 * (64 / (C / epl)) * PS_NPL;
 }
+static LmTiling ps_tiling(const hla_s2g_level& v) { return lm_tiling(lm_npix_s2g(v), [&](int) { return ps_tile(v.C, v.feat_dtype); }); }
 
 template <int C, bool USE_W, typename F>
 __global__ __launch_bounds__(256) void ps_accum(PsArgs a) {
@@ -228,12 +229,7 @@ __global__ __launch_bounds__(64) void ps_close(const float* __restrict__ part, c
 
 template <bool W, typename F>
 static void ps_launch_f(int C, dim3 grid, hipStream_t st, const PsArgs& a) {
-  switch (C) {
-    case 256: hipLaunchKernelGGL((ps_accum<256, W, F>), grid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL((ps_accum<128, W, F>), grid, dim3(256), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((ps_accum<64, W, F>), grid, dim3(256), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((ps_accum<16, W, F>), grid, dim3(256), 0, st, a); break;
-  }
+  lm_dispatch_c<256, 128, 64, 16>(C, [&](auto c) { hipLaunchKernelGGL((ps_accum<decltype(c)::value, W, F>), grid, dim3(256), 0, st, a); });
 }
 template <bool W>
 static void ps_launch(int C, int feat_dtype, dim3 grid, hipStream_t st, const PsArgs& a) {
@@ -258,16 +254,17 @@ static int ps_check(const char* who, const hla_s2g_config* cfg, const hla_s2g_le
   HLA_REQUIRE(v->grd_row_skip >= 0 && v->grd_row_skip <= v->row0, "%s: grd_row_skip must be in [0,row0]", who);
   HLA_REQUIRE((size_t)v->A * v->A * C < (1u << 31), "%s: satellite map too large", who);
   HLA_REQUIRE((long long)(v->h - v->row0) * v->w < (1LL << 31), "%s: ground map too large", who);
-  const long long npix = (long long)(v->h - v->row0) * v->w, tp = ps_tile(C, v->feat_dtype), nt = (npix + tp - 1) / tp;
-  const long long blocks = (long long)(8 * ((B + 7) / 8)) * nt * ((K + PS_KC - 1) / PS_KC);
+  const long long blocks = (long long)lm_grid_blocks(1, B, 1) * ps_tiling(*v).nt * ((K + PS_KC - 1) / PS_KC);
   HLA_REQUIRE(blocks < (1LL << 31) && (long long)B * K < (1LL << 31), "%s: B * K too large for one launch", who);
   return HLA_OK;
 }
 
+// the one region: the tile partials [B,K,nt,PS_NS]
+static size_t ps_ws_bytes(int B, int K, const LmTiling& t) { return lm_one_region_bytes((size_t)B * K * t.nt * PS_NS * sizeof(float)); }
+
 extern "C" size_t hla_s2g_pose_score_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K) {
   if (ps_check("hla_s2g_pose_score_workspace_bytes", cfg, level, B, K)) return 0;
-  const int npix = (level->h - level->row0) * level->w, tp = ps_tile(level->C, level->feat_dtype), nt = (npix + tp - 1) / tp;
-  return hla_align_up((size_t)B * K * nt * PS_NS * sizeof(float), 256);
+  return ps_ws_bytes(B, K, ps_tiling(*level));
 }
 
 extern "C" int hla_s2g_pose_score(const hla_s2g_config* cfg, const hla_s2g_level* level, const float* R_FL, const float* T_FL,
@@ -281,24 +278,18 @@ extern "C" int hla_s2g_pose_score(const hla_s2g_config* cfg, const hla_s2g_level
   PsArgs a{};
   a.sat = v.sat_feat; a.grd = v.grd_feat; a.conf = v.grd_conf; a.pts = lm_points_of(v);
   a.poses = poses; a.R_FL = cfg->ford ? R_FL : nullptr; a.T_FL = cfg->ford ? T_FL : nullptr;
-  a.geom.ford = cfg->ford; a.geom.lat = cfg->shift_range_lat; a.geom.lon = cfg->shift_range_lon; a.geom.rot = cfg->rotation_range;
-  a.geom.mpp = v.meter_per_pixel; a.geom.ctr = v.centre;
-  a.A = v.A; a.h = v.h; a.w = v.w; a.row0 = v.row0; a.npix = (v.h - v.row0) * v.w;
-  a.hs = v.h - v.grd_row_skip; a.rskip = v.grd_row_skip;
-  a.TP = ps_tile(v.C, v.feat_dtype); a.nt = (a.npix + a.TP - 1) / a.TP; a.nch = (K + PS_KC - 1) / PS_KC;
-  a.K = K; a.B = B; a.xcd_affine = B >= 8 ? 1 : 0;
-  const size_t need = hla_align_up((size_t)B * K * a.nt * PS_NS * sizeof(float), 256);
-  if (workspace_bytes < need) {
-    hla_set_error("hla_s2g_pose_score: workspace %zu < %zu", workspace_bytes, need);
-    return HLA_ERR_WORKSPACE;
-  }
+  a.geom = lm_geom_of(cfg, v);
+  const LmTiling til = ps_tiling(v);
+  lm_fill_s2g_dims(a, v, til);
+  a.nch = (K + PS_KC - 1) / PS_KC;
+  a.K = K; a.B = B; a.xcd_affine = lm_xcd_affine(B);
+  const size_t need = ps_ws_bytes(B, K, til);
+  if (workspace_bytes < need) return lm_workspace_short("hla_s2g_pose_score", workspace_bytes, need);
   a.part = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  const int per = a.nt * a.nch;
-  const int nblk = a.xcd_affine ? 8 * ((B + 7) / 8) * per : B * per;
+  const int nblk = lm_grid_blocks(a.xcd_affine, B, a.nt * a.nch);
   const double esz = v.feat_dtype == HLA_F32 ? 4.0 : 2.0;
-  hla_prof_begin(v.C == 256 ? K_LM256 : v.C == 128 ? K_LM128 : v.C == 64 ? K_LM64 : K_LM16, 0,
-                 (double)B * ((double)v.A * v.A + (double)a.npix * a.nch) * v.C * esz, st);
+  hla_prof_begin(lm_prof_id(v.C), 0, (double)B * ((double)v.A * v.A + (double)a.npix * a.nch) * v.C * esz, st);
   if (cfg->using_weight) ps_launch<true>(v.C, v.feat_dtype, dim3(nblk), st, a);
   else ps_launch<false>(v.C, v.feat_dtype, dim3(nblk), st, a);
   hla_prof_end(st);
