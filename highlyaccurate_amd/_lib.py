@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 class HlaError(RuntimeError):
@@ -191,6 +191,11 @@ def load() -> C.CDLL:
     lib.hla_s2g_pose_score_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, i]
     lib.hla_s2g_pose_score.restype = i
     lib.hla_s2g_pose_score.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), vp, vp, vp, i, vp, vp, vp, sz, i, vp]
+    lib.hla_s2g_pose_score_bwd_workspace_bytes.restype = sz
+    lib.hla_s2g_pose_score_bwd_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, i]
+    lib.hla_s2g_pose_score_bwd.restype = i
+    lib.hla_s2g_pose_score_bwd.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), C.POINTER(S2GLevelGrad), vp, vp, vp, i, vp, vp,
+                                           vp, sz, i, vp]
     lib.hla_s2g_bwd_workspace_bytes.restype = sz
     lib.hla_s2g_bwd_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i]
     lib.hla_s2g_lm_solve_bwd.restype = i

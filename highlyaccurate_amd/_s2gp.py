@@ -285,6 +285,7 @@ class S2GPBase(nn.Module):
         self.last_features = None
         self.last_reach_flag = None  # int32 [B] of the last localise that ran with args.sat_reach_crop in effect (1: recomputed), else None
         self.last_search = None      # forward_search: cost, sums, start_index, traces, final_cost, best of the last call
+        self.last_score_loss = None  # score_loss: costs [B,K+1] and sums [B,K+1,8] per scored level of the last call (entry 0: the true pose)
 
     # -- geometry tables ---------------------------------------------------------------------
     def xyz_tables(self, grd_H: int, grd_W: int, device):
@@ -616,6 +617,102 @@ class S2GPBase(nn.Module):
                                     _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
         _lib.check(rc, 'hla_s2g_pose_score')
         return cost, sums
+
+    @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
+    def score_poses_bwd(self, sat_feats, grd_feats, grd_confs, grd_hw, poses, level, sums, d_cost, extra=None, sat_inv_norm=None,
+                        grd_inv_norm=None):
+        """Backward of ``score_poses`` (``hla_s2g_pose_score_bwd``, include/hla.h): the same map arguments (fp32 maps), ``sums``
+        [B,K,8] of the forward and ``d_cost`` [B,K] -> (d_sat [B,A,A,C], d_grd like grd_feats[level], d_conf [B,h,w] or None) of
+        level ``level``, fp32 NHWC, with respect to the L2-normalised maps -- what ``vgg_backward_nhwc(..., scale_invariant=True)``
+        takes.  All three are written by the call (ground rows above row0 are zero); poses get no gradient.  d_grd and d_conf are
+        bitwise reproducible, d_sat (fp32 atomics) is not."""
+        B, L = sat_feats[0].shape[0], len(sat_feats)
+        p = _poses_arg(poses, B)
+        if not 0 <= int(level) < L:
+            raise ValueError(f'level must be in [0, {L}), got {level}')
+        _lib.require_gpu(sat_feats[0], 'sat_feats')
+        lib = _lib.load()
+        dev = sat_feats[0].device
+        l = int(level)
+        cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, 0, sat_inv_norm, grd_inv_norm)
+        p = p.to(dev).contiguous()
+        K = p.shape[1]
+        if tuple(sums.shape) != (B, K, 8) or sums.dtype != torch.float64 or tuple(d_cost.shape) != (B, K):
+            raise ValueError(f'expected sums [B,K,8] fp64 and d_cost [B,K] with B = {B}, K = {K}, got {tuple(sums.shape)} '
+                             f'{sums.dtype} and {tuple(d_cost.shape)}')
+        sums, dc = sums.to(dev).contiguous(), d_cost.to(dev).float().contiguous()
+        one = C.byref(lv[l])
+        d_sat, d_grd = torch.empty_like(sat_feats[l], dtype=torch.float32), torch.empty_like(grd_feats[l], dtype=torch.float32)
+        d_conf = torch.empty_like(grd_confs[l]) if cfg.using_weight else None
+        gr = _lib.S2GLevelGrad()
+        gr.d_sat_feat, gr.d_grd_feat, gr.d_grd_conf = d_sat.data_ptr(), d_grd.data_ptr(), d_conf.data_ptr() if d_conf is not None else 0
+        nbytes = lib.hla_s2g_pose_score_bwd_workspace_bytes(C.byref(cfg), one, B, K)
+        if nbytes == 0:
+            _lib.check(-1, 'hla_s2g_pose_score_bwd_workspace_bytes')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.hla_s2g_pose_score_bwd(C.byref(cfg), one, C.byref(gr), _lib.ptr(R_FL), _lib.ptr(T_FL), _lib.ptr(p), K, _lib.ptr(sums),
+                                        _lib.ptr(dc), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
+        _lib.check(rc, 'hla_s2g_pose_score_bwd')
+        return d_sat, d_grd, d_conf
+
+    def _score_checks(self, what, sat_map, grd_img):
+        if getattr(self.args, 'dropout', 0):
+            raise NotImplementedError(f'{what} with args.dropout: a pose is scored on every pixel, the dropout loop on a random '
+                                      'half -- their objectives differ')
+        if self.level != 3:
+            raise NotImplementedError(f'{what} is built for args.level = 3 (x15, x18, x21), got level {self.level}')
+        _lib.require_gpu(sat_map, 'sat_map')
+        _lib.require_gpu(grd_img, 'grd_img')
+        if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
+                or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
+            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
+                             f'and {tuple(grd_img.shape)}')
+        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
+
+    @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
+    def score_candidates(self, sat_map, grd_img, poses, levels=None, extra=None):
+        """The LM objective at ``poses`` ([K,3] or [B,K,3], normalised units) on the maps of the two images, differentiable with
+        respect to both extractors' parameters (not the poses): -> (costs, sums), a list of [B,K] fp32 costs and a list of
+        [B,K,8] fp64 sums, one entry per level in ``levels`` (default: every level).  Under autograd it is ONE autograd.Function:
+        both extractors with their activations saved, ``hla_s2g_pose_score`` per scored level; its backward runs
+        ``hla_s2g_pose_score_bwd`` per scored level and ``hla_vgg_backward`` for both extractors.  ``sums`` carry no gradient.
+        Without grad it is the inference extractors plus ``score_poses``.  ``extra``: the Ford dict (R_FL, T_FL, side_m)."""
+        self._score_checks('score_candidates', sat_map, grd_img)
+        B = sat_map.shape[0]
+        cand = _poses_arg(poses, B).to(sat_map.device).contiguous()
+        lvls = tuple(range(self.level)) if levels is None else tuple(int(l) for l in levels)
+        if not lvls or len(set(lvls)) != len(lvls) or not all(0 <= l < self.level for l in lvls):
+            raise ValueError(f'levels must be distinct indices in [0, {self.level}), got {levels}')
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            names = [n for n, _ in self.named_parameters()]
+            params = [p for _, p in self.named_parameters()]
+            out = _ScoreFn.apply(self, names, sat_map, grd_img, cand, lvls, extra, *params)
+            n = len(lvls)
+            return list(out[:n]), list(out[n:])
+        with torch.no_grad():
+            sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, bool(self.using_weight), False)
+            res = [self.score_poses(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], cand, l, extra, sat_inv, grd_inv) for l in lvls]
+        return [r[0] for r in res], [r[1] for r in res]
+
+    def _score_loss(self, sat_map, grd_img, extra, candidates, gt_pose, levels, min_in_view):
+        """``score_loss`` of both models.  gt_pose: (shift_u, shift_v, heading), each [B] or [B,1], normalised units."""
+        self._score_checks('score_loss', sat_map, grd_img)
+        B, dev = sat_map.shape[0], sat_map.device
+        cand = _poses_arg(candidates, B, 'candidates').to(dev)
+        gt = torch.stack([torch.as_tensor(g, dtype=torch.float32).detach().to(dev).reshape(B) for g in gt_pose], dim=1)
+        poses = torch.cat([gt[:, None, :], cand], dim=1).contiguous()             # entry 0: the ground truth
+        costs, sums = self.score_candidates(sat_map, grd_img, poses, levels, extra)
+        K = cand.shape[1]
+        loss = 0
+        for cost, s in zip(costs, sums):
+            # eligible_cost's in-view rule over the K + 1 entries; an ineligible negative contributes exactly zero
+            in_view = s[..., 6]
+            ok = (in_view >= float(min_in_view) * in_view.max(dim=1, keepdim=True).values)[:, 1:]
+            # models_kitti.py:592, 1622: log(1 + exp(10 (pos - neg))), averaged; cost <= 4 keeps the exponent below 40
+            t = torch.log(1 + torch.exp(10.0 * (cost[:, :1] - cost[:, 1:])))
+            loss = loss + torch.where(ok, t, torch.zeros_like(t)).sum() / (B * K)     # models_kitti.py:595: summed over the levels
+        self.last_score_loss = dict(costs=[c.detach() for c in costs], sums=sums)
+        return loss
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def _search(self, sat_map, grd_img, extra, candidates, top_m, score_level, min_in_view, level_first):
@@ -1038,5 +1135,60 @@ class _LocaliseFn(torch.autograd.Function):
         ctx.state = None            # release the saved workspaces now, not when the loss tensor dies
         _phase('vgg_bwd')
         return (None,) * 9 + tuple(grads.get(n) for n in ctx.names)
+
+
+class _ScoreFn(torch.autograd.Function):
+    """``S2GPBase.score_candidates`` under autograd.  forward: the costs [B,K] of every scored level, then their sums [B,K,8]
+    (non-differentiable); backward: parameter gradients of both extractors from HIP kernels (level 3 models)."""
+
+    @staticmethod
+    def forward(ctx, model, names, sat_map, grd_img, poses, levels, extra, *params):
+        want_conf = bool(model.using_weight)
+        sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True,
+                                                     save_for_backward=True)
+        grd_feats, grd_confs, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=want_conf, defer_norm=True,
+                                                             save_for_backward=True)
+        if grd_confs is None:
+            grd_confs = [None] * len(grd_feats)
+        hw = tuple(grd_img.shape[-2:])
+        res = [model.score_poses(sat_feats, grd_feats, grd_confs, hw, poses, l, extra, sat_inv, grd_inv) for l in levels]
+        costs, sums = tuple(r[0] for r in res), tuple(r[1] for r in res)
+        ctx.model, ctx.names, ctx.extra, ctx.levels = model, names, extra, levels
+        ctx.state = (sat_feats, grd_feats, grd_confs, hw, poses, sums, sat_inv, grd_inv, cs, cg)
+        ctx.mark_non_differentiable(*sums)
+        ctx.set_materialize_grads(False)
+        return costs + sums
+
+    @staticmethod
+    def backward(ctx, *d_out):
+        model = ctx.model
+        if ctx.state is None:
+            raise RuntimeError('backward through the same score_candidates call twice: the saved activations are released after '
+                               'the first backward; retain_graph is not supported by the HIP backward')
+        sat_feats, grd_feats, grd_confs, hw, poses, sums, sat_inv, grd_inv, cs, cg = ctx.state
+        use_w = bool(model.using_weight) and all(c is not None for c in grd_confs)
+        d_sat, d_grd, d_conf = [None] * len(sat_feats), [None] * len(sat_feats), [None] * len(sat_feats)
+        for n, l in enumerate(ctx.levels):
+            if d_out[n] is None:            # this level's cost was not used downstream
+                continue
+            d_sat[l], d_grd[l], d_conf[l] = model.score_poses_bwd(sat_feats, grd_feats, grd_confs, hw, poses, l, sums[n], d_out[n],
+                                                                  ctx.extra, sat_inv, grd_inv)
+        for l in range(len(sat_feats)):     # an unscored level takes no part: zeros
+            if d_sat[l] is None:
+                d_sat[l], d_grd[l] = torch.zeros_like(sat_feats[l]), torch.zeros_like(grd_feats[l])
+            if use_w and d_conf[l] is None:
+                d_conf[l] = torch.zeros_like(grd_confs[l])
+        # the cost renormalises both maps: every d_map is orthogonal to its map (HLA_VGG_BWD_SCALE_INVARIANT, include/hla.h), and
+        # the ground maps' gradient lives in the rows the score reads (row0..: the backward skips the rows above its support)
+        trim = bool(getattr(model.args, 'bwd_trim', 1))
+        f8 = 0 if model.polar else _bwd_first_row8(model, hw, grd_feats[-1].shape[1])
+        tp = int(getattr(model.args, 'wgrad_two_phase', 0))
+        g_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, scale_invariant=True, dense=not trim, wgrad_two_phase=tp)
+        g_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
+                                  scale_invariant=True, first_row8=f8, dense=not trim, wgrad_two_phase=tp)
+        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
+        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
+        ctx.state = None                    # release the saved workspaces now
+        return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)
 
 

@@ -41,3 +41,11 @@ class LM_S2GP_Ford(S2GPBase):
         extra = dict(R_FL=R_FL, T_FL=T_FL, side_m=float(satmap_sidelength_meters))
         pose = self._search(sat_map, grd_img_left, extra, candidates, top_m, score_level, min_in_view, level_first)
         return pose[:, 0], pose[:, 1], pose[:, 2]
+
+    def score_loss(self, sat_map, grd_img_left, satmap_sidelength_meters, R_FL, T_FL, candidates, gt_shiftu, gt_shiftv, gt_heading,
+                   levels=None, min_in_view=0.5):
+        """``LM_S2GP.score_loss`` on the Ford chain: the triplet-form loss of the true pose (gt_shiftu, gt_shiftv, gt_heading)
+        against ``candidates`` on the score surface of ``forward_search``, summed over the scored levels; a scalar that
+        back-propagates into both extractors.  ``last_score_loss`` keeps the costs and sums."""
+        extra = dict(R_FL=R_FL, T_FL=T_FL, side_m=float(satmap_sidelength_meters))
+        return self._score_loss(sat_map, grd_img_left, extra, candidates, (gt_shiftu, gt_shiftv, gt_heading), levels, min_in_view)

@@ -105,3 +105,18 @@ class LM_S2GP(S2GPBase):
             raise NotImplementedError('forward_search with a depth map: depth-lifted pose scoring is not built')
         pose = self._search(sat_map, grd_img_left, None, candidates, top_m, score_level, min_in_view, level_first)
         return pose[:, 1], pose[:, 0], pose[:, 2]
+
+    def score_loss(self, sat_map, grd_img_left, candidates, gt_shiftu, gt_shiftv, gt_heading, levels=None, min_in_view=0.5,
+                   gt_depth=None):
+        """Metric learning on the surface ``forward_search`` ranks with (an extension, in the form of the reference's
+        triplet_loss, models_kitti.py:579-595 and 1607-1624): the pose list of every sample is the true pose (gt_shiftu,
+        gt_shiftv, gt_heading: [B] or [B,1], normalised units) followed by ``candidates`` ([K,3] or [B,K,3], e.g.
+        ``pose_grid(5, 5, 5)``); per scored level (``levels``, default all)
+            loss_l = sum_b sum_k log(1 + exp(10 (cost[b, true] - cost[b, k]))) / (B K)
+        over the candidates that keep at least ``min_in_view`` of the sample's best pixel count in view (``eligible_cost``'s rule
+        over the K + 1 entries; the others contribute exactly zero), and the result is the sum over the levels: a scalar that
+        back-propagates into both extractors through HIP kernels (``score_candidates``).  Call it next to
+        ``forward(mode='train')``.  ``last_score_loss`` keeps the costs [B,K+1] and sums [B,K+1,8] per level."""
+        if gt_depth is not None and getattr(self.args, 'use_gt_depth', 0):
+            raise NotImplementedError('score_loss with a depth map: depth-lifted pose scoring is not built')
+        return self._score_loss(sat_map, grd_img_left, None, candidates, (gt_shiftu, gt_shiftv, gt_heading), levels, min_in_view)

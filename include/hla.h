@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 29
+#define HLA_ABI_VERSION 30
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -519,6 +519,32 @@ int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_level* levels,
                          const float* R_FL, const float* T_FL, const float* pose0, const float* trace,
                          const double* normal_eq, const float* d_trace, double* d_damping, void* workspace,
                          size_t workspace_bytes, int B, hla_stream_t stream);
+
+/* Backward of hla_s2g_pose_score (no reference function; what autograd gives for the cost formula above, which is the residual
+ * of LM_update, models_kitti.py:982-996 / models_ford.py:414-430 -- the surface the reference trains by metric learning with
+ * triplet_loss, models_kitti.py:579-595, 1607-1624).  Given d(loss)/d(cost) it writes d(loss)/d(the level's maps); poses get no
+ * gradient.
+ *   cfg, level, R_FL, T_FL, poses, K   the forward's; feat_dtype must be HLA_F32 (16-bit maps are refused), cfg->keep and
+ *                                      level->depth NULL as in the forward, cfg->deterministic 0
+ *   sums   [B,K,8] fp64   the forward's output;   d_cost [B,K] fp32
+ *   grad   d_sat_feat [B,A,A,C], d_grd_feat [B,h-grd_row_skip,w,C] and, iff cfg->using_weight, d_grd_conf [B,h-grd_row_skip,w]:
+ *          fp32 NHWC, all OVERWRITTEN (the call clears what it accumulates into; the stored ground rows above row0 are zero).
+ *          Gradients are taken w.r.t. the L2-NORMALISED maps (inv_norm x stored map), hla_s2g_lm_solve_bwd's convention:
+ *          hla_vgg_backward with HLA_VGG_BWD_SCALE_INVARIANT consumes them as they are (sum map x d_map = 0 per sample)
+ * With s, g the masked normalised values, N = sums[0], G = sums[1], a = sums[3], e = sums[4], c = sums[5], ns = max(sqrt N, 1e-6),
+ * ng = max(sqrt G, 1e-6) and w as in the forward:
+ *   d cost/d s    = 2 w s/ns^2 - 2 a s/ns^4 - 2 w g/(ns ng) + 2 c s/(ns^3 ng)     (pixels in view; through lm_pixel's tap weights)
+ *   d cost/d g    = 2 w g/ng^2 - 2 e g/ng^4 - 2 w s/(ns ng) + 2 c g/(ng^3 ns)     (pixels with the ground mask)
+ *   d cost/d conf = ground mask x sum_channels (s/ns - g/ng)^2
+ * where a clamped norm is a constant (its second and fourth term are absent), and without weights the first two terms, which
+ * cancel identically, are not formed.  The per-(sample, hypothesis) scalars are formed in fp64 from `sums` and rounded once.
+ * d_grd_feat and d_grd_conf are summed over k in ascending order in registers and stored once: the same bits from run to run and
+ * whatever B is.  d_sat_feat is summed with fp32 atomics: NOT bitwise reproducible.  A hypothesis with d_cost == 0 or
+ * sums[6] == 0 costs no map traffic.  hla_s2g_pose_score_bwd_workspace_bytes returns 0 and sets the last error on bad arguments. */
+size_t hla_s2g_pose_score_bwd_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K);
+int hla_s2g_pose_score_bwd(const hla_s2g_config* cfg, const hla_s2g_level* level, const hla_s2g_level_grad* grad,
+                           const float* R_FL, const float* T_FL, const float* poses, int K, const double* sums,
+                           const float* d_cost, void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
 
 /* Backward of hla_g2s_lm_solve (autograd through the same reference lines).  grads[l]: d_sat_feat [B,A,A,C] and
  * d_grd_feat [B,h,w,C] are ACCUMULATED into (zero them first), likewise d_grd_conf [B,h,w] iff using_weight;
