@@ -9,6 +9,11 @@ arguments, so that a test can put a ground pixel exactly where it wants it on th
 either side of it, on a texel, in a clamped far-corner cell.  Sampling (``O.grid_sample``) and the update (``O.lm_update``) are the
 oracle's own, unchanged.  Everything runs in the dtype of its inputs (the fp32 table is upcast, as in the kernels): the same code
 on ``torch.float32`` inputs is the "ref32" that sizes the gates.
+
+Two kinds of table: ``border_table`` (every border class, then random targets: next to every pixel in a texel cell of its own) and
+``coherent_table`` (targets linear along each row: runs of pixels in one cell, which lm_bwd_accum and psb_accum merge in registers
+before their atomics), with ``run_stats``, the CPU mirror of that merge, for ``tests/test_cell_runs_cpu.py`` /
+``tests/test_cell_runs_vs_fp64.py``.
 """
 from types import SimpleNamespace
 
@@ -159,6 +164,24 @@ SHAPES = {                     # h, w, row0, grd_row_skip
     'many': (129, 257, 0, 0),        # 33153 px: forward 65 tiles (the last one 385 px), backward 130
     'octet': (7, 37, 0, 0),          # run with B = 8 and 9: the XCD-affine block map, B = 9 with seven idle blocks per tile
 }
+# How the two backward kernels that merge texel-cell runs deal a level's pixels to their lane groups (``run_stats`` mirrors it; the
+# kernels' own statements are lm_pick_tile_bwd in csrc/lm_backward.hip and psb_tile / PSB_NPL in csrc/pose_score.hip).  A block
+# has 4 waves, a pixel takes C / 4 lanes, so a block has 4 * (256 / C) lane groups; each walks RUN consecutive pixels of the tile.
+def lm_bwd_tile(npix):
+    return 256 if npix >= 4096 else 128         # lm_pick_tile_bwd
+
+
+PSB_RUN = 8                                      # PSB_NPL
+
+
+def lane_groups(C):
+    return 4 * (256 // C)
+
+
+def psb_tile(C):
+    return lane_groups(C) * PSB_RUN              # psb_tile
+
+
 # (ford, shape, C, A, B) of every pose-0 case tests/test_lm_kernels_vs_fp64.py runs, forward or backward
 BORDER_CASES = [(0, 'ragged', C, 16, 3) for C in (16, 64, 128, 256)] + [
     (1, 'ragged', 64, 16, 3), (0, 'ragged', 64, 13, 3), (1, 'ragged', 64, 13, 3), (0, 'sub_tile', 256, 16, 1), (0, 'skip', 128, 16, 2),
@@ -223,12 +246,205 @@ def border_table(ford, A, h, w, row0, seed, mpp=0.5):
     return torch.from_numpy(table_from_targets(ford, tu, tv, mpp, centre)), tu, tv, ku, kv
 
 
-def make_level(ford, shape, C, A, B, seed, mpp=0.5, dtype=torch.float32):
+# ----------------------------------------------------------------------------------------------------------------------
+# coherent tables: neighbouring ground pixels fall into the same texel cell, as at real geometry (the border table's random fill
+# gives every pixel a cell of its own, so the backward kernels' merge of a cell run in registers is next to never taken there)
+# ----------------------------------------------------------------------------------------------------------------------
+# Step of the swept coordinate per pixel, by row: the cycle 1/16, 3/32, 1/8, 3/16, 5/16, 1/2, 1, 0 in an order that brings both
+# extremes (one pixel per cell, a whole row in one cell) into the first seven rows, the height of the smallest shapes.
+COHERENT_STEPS = (1 / 16, 3 / 32, 1 / 8, 0.0, 5 / 16, 1.0, 1 / 2, 3 / 16)
+COHERENT_DRIFT = 1 / 64                # of the other coordinate, per pixel
+HOLE_PERIOD = 12                       # one pixel in twelve of every row is a hole
+OUTSIDE = 3.0                          # no target lies further than this from the map: OUT_OF_VIEW_POSE clears these tables too
+
+
+def coherent_table(ford, A, h, w, row0, seed, mpp=0.5):
+    """-> the tuple of ``border_table`` (class indices all -1).  Pose-0 targets vary linearly along every row, on the 2^-10 grid.
+    Row k counted from row0 (wrapping): k even sweeps v, k odd sweeps u, by COHERENT_STEPS[j % 8] per pixel (j = k, less one after
+    the copied row) while the other coordinate drifts by 1/64 per pixel.
+      k = 0   u == A - 1 exactly, v sweeping: a run in a clamped cell with dxo == 0
+      k = 1   v == A - 1 exactly, u sweeping: dyo == 0 (Ford: z <= 0 on that line at these constants, the row is masked)
+      k = 3   row 2 again, moved by 1/32 in both coordinates: two rows that share their cells
+      step 0  a whole row in as few cells as the drift allows (one cell for w <= 48)
+    The other rows start and run as drawn from ``seed``: inside the visible part of the map (KITTI: u > centre, Ford: v < centre
+    + 4), entering it from outside the map, or leaving it; a row that has left stays OUTSIDE px from the border.
+    Holes: column c of row k with (c + 5 k) % 12 == 7 is moved out of the map (by OUTSIDE) or, every second one, onto a masked
+    target inside the map (z <= 0)."""
+    centre = centre_of(ford, A)
+    lim = A - 1.0
+    q = lambda x: np.round(np.asarray(x, np.float64) * 1024) / 1024
+    zero_v = centre - FORD_T[0] / mpp      # Ford: z > 0 is v < zero_v (centre + 4 at mpp = 0.5)
+    vis = {'u': (0.0, lim) if ford else (centre + 0.25, lim), 'v': (0.0, min(lim, zero_v - 0.25)) if ford else (0.0, lim)}
+    # the map border a row can enter or leave through with z > 0 on both sides of it
+    open_side = {'u': (-1, +1) if ford else (+1,), 'v': (-1,) if ford else (-1, +1)}
+    rs = np.random.RandomState(seed)
+    cols = np.arange(w)
+    tu, tv = np.empty((h, w)), np.empty((h, w))
+    for k in range(h):
+        r = (row0 + k) % h
+        j = k if k < 3 else k - 1
+        step = COHERENT_STEPS[j % 8]
+        sw, ot = ('v', 'u') if k % 2 == 0 else ('u', 'v')
+        span, dspan = step * (w - 1), COHERENT_DRIFT * (w - 1)
+        (lo, hi), (olo, ohi) = vis[sw], vis[ot]
+        mode, sign, side, f0, f1 = rs.randint(3), rs.choice((-1, 1)), rs.randint(2), rs.uniform(), rs.uniform()   # (drawn for every row)
+        if k == 3:
+            tu[r], tv[r] = tu[(row0 + 2) % h] + 1 / 32, tv[(row0 + 2) % h] + 1 / 32
+            continue
+        side = open_side[sw][side % len(open_side[sw])]
+        n_out = min(5, w // 4) + 0.5
+        if step == 0 or (k < 3 and span <= hi - lo) or (mode == 0 and span <= hi - lo):      # inside
+            s0 = lo + f0 * (hi - lo - span)
+            s0, d = (s0, step) if sign > 0 else (s0 + span, -step)
+        elif mode == 1 or k < 3:                                                           # enters through `side`
+            s0 = (lim + n_out * step) if side > 0 else -n_out * step
+            d = -side * step
+        else:                                                                              # leaves through `side`
+            s0 = ((lim + n_out * step) if side > 0 else -n_out * step) - side * span
+            d = side * step
+        if step == 0 and dspan < 0.75:          # the drift stays inside one cell
+            o0 = np.ceil(olo) + np.floor(f1 * (np.floor(ohi) - np.ceil(olo))) + 0.125
+        else:
+            o0 = olo + f1 * max(ohi - olo - dspan, 0.0)
+        s, o = q(s0) + d * cols, q(o0) + COHERENT_DRIFT * cols
+        if k == 0:
+            o = np.full(w, lim)                 # sw = 'v': u == A - 1
+        if k == 1:
+            o = np.full(w, lim)                 # sw = 'u': v == A - 1
+        tu[r], tv[r] = (o, s) if sw == 'v' else (s, o)
+    tu, tv = np.clip(tu, -OUTSIDE, lim + OUTSIDE), np.clip(tv, -OUTSIDE, lim + OUTSIDE)
+    for k in range(h):
+        r = (row0 + k) % h
+        for n, c in enumerate(cols[(cols + 5 * k) % HOLE_PERIOD == 7]):
+            if (n + k) % 2 == 0:                # out of the map, z > 0
+                if ford:
+                    tv[r, c] = -OUTSIDE
+                else:
+                    tu[r, c] = lim + OUTSIDE
+            elif ford:                          # inside the map, z <= 0
+                tv[r, c] = zero_v + 0.5
+            else:
+                tu[r, c] = centre - 1.5
+    tu, tv = q(tu), q(tv)
+    none = -np.ones((h, w), int)
+    return torch.from_numpy(table_from_targets(ford, tu, tv, mpp, centre)), tu, tv, none, none.copy()
+
+
+def pixel_cells(lv, pose, keep=None):
+    """What lm_pixel (csrc/lm_common.h) makes of the pixels the loop reads, for ONE sample at ``pose`` = (su, sv, th) floats, in
+    fp64: live [npix] bool (ground mask, in view, kept) and cell [npix,4] int = (x0, y0, dx, dy), dx / dy = 0 in a clamped cell."""
+    one = lambda x: torch.tensor([[float(x)]], dtype=torch.float64)
+    uv, _, mask = level_uv(cast_geom(make_geom(lv.ford, 1), torch.float64), lv, tuple(one(x) for x in pose))
+    u, v = [uv[0, lv.row0:, :, i].reshape(-1).numpy() for i in range(2)]
+    lim = lv.A - 1
+    live = (u >= 0) & (u <= lim) & (v >= 0) & (v <= lim) & (mask[0, lv.row0:].reshape(-1).numpy() > 0)
+    if keep is not None:
+        live &= np.asarray(keep).reshape(-1)[:len(live)].astype(bool)
+    x0, y0 = np.floor(u), np.floor(v)
+    cell = np.stack([x0, y0, np.minimum(x0 + 1, lim) - x0, np.minimum(y0 + 1, lim) - y0], 1).astype(int)
+    return live, cell
+
+
+def run_stats(lv, pose, C, kind, keep=None):
+    """The CPU mirror of how ``kind`` = 'lm_bwd' (lm_bwd_accum) or 'psb' (psb_accum) merges texel-cell runs, for one sample at
+    ``pose``: a lane group walks RUN consecutive pixels of its tile; a live pixel in another cell than the open one flushes it; a
+    pixel that is not live (a hole) leaves it open.  -> dict:
+      live         pixels that reach the satellite map          merged      those in runs of 2 or more
+      longest      the longest run                               run         RUN of the (full) tile
+      across_hole  runs that go on in the same cell after a hole             open_hole   holes met with a cell open
+      clamped      runs of 2 or more in a cell with dxo == 0 or dyo == 0     tiles       tiles of the level
+      multi_group / multi_tile   texels flushed to by at least 2 lane groups / by lane groups of at least 2 tiles
+      merged_pixels              the indices (from row0 on) of the merged pixels"""
+    live, cell = pixel_cells(lv, pose, keep)
+    tp = lm_bwd_tile(len(live)) if kind == 'lm_bwd' else psb_tile(C)
+    return group_stats(live, cell, lane_groups(C), tp, None if kind == 'lm_bwd' else PSB_RUN)
+
+
+def group_stats(live, cell, groups, tp, fixed_run=None):
+    """``run_stats`` on given pixels: live [npix] bool, cell [npix,4] int, ``groups`` lane groups per block, tiles of ``tp`` pixels,
+    RUN = ``fixed_run`` or, if None, ceil(pixels of the tile / groups)."""
+    npix = len(live)
+    nt = (npix + tp - 1) // tp
+    out = dict(live=int(live.sum()), merged=0, longest=0, across_hole=0, open_hole=0, clamped=0, tiles=nt,
+               run=fixed_run or (min(tp, npix) + groups - 1) // groups, merged_pixels=[])
+    writers = {}
+
+    def flush(c, n, who, pix):
+        if c is None:
+            return
+        out['merged'] += n if n >= 2 else 0
+        out['merged_pixels'] += pix if n >= 2 else []
+        out['longest'] = max(out['longest'], n)
+        out['clamped'] += int(n >= 2 and (c[2] == 0 or c[3] == 0))
+        for t in {(c[1], c[0]), (c[1], c[0] + c[2]), (c[1] + c[3], c[0]), (c[1] + c[3], c[0] + c[2])}:
+            writers.setdefault(t, set()).add(who)
+
+    for tile in range(nt):
+        p0 = tile * tp
+        n_p = min(tp, npix - p0)
+        run = fixed_run or (n_p + groups - 1) // groups
+        for g in range(groups):
+            cur, n, hole, counted, pix = None, 0, False, False, []
+            for i in range(g * run, min((g + 1) * run, n_p)):
+                p = p0 + i
+                if not live[p]:
+                    out['open_hole'] += int(cur is not None)
+                    hole = cur is not None
+                    continue
+                c = tuple(cell[p])
+                if c != cur:
+                    flush(cur, n, (tile, g), pix)
+                    cur, n, counted, pix = c, 0, False, []
+                elif hole and not counted:
+                    out['across_hole'] += 1
+                    counted = True
+                n, hole = n + 1, False
+                pix.append(p)
+            flush(cur, n, (tile, g), pix)
+    out['multi_group'] = sum(len(s) >= 2 for s in writers.values())
+    out['multi_tile'] = sum(len({t for t, _ in s}) >= 2 for s in writers.values())
+    return out
+
+
+# (ford, shape, C, A, B) of the one-level coherent cases of tests/test_cell_runs_vs_fp64.py, each run at pose 0 and COHERENT_POSE
+COHERENT_CASES = [(0, 'ragged', C, 16, 3) for C in (16, 64, 128, 256)] + [
+    (1, 'ragged', 64, 16, 3), (0, 'ragged', 64, 13, 3), (1, 'ragged', 64, 13, 3), (0, 'mid', 64, 16, 2), (0, 'skip', 128, 16, 2),
+    (0, 'octet', 64, 16, 9)]
+COHERENT_POSE = (0.05, -0.03, 0.4)
+# (ford, level_first, dropout keep masks, using_weight) of the two-level coherent cases
+COHERENT_TWO_LEVEL_CASES = [(f, lf, kp, (f + lf + kp) % 2) for f in (0, 1) for lf in (0, 1) for kp in (0, 1)]
+# Seeds.  tests/test_cell_runs_cpu.py states what a case's inputs must reach at every pose it is run at (a full lane group of 8
+# live pixels in one cell, a run across a hole, ...) and holds the references' own fp32 runs inside the gates; on a level of seven
+# rows of 37 pixels, two or three in a hundred (pose, condition) pairs miss by chance.  The salts are the FIRST ones, counted
+# from 0, under which every condition of that file holds: found on the CPU, on the inputs and the references alone.
+COHERENT_SALT = {}                     # (ford, shape, C, A, B) -> salt (0 where not listed: every table is its first one)
+COHERENT_TWO_LEVEL_SALT = {(1, 0): 1}  # (ford, level_first) -> salt
+_COHERENT = {}
+
+
+def coherent_level(ford, shape, C, A, B, dtype=torch.float32):
+    """(geom, level) of a coherent case, made once per process and never modified."""
+    key = (ford, shape, C, A, B, dtype)
+    if key not in _COHERENT:
+        _COHERENT[key] = (make_geom(ford, B), make_level(ford, shape, C, A, B, case_seed('coherent', ford, shape, C, A, B,
+                                                                                            COHERENT_SALT.get(key[:5], 0)),
+                                                         dtype=dtype, table='coherent'))
+    return _COHERENT[key]
+
+
+def coherent_two_level_case(ford, level_first):
+    """``make_two_level_case`` on coherent tables; the dropout masks drop one pixel in six (holes inside open cells)."""
+    salt = COHERENT_TWO_LEVEL_SALT.get((ford, level_first), 0)
+    return make_two_level_case(ford, case_seed('coherent2', ford, level_first, salt), table='coherent', keep_p=5 / 6)
+
+
+def make_level(ford, shape, C, A, B, seed, mpp=0.5, dtype=torch.float32, table='border'):
     """One level of a case (``shape``: a name in SHAPES or (h, w, row0, skip)): border table + unit-norm-ish random maps.  ``dtype`` bf16 / fp16: the maps are rounded to it here (on
-    the host) and the reference reads the rounded values."""
+    the host) and the reference reads the rounded values.  table = 'coherent': ``coherent_table`` instead of ``border_table``
+    (the maps are the same bytes either way)."""
     h, w, row0, skip = SHAPES[shape] if isinstance(shape, str) else shape
     rs = np.random.RandomState(seed + 1000)
-    table, tu, tv, ku, kv = border_table(ford, A, h, w, row0, seed, mpp)
+    table, tu, tv, ku, kv = {'border': border_table, 'coherent': coherent_table}[table](ford, A, h, w, row0, seed, mpp)
     npix = (h - row0) * w
     sat = torch.from_numpy((rs.standard_normal((B, C, A, A)) / np.sqrt(C * A * A)).astype(np.float32)).to(dtype)
     grd = torch.from_numpy((rs.standard_normal((B, C, h, w)) / np.sqrt(C * npix)).astype(np.float32)).to(dtype)
@@ -236,7 +452,7 @@ def make_level(ford, shape, C, A, B, seed, mpp=0.5, dtype=torch.float32):
     grd[:, :, :skip] = 0      # rows the caller does not store
     conf[:, :, :skip] = 0
     return SimpleNamespace(shape=shape, h=h, w=w, row0=row0, skip=skip, C=C, A=A, mpp=mpp, centre=centre_of(ford, A), table=table,
-                           sat=sat, grd=grd, conf=conf, dtype=dtype, tu=tu, tv=tv, ku=ku, kv=kv)
+                           sat=sat, grd=grd, conf=conf, dtype=dtype, tu=tu, tv=tv, ku=ku, kv=kv, ford=int(ford))
 
 
 def make_geom(ford, B):
@@ -287,17 +503,17 @@ TWO_LEVELS = (('ragged', 128, 16, 0.5), ('mid', 16, 13, 0.75))
 OUT_OF_VIEW_POSE = (2.4, 0.125, -0.25)       # shift_u = 2.4 x 6 m = 19 px or more: every pixel leaves the map
 
 
-def make_two_level_case(ford, seed, B=3, out_sample=1):
+def make_two_level_case(ford, seed, B=3, out_sample=1, table='border', keep_p=0.5):
     """-> (geom, levels, pose0 [B,3] fp32, rand_uv [steps,2,B] fp32, keep [steps, max npix] uint8) for 2 levels x 2 iterations.
-    Sample ``out_sample`` starts out of view (None: no such sample)."""
-    levels = [make_level(ford, s, C, A, B, seed + 10 * l, mpp) for l, (s, C, A, mpp) in enumerate(TWO_LEVELS)]
+    Sample ``out_sample`` starts out of view (None: no such sample); keep_p: the share of pixels a dropout mask keeps."""
+    levels = [make_level(ford, s, C, A, B, seed + 10 * l, mpp, table=table) for l, (s, C, A, mpp) in enumerate(TWO_LEVELS)]
     rs = np.random.RandomState(seed + 77)
     p0 = rs.uniform(-0.3, 0.3, size=(B, 3)).astype(np.float32)
     if out_sample is not None:
         p0[out_sample] = OUT_OF_VIEW_POSE
     rand_uv = rs.uniform(-1, 1, size=(4, 2, B)).astype(np.float32)
     npix = [(lv.h - lv.row0) * lv.w for lv in levels]
-    keep = (rs.uniform(size=(4, max(npix))) < 0.5).astype(np.uint8)
+    keep = (rs.uniform(size=(4, max(npix))) < keep_p).astype(np.uint8)
     return make_geom(ford, B), levels, torch.from_numpy(p0), torch.from_numpy(rand_uv), torch.from_numpy(keep)
 
 

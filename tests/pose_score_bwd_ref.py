@@ -105,13 +105,30 @@ CASES = [(0, 'ragged', C, 16, 3, w, PS.K_CASE, PS.OUT_K, False) for C in (16, 64
         [(0, 'ragged', 128, 16, 3, w, PS.K_CASE, PS.OUT_K, True) for w in (0, 1)]
 
 
+# The same tuples with a tenth field 'coherent': on the coherent table of lm_kernel_ref (cell runs that psb_accum merges before its
+# atomics), every run of tests/test_cell_runs_vs_fp64.py.  The out-of-view hypothesis clears these tables too
+# (tests/test_cell_runs_cpu.py).
+RUN_CASES = [(0, 'ragged', C, 16, 3, w, PS.K_CASE, PS.OUT_K, False, 'coherent') for C in (16, 64, 128, 256) for w in (0, 1)] + \
+            [(0, 'mid', 64, 16, 2, 1, 33, None, False, 'coherent'), (1, 'mid', 16, 13, 2, 1, PS.K_CASE, PS.OUT_K, False, 'coherent')]
+
+
+# case -> salt of its hypotheses' seed (0 where not listed): see lm_kernel_ref.COHERENT_SALT
+RUN_POSE_SALT = {RUN_CASES[1]: 1, RUN_CASES[4]: 8, RUN_CASES[5]: 9}
+
+
 def case_inputs(case):
     """-> (geom, lv32 as the kernel reads it (raw maps when deferred), inv_norm or None, lv64 the reference reads (normalised maps),
     poses [B,K,3] fp32, d_cost [B,K] fp32)."""
-    ford, shape, Cn, A, B, w, K, out_k, deferred = case
+    ford, shape, Cn, A, B, w, K, out_k, deferred = case[:9]
     geom = R.make_geom(ford, B)
-    lv = R.make_level(ford, shape, Cn, A, B, R.case_seed(ford, shape, Cn, A, B))
-    poses = PS.hypotheses(B, K, R.case_seed('psb', ford, shape, Cn, A, B, w, K), out_of_view=out_k)
+    if len(case) > 9:
+        assert case[9] == 'coherent'
+        lv = R.coherent_level(ford, shape, Cn, A, B)[1]
+    else:
+        lv = R.make_level(ford, shape, Cn, A, B, R.case_seed(ford, shape, Cn, A, B))
+    # (coherent: poses within 1.2 px and 1 degree of the zero pose, so that every hypothesis keeps the table's cell runs)
+    salt = (RUN_POSE_SALT.get(case, 0),) if len(case) > 9 else ()
+    poses = PS.hypotheses(B, K, R.case_seed('psb', ford, shape, Cn, A, B, w, K, *salt), out_of_view=out_k, lim=0.1 if len(case) > 9 else 0.3)
     dc = d_costs(B, K, R.case_seed('psb-dc', ford, shape, Cn, A, B, w, K), keep=() if out_k is None else (out_k,))
     ref_lv, run_lv, inv = R.cast_level(lv, torch.float64), lv, None
     if deferred:

@@ -196,8 +196,9 @@ def _zero_pose(B):
 # ----------------------------------------------------------------------------------------------------------------------
 # forward at pose 0: the border classes
 # ----------------------------------------------------------------------------------------------------------------------
-def _forward_pose0(ford, shape, Cn, A, B, dtype, using_weight, inv_norm=None):
-    geom, lv = _border_level(ford, shape, Cn, A, B, dtype)
+def _forward_pose0(ford, shape, Cn, A, B, dtype, using_weight, inv_norm=None, level=None):
+    """level: (geom, lv) to run on (None: the border level of the case)."""
+    geom, lv = level if level is not None else _border_level(ford, shape, Cn, A, B, dtype)
     ref_lv = R.cast_level(lv, F64)
     run_lv = lv
     if inv_norm is not None:        # deferred norms: the kernel reads raw maps and rescales its sums; the reference reads raw * inv
@@ -319,19 +320,20 @@ def test_forward_random_poses_two_levels_teacher_forced(ford, level_first, use_k
 # ----------------------------------------------------------------------------------------------------------------------
 # backward
 # ----------------------------------------------------------------------------------------------------------------------
-def _reference_grads(geom, levels, p0, rand_uv, N, level_first, using_weight, coef, keep=None, use_keep=False):
-    """fp64 autograd through the reference's steps from pose0, loss = sum(coef * trace).  -> leaves (with .grad), dparam."""
-    g = R.cast_geom(geom, F64)
-    lvs = [R.cast_level(lv, F64, requires_grad=True) for lv in levels]
-    dparam = torch.tensor(DPARAM, dtype=F64, requires_grad=True)
+def _reference_grads(geom, levels, p0, rand_uv, N, level_first, using_weight, coef, keep=None, use_keep=False, dt=F64):
+    """fp64 autograd through the reference's steps from pose0, loss = sum(coef * trace).  -> leaves (with .grad), dparam.
+    dt = torch.float32: the reference's own fp32 run (tests/test_cell_runs_cpu.py)."""
+    g = R.cast_geom(geom, dt)
+    lvs = [R.cast_level(lv, dt, requires_grad=True) for lv in levels]
+    dparam = torch.tensor(DPARAM, dtype=dt, requires_grad=True)
     args = R.update_args(train_damping=1)
-    pose = R.pose_cols(p0, F64)
+    pose = R.pose_cols(p0, dt)
     loss = 0
     for k, (i, l) in enumerate(R.step_order(len(levels), N, level_first)):
         lv = lvs[l]
         kp = keep[k, :(lv.h - lv.row0) * lv.w].bool() if use_keep else None
-        pose = R.level_step(args, g, lv, pose, using_weight, tuple(rand_uv[k, j][:, None].double() for j in range(2)), dparam, kp)
-        loss = loss + (coef[:, i, l].double() * torch.cat(pose, 1)).sum()
+        pose = R.level_step(args, g, lv, pose, using_weight, tuple(rand_uv[k, j][:, None].to(dt) for j in range(2)), dparam, kp)
+        loss = loss + (coef[:, i, l].to(dt) * torch.cat(pose, 1)).sum()
     loss.backward()
     return lvs, dparam
 
@@ -351,14 +353,19 @@ def _gate_all_grads(tag, levels, lvs, dparam, using_weight, d_sat, d_grd, d_conf
     _gate_grad(f'{tag} d_damping', got, dparam.grad)
 
 
-def _backward_pose0(ford, shape, Cn, A, B, using_weight, deterministic=0):
-    geom, lv = _border_level(ford, shape, Cn, A, B)
+def _backward_pose0(ford, shape, Cn, A, B, using_weight, deterministic=0, pose=None, level=None):
+    """One level, one step, backward against fp64 autograd.  pose: the start pose of every sample (None: pose 0); level: (geom, lv)
+    to run on (None: the border level of the case)."""
+    geom, lv = level if level is not None else _border_level(ford, shape, Cn, A, B)
     p0, ruv = _zero_pose(B)
+    if pose is not None:
+        p0 = torch.tensor([pose], dtype=F32).repeat(B, 1)
     call = _Call(geom, [lv], using_weight=using_weight, damping=_lambda())
     call.forward(p0, ruv)
     coef = torch.from_numpy(np.random.RandomState(R.case_seed('coef', shape, Cn, B)).standard_normal((B, 1, 1, 3)))
     lvs, dparam = _reference_grads(geom, [lv], p0, ruv, 1, 0, using_weight, coef)
-    tag = f"bwd pose0 {'ford' if ford else 'kitti'} {shape} C{Cn} A{A} B{B} w{using_weight}" + (' det' if deterministic else '')
+    tag = f"bwd pose{0 if pose is None else pose} {'ford' if ford else 'kitti'} {shape} C{Cn} A{A} B{B} w{using_weight}" + \
+          (' det' if deterministic else '') + (' given level' if level is not None else '')
     out = call.backward(coef, overwrite=1, deterministic=deterministic)
     _gate_all_grads(tag, [lv], lvs, dparam, using_weight, *out)
     return call, coef, out
