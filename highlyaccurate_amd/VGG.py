@@ -190,12 +190,13 @@ def promised_cols(first_col32: int):
     return (16 * c + 2, 32 * c + 6, 64 * c + 14) if c > 0 else (0, 0, 0)
 
 
-@_lib.on_device(lambda state, gate: gate)
-def vgg_fixup_nhwc(state: dict, gate: torch.Tensor) -> None:
+@_lib.on_device(lambda state, gate, *a, **k: gate)
+def vgg_fixup_nhwc(state: dict, gate: torch.Tensor, one_launch: bool = True) -> None:
     """The fix-up pass of a forward made with ``first_col32`` > 0 (``state``: its ``col_state``): for every sample b with
     ``gate[b] != 0`` (int32 [B] on the device) the columns that forward skipped or left wrong are computed, and inv_norm again --
     in place, on the current stream, without a host synchronisation.  Such a sample's maps and inv_norm are then bit for bit the
-    full forward's; the others are not touched."""
+    full forward's; the others are not touched.  ``one_launch`` ('bf16' / 'fp16'): the pass is one launch with a workgroup per
+    sample (``hla_vgg_fixup``, include/hla.h) instead of ten gated conv launches and a gated inv_norm; the same bits."""
     s = state
     if not s or not s['first_col32']:
         return
@@ -203,11 +204,11 @@ def vgg_fixup_nhwc(state: dict, gate: torch.Tensor) -> None:
         raise ValueError('gate must be a contiguous int32 [B] tensor on the device of the maps')
     L = s['L']
     fp = (C.c_void_p * 4)(*([f.data_ptr() for f in s['feats']] + [0] * (4 - L)))
-    cp = (C.c_void_p * 4)(0, 0, 0, 0)
-    rc = _lib.load().hla_vgg_forward_cols(_lib.ptr(s['x']), s['x_plane'], C.byref(s['prm']), _lib.ptr(s['packed']), fp, cp,
-                                     _lib.ptr(s['inv_norm']), _lib.ptr(s['ws']), s['ws'].numel(), s['B'], s['H'], s['W'], L, s['dt'],
-                                     s['flags'], s['first_row8'], s['first_col32'], _lib.ptr(gate), _lib.stream_ptr())
-    _lib.check(rc, 'hla_vgg_forward_cols (fix-up pass)')
+    rc = _lib.load().hla_vgg_fixup(_lib.ptr(s['x']), s['x_plane'], C.byref(s['prm']), _lib.ptr(s['packed']), fp,
+                                   _lib.ptr(s['inv_norm']), _lib.ptr(s['ws']), s['ws'].numel(), s['B'], s['H'], s['W'], L, s['dt'],
+                                   s['flags'], s['first_row8'], s['first_col32'], _lib.ptr(gate), 1 if one_launch else 0,
+                                   _lib.stream_ptr())
+    _lib.check(rc, 'hla_vgg_fixup')
 
 
 @_lib.on_device(lambda modules, xs, *a, **k: xs[0])

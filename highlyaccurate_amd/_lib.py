@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 class HlaError(RuntimeError):
@@ -143,6 +143,8 @@ def load() -> C.CDLL:
     lib.hla_vgg_forward_cols.restype = i
     lib.hla_vgg_forward_cols.argtypes = [vp, sz, C.POINTER(VggParams), vp, C.POINTER(vp), C.POINTER(vp), vp, vp, sz,
                                          i, i, i, i, i, i, i, i, vp, vp]
+    lib.hla_vgg_fixup.restype = i
+    lib.hla_vgg_fixup.argtypes = [vp, sz, C.POINTER(VggParams), vp, C.POINTER(vp), vp, vp, sz, i, i, i, i, i, i, i, i, vp, i, vp]
     lib.hla_vgg_forward_pair.restype = i
     lib.hla_vgg_forward_pair.argtypes = [C.POINTER(VggBranch), i, i, i, i, C.POINTER(i), vp]
     lib.hla_vgg_packed_weight_bytes.restype = sz

@@ -218,6 +218,8 @@ class S2GPBase(nn.Module):
     #                      left columns of the satellite maps that no pose inside the configured shift / rotation range reads;
     #                      a sample whose loop leaves that reach is detected on the device and recomputed exactly, without a
     #                      host synchronisation.  0: whole maps                                                  DESIGN.md 3.5
+    #   fixup_one_launch   1: that recomputation's extractor half is one launch with a workgroup per sample (bf16 / fp16); 0: ten
+    #                      gated conv launches and a gated inv_norm.  Same bits (A/B and tests)                   DESIGN.md 3.5
     #   train_ground_crop  0; 1: the same for training (changes the returned confidence maps above the crop)   DESIGN.md 3.5
     #   bwd_trim           1: the backward skips rows / tiles whose gradient is exactly zero; 0: dense walk     DESIGN.md 6
     #   bwd_two_streams    1: the two extractors' backward passes run on two streams (single-GPU training)       DESIGN.md 6
@@ -837,7 +839,7 @@ class S2GPBase(nn.Module):
             c32 = self.sat_first_col32(sat_map.shape[-1], grd_img.shape[-2], grd_img.shape[-1])
         state = {} if c32 else None
         sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, want_conf, return_confs, c32, state)
-        reach = (promised_cols(c32), lambda flag: vgg_fixup_nhwc(state, flag)) if c32 else None
+        reach = (promised_cols(c32), lambda flag: vgg_fixup_nhwc(state, flag, bool(getattr(a, 'fixup_one_launch', 1)))) if c32 else None
         trace = self.lm_solve(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], extra, level_first, init_pose,
                               sat_inv, grd_inv, gt_depth=gt_depth, reach=reach)
         if self.keep_features:

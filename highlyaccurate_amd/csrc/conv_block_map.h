@@ -16,6 +16,13 @@ HLA_MAP_FN int xcd_contiguous(int bid, int nb) {
   const int q = nb >> 3, r = nb & 7, xcd = bid & 7;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
+// The inverse: the workgroup id that xcd_contiguous maps to position v (vgg_fixup_loop walks one sample's positions in order and
+// hands each body the id the launch over the whole batch would have given it; tests/test_conv_block_map_inverse_cpu.py).
+HLA_MAP_FN int xcd_contiguous_inv(int v, int nb) {
+  const int q = nb >> 3, r = nb & 7, split = r * (q + 1);      // (v >= split implies q > 0: with q == 0, split == nb)
+  const int xcd = v < split ? v / (q + 1) : r + (v - split) / q;
+  return ((v < split ? v - xcd * (q + 1) : v - split - (xcd - r) * q) << 3) + xcd;
+}
 
 // A launch with `gy` output-channel blocks per tile is a 1-D grid of nwg = tiles * gy workgroups, the channel block innermost in
 // the XCD-contiguous order: the workgroups an XCD receives one after the other (bid, bid + 8, ...) are the gy blocks of one tile,

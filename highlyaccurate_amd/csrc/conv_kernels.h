@@ -1028,7 +1028,16 @@ __device__ __forceinline__ void stage_mma(typename AccMap<SHAPE>::Tile (&acc)[MT
 // arguments: a plain launch passes blockIdx.x / gridDim.x (conv3x3_kernel), a two-segment launch the ids local to the workgroup's
 // segment (conv3x3_pair_kernel below).  They are all the kernel knows of its place in the grid: the XCD-contiguous map, the
 // (b, ty, tx, channel block) decode and the sum-of-squares slot use them.
-template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16>
+// XLDS: the halo buffers are the launch's dynamic LDS instead of an array of the body's own: a kernel that runs several
+// instantiations one after the other (vgg_fixup_loop) gives them all the same bytes, conv3x3_lds_bytes of the largest.
+template <typename T, int MT, int NT, int WM, bool UNPOOL = false>
+constexpr int conv3x3_lds_bytes() {      // LDS bytes of conv3x3_body<T, MT, NT, WM, ...> (its LDSB)
+  constexpr int HP = (WM * MT + 2) * HWID, NP = (HP * 4 + 255) / 256;
+  constexpr int buf = ((sizeof(T) == 2 && !UNPOOL && !Prec<T>::SPLIT) ? NP * 64 : HP) * PSTR;
+  constexpr int stg = 32 * (RowStager<float, NT>::PITCH + (sizeof(T) == 2 ? RowStager<T, NT>::PITCH : 0));
+  return 2 * buf > 4 * stg ? 2 * buf : 4 * stg;
+}
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16, bool XLDS = false>
 __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, const int nblk) {
   static_assert(WM * WN == 4, "4 waves per block");
   static_assert(SHAPE == SHAPE_32x32x16 || (sizeof(T) == 2 && !UNPOOL), "16x16x32: bf16 / f16 forward kernels only");
@@ -1048,7 +1057,10 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   // activation row side by side (EPI_ACT_RAW on 16-bit types), everything else one row of at most NT*32 fp32
   constexpr int STG = 32 * (RowStager<float, NT>::PITCH + (sizeof(T) == 2 ? RowStager<T, NT>::PITCH : 0));
   constexpr int LDSB = 2 * BUF > 4 * STG ? 2 * BUF : 4 * STG;
-  __shared__ __attribute__((aligned(16))) char lds[LDSB];
+  static_assert(LDSB == conv3x3_lds_bytes<T, MT, NT, WM, UNPOOL>(), "conv3x3_lds_bytes is what a launch with XLDS allocates");
+  __shared__ __attribute__((aligned(16))) char lds_own[XLDS ? 16 : LDSB];
+  extern __shared__ __attribute__((aligned(16))) char lds_dyn[];
+  char* const lds = XLDS ? lds_dyn : lds_own;
   __shared__ float red[8];
 
   HLA_STAMP(0);
@@ -1372,17 +1384,23 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs 
 // from ONE selected kernarg address: selecting between the two blocks of a by-value struct field by field keeps both live, and
 // indexing the struct dynamically makes the compiler copy it to the stack.
 template <typename A> struct PairArgs { A s[2]; int n0; };
+// (kernarg_block: the argument block `word_off` 32-bit words into the kernarg segment; the offset is workgroup-uniform)
 template <typename A>
-__device__ __forceinline__ A pair_segment_args(bool second) {
-  static_assert(sizeof(A) % 4 == 0 && offsetof(PairArgs<A>, s) == 0, "the argument blocks lead the kernarg segment");
+__device__ __forceinline__ A kernarg_block(unsigned word_off) {
+  static_assert(sizeof(A) % 4 == 0, "argument blocks are fetched as 32-bit words");
   typedef const __attribute__((address_space(4))) unsigned* kptr_t;
-  const kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr() + (second ? sizeof(A) / 4 : 0);
+  const kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr() + word_off;
   unsigned w[sizeof(A) / 4];
 #pragma unroll
   for (unsigned i = 0; i < sizeof(A) / 4; ++i) w[i] = kp[i];
   A a;
   __builtin_memcpy(&a, w, sizeof(A));
   return a;
+}
+template <typename A>
+__device__ __forceinline__ A pair_segment_args(bool second) {
+  static_assert(offsetof(PairArgs<A>, s) == 0, "the argument blocks lead the kernarg segment");
+  return kernarg_block<A>(second ? sizeof(A) / 4 : 0);
 }
 // A pointer fetched that way is a generic one to the compiler (only pointers that are kernel arguments by themselves are known to
 // be global): it would address memory with flat_load / flat_store, which count on the LDS counter as well and may not be mixed
@@ -1762,11 +1780,7 @@ template <typename T, int WD>
 __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_kernel(Conv02Args a0) {
   conv02_body<T, WD>(a0, (int)blockIdx.x);
 }
-template <typename T, int WD>
-__global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_pair_kernel(PairArgs<Conv02Args> p) {
-  const int n0 = p.n0;
-  const bool second = (int)blockIdx.x >= n0;      // workgroup-uniform
-  Conv02Args a0 = pair_segment_args<Conv02Args>(second);
+__device__ __forceinline__ void pair_inference_args(Conv02Args& a0) {      // (as for ConvArgs above)
   a0.x = pair_global(a0.x); a0.w0 = pair_global(a0.w0); a0.b0 = pair_global(a0.b0); a0.w2 = pair_global(a0.w2); a0.b2 = pair_global(a0.b2);
   a0.out_act = pair_global(a0.out_act); a0.wtail = pair_global(a0.wtail); a0.amax_out = pair_global(a0.amax_out);
   a0.a0_out = nullptr; a0.idx_out = nullptr; a0.a2_out = nullptr; a0.amax_a2_out = nullptr; a0.amax_a0_out = nullptr;      // (inference, level 3)
@@ -1774,6 +1788,13 @@ __global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_pair_kerne
 #if HLA_CONV_STAMPS
   a0.stamps = nullptr;
 #endif
+}
+template <typename T, int WD>
+__global__ __launch_bounds__(256, Prec<T>::SPLIT ? 2 : 3) void conv02_pair_kernel(PairArgs<Conv02Args> p) {
+  const int n0 = p.n0;
+  const bool second = (int)blockIdx.x >= n0;      // workgroup-uniform
+  Conv02Args a0 = pair_segment_args<Conv02Args>(second);
+  pair_inference_args(a0);
   conv02_body<T, WD>(a0, second ? (int)blockIdx.x - n0 : (int)blockIdx.x);
 }
 
@@ -2021,6 +2042,16 @@ static __global__ __launch_bounds__(256) void inv_norm_multi_kernel(InvNormArgs 
   __syncthreads();
   if (threadIdx.x == 0) a.inv[l][b] = 1.0 / fmax(sqrt((sh[0] + sh[1]) + (sh[2] + sh[3])), 1e-12);
 }
+// One row of that kernel for sample b, by the 256 threads of a workgroup that has other work as well (vgg_fixup_loop): the same
+// slots summed in the same order.  (A copy: sharing the text moved the scalar code of the kernel above.)
+__device__ __forceinline__ void inv_norm_row(const double* sumsq, int np, double* inv, int b, double* sh) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < np; i += 256) s += sumsq[(size_t)b * np + i];
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) inv[b] = 1.0 / fmax(sqrt((sh[0] + sh[1]) + (sh[2] + sh[3])), 1e-12);
+}
 // scale_kernel: in-place x *= inv[b] (fp64 multiply, one rounding)
 static __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, const double* __restrict__ inv, size_t per_sample,
                                                     int blocks_per_sample) {
@@ -2052,6 +2083,85 @@ enum { CONV_CLASS_NT2 = 0,         // Cout >= 128, plain: conv5, conv10, conv12,
 constexpr int kConvClassShape[3] = {SHAPE_16x16x32, SHAPE_16x16x32, SHAPE_32x32x16};
 constexpr int conv_class(int cout, bool pool) { return cout >= 128 ? (pool ? CONV_CLASS_NT2_POOL : CONV_CLASS_NT2) : CONV_CLASS_NT1; }
 template <typename T, bool BWD> constexpr int conv_shape(int cls) { return (sizeof(T) == 2 && !BWD) ? kConvClassShape[cls] : SHAPE_32x32x16; }
+
+// ---------------------------------------------------------------------------------------------
+// vgg_fixup_loop: the fix-up pass of a column-trimmed inference forward (vgg.hip, hla_vgg_forward_cols with col_gate) as ONE launch
+// instead of ten gated conv launches and a gated inv_norm.  Almost always no sample is flagged, and the pass then costs one launch
+// of workgroups that return at once instead of eleven of them in a dependent chain.  Workgroup b owns sample b: it walks the ten
+// layers in order and, per layer, the positions (tile, cout block) the gated launch over the whole batch gives that sample, handing
+// each body the workgroup id and count of THAT launch -- all a body knows of its place in a grid -- so a tile computes what it
+// computes there.  Every class runs its 8-row tile (a gated launch below CONV_SMALL_GRID takes the 4-row one: the same bits,
+// conv_plan).  One CU carries the sample's whole left strip: the flagged case is slow by design (EXPERIMENTS.md).
+// A layer reads what the layer before it stored from this same CU, through its L1 and through LDS-DMA loads: between two layers
+// every wave waits for its stores and releases them at agent scope, the workgroup meets, and every wave drops the CU's L1 lines
+// with an agent-scope acquire and waits for that to complete before its first load (MI355X_MICROARCH.md, "inter-workgroup
+// visibility").  Between two tiles of a layer only LDS is shared: one barrier.
+constexpr int kFixupConvs = 9;      // conv5 .. dec2.3: the 3x3 layers of level 3, in order (vgg_layers.h 2..10)
+struct VggFixupArgs {
+  ConvArgs conv[kFixupConvs];       // (leads the kernarg segment: kernarg_block) tiles_x / tiles_y as conv_plan leaves them
+  Conv02Args c02;
+  int pooled;                       // bit k: conv[k] takes the pooling kernel class
+  const double* ss[3];              // inv_norm_multi_kernel's rows of this network: partials, their count per sample, output
+  int np[3];
+  double* inv[3];
+  const int* gate;                  // [B], never null
+};
+template <typename T> constexpr int vgg_fixup_lds_bytes() {
+  constexpr int a = conv02_lds_bytes<T>(), b = conv3x3_lds_bytes<T, 4, 2, 2>(), c = conv3x3_lds_bytes<T, 4, 1, 2>();
+  return a > b ? (a > c ? a : c) : (b > c ? b : c);
+}
+__device__ __forceinline__ void fixup_layer_sync() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // this wave's stores have completed and left the L2
+  __syncthreads();                                        // ... every wave's
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // this CU's L1 lines are dropped (asynchronously: the wait below)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+template <typename T>
+__global__ __launch_bounds__(256) void vgg_fixup_loop(VggFixupArgs p) {
+  static_assert(sizeof(T) == 2 && !Prec<T>::SPLIT, "the column trim's 16-bit types");
+  static_assert(offsetof(VggFixupArgs, conv) == 0, "the conv argument blocks lead the kernarg segment");
+  const int b = blockIdx.x;
+  if (p.gate[b] == 0) return;      // workgroup-uniform, ahead of any barrier
+  {
+    Conv02Args a = p.c02;
+    pair_inference_args(a);
+    const int per = a.tiles_x * a.tiles_y;
+#pragma unroll 1
+    for (int i = 0; i < per; ++i) {
+      conv02_body<T, 2>(a, b * per + i);
+      __syncthreads();
+    }
+    fixup_layer_sync();
+  }
+  constexpr int S_NT2 = conv_shape<T, false>(CONV_CLASS_NT2), S_NT2P = conv_shape<T, false>(CONV_CLASS_NT2_POOL),
+                S_NT1 = conv_shape<T, false>(CONV_CLASS_NT1);
+#pragma unroll 1
+  for (int k = 0; k < kFixupConvs; ++k) {
+    ConvArgs a = kernarg_block<ConvArgs>(k * (unsigned)(sizeof(ConvArgs) / 4));      // (k is uniform: scalar loads)
+    pair_inference_args(a);
+    const bool big = a.Cout >= 128, pool = (p.pooled >> k) & 1;
+    const int per = a.tiles_x * a.tiles_y * (big ? a.Cout / 128 : 1), nblk = per * a.B;
+#pragma unroll 1
+    for (int v = b * per; v < (b + 1) * per; ++v) {
+      const int blk = xcd_contiguous_inv(v, nblk);      // conv_block_map(blk, nblk, gy) is position v again
+      if (big && pool) conv3x3_body<T, 4, 2, 2, 2, true, 1, false, S_NT2P, true>(a, blk, nblk);
+      else if (big) conv3x3_body<T, 4, 2, 2, 2, false, 1, false, S_NT2, true>(a, blk, nblk);
+      else conv3x3_body<T, 4, 1, 2, 2, false, 2, false, S_NT1, true>(a, blk, nblk);
+      __syncthreads();
+    }
+    fixup_layer_sync();
+  }
+  // the sample's three inv_norm values, from the slots and in the order of inv_norm_multi_kernel
+  __shared__ double sh[4];
+#pragma unroll
+  for (int l = 0; l < 3; ++l) {
+    inv_norm_row(pair_global(p.ss[l]), p.np[l], pair_global(p.inv[l]), b, sh);
+    __syncthreads();
+  }
+}
+
 // What a launch decides before it picks its kernel: the tile geometry (written into the arguments), the grid and the profile record.
 struct ConvPlan { bool small; int gx, gy, kid; double flops, bytes; };
 template <typename T, bool BWD>

@@ -293,6 +293,44 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   return launch_ok ? HLA_OK : HLA_ERR_ARG;
 }
 
+// The fix-up pass (col_gate) as ONE launch, a workgroup per sample: vgg_fixup_loop (conv_kernels.h) walks the argument blocks that
+// vgg_forward_t would have launched one by one, with the tile counts conv_plan gives them, and forms inv_norm at its end.  The
+// caller has checked that the column trim applies (vgg_first_col32: level 3, inference, deferred norm, no heads, no fold).
+template <typename T>
+int vgg_fixup_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
+                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
+                const int* col_gate, hipStream_t st) {
+  static_assert(sizeof(T) == 2, "vgg_fixup_loop: bf16 / fp16");
+  VggConvSet S;
+  vgg_build_convs<T>(x, x_plane, prm, packed, dtype, feat, false, ws, pl, B, H, W, flags, first_row8, first_col32, col_gate, S);
+  if (!S.ok) return HLA_ERR_ARG;
+  VggFixupArgs fa{};
+  fa.c02 = S.c02;
+  for (int k = 0; k < kFixupConvs; ++k) {
+    const int l = k + 2;
+    ConvArgs a = S.conv[l];
+    const bool ok = S.used[l] && (a.Cout >= 128 || !S.pool[l]) && !a.idx_out;
+    HLA_REQUIRE(ok, "vgg_fixup: layer %d is not one of the level-3 inference launches", l);
+    if (conv_plan<T, false>(a, S.pool[l]).small) a.tiles_y = (a.H - a.row_begin + 7) / 8;      // (the loop's tiles are 8 rows)
+    fa.conv[k] = a;
+    if (S.pool[l]) fa.pooled |= 1 << k;
+  }
+  for (int l = kFixupConvs + 2; l < kAllLayers; ++l) HLA_REQUIRE(!S.used[l], "vgg_fixup: level 3 only");
+  for (int l = 0; l < 3; ++l) {      // (as vgg_norms fills inv_norm_multi_kernel's rows)
+    fa.ss[l] = (const double*)(ws + pl.ss[l]); fa.np[l] = S.np_used[l];
+    fa.inv[l] = (inv_norm ? inv_norm : (double*)(ws + pl.inv)) + (size_t)l * B;
+  }
+  fa.gate = col_gate;
+  constexpr int lds_bytes = vgg_fixup_lds_bytes<T>();
+  static HlaPerDeviceOnce attr_once;
+  HLA_CHECK_HIP(attr_once.run([] {
+    return hipFuncSetAttribute((const void*)vgg_fixup_loop<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  }));
+  hipLaunchKernelGGL((vgg_fixup_loop<T>), dim3(B), dim3(256), lds_bytes, st, fa);
+  HLA_CHECK_HIP(hipGetLastError());
+  return HLA_OK;
+}
+
 // Inference forward of TWO networks (the satellite and the ground extractor) whose every convolution layer runs as ONE launch of
 // two segments.  The caller (hla_vgg_forward_pair) has checked the flags; returns HLA_PAIR_FALLBACK with nothing launched when a
 // layer's two segments would not take the same kernel instantiation (the two sides of CONV_SMALL_GRID).
@@ -342,6 +380,11 @@ template int vgg_forward_t<TuT>(const float* x, size_t x_plane, const hla_vgg_pa
                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
                               int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st);
 template int vgg_forward_pair_t<TuT>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
+#if HLA_TU_DTYPE == 1 || HLA_TU_DTYPE == 2
+template int vgg_fixup_t<TuT>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
+                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
+                const int* col_gate, hipStream_t st);
+#endif
 #else
 #define HLA_EXTERN_T(T) \
   extern template void vgg_pack_all<T>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st); \
@@ -350,6 +393,12 @@ HLA_EXTERN_T(float) HLA_EXTERN_T(bf16) HLA_EXTERN_T(f16) HLA_EXTERN_T(split32)
 #define HLA_EXTERN_PAIR_T(T) \
   extern template int vgg_forward_pair_t<T>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
 HLA_EXTERN_PAIR_T(float) HLA_EXTERN_PAIR_T(bf16) HLA_EXTERN_PAIR_T(f16) HLA_EXTERN_PAIR_T(split32)
+extern template int vgg_fixup_t<bf16>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
+                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
+                const int* col_gate, hipStream_t st);
+extern template int vgg_fixup_t<f16>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
+                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
+                const int* col_gate, hipStream_t st);
 
 extern "C" size_t hla_vgg_packed_weight_bytes(int dtype) {
   return packed_offset(kAllLayers, dtype) + (dtype == HLA_F16X3 ? kPackTailBytes : 0);
@@ -387,10 +436,11 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
                               flags, first_row8, 0, nullptr, stream);
 }
 
-extern "C" int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
-                                    void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
-                                    size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
-                                    int first_row8, int first_col32, const int* col_gate, hla_stream_t stream) {
+// hla_vgg_forward_cols; fixup_one_launch: a fix-up pass (col_gate) may run as vgg_fixup_loop
+static int vgg_forward_cols_impl(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
+                                 void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
+                                 size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
+                                 int first_row8, int first_col32, const int* col_gate, bool fixup_one_launch, hla_stream_t stream) {
   HLA_REQUIRE(x && params && packed_weights && feat && workspace, "hla_vgg_forward: null argument");
   HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_forward: dtype must be HLA_F32, HLA_BF16, HLA_F16 or HLA_F16X3 (got %d)", dtype);
   HLA_REQUIRE(B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, "hla_vgg_forward: H and W must be multiples of 8");
@@ -424,6 +474,15 @@ extern "C" int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vg
     hla_set_error("hla_vgg_forward: workspace %zu < %zu", workspace_bytes, pl.total);
     return HLA_ERR_WORKSPACE;
   }
+  // The fix-up pass as one launch: the 16-bit types (first_col32 > 0 here says the rest: level 3, inference, deferred norm, no
+  // confidence heads, no folded decoder).  fp32 and a profiled run, whose records are per layer, keep the ten gated launches.
+  if (col_gate && fixup_one_launch && (dtype == HLA_BF16 || dtype == HLA_F16) && !hla_prof_on()) {
+    if (dtype == HLA_BF16)
+      return vgg_fixup_t<bf16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, inv_norm, (char*)workspace, pl, B, H, W, flags,
+                               first_row8, first_col32, col_gate, (hipStream_t)stream);
+    return vgg_fixup_t<f16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, inv_norm, (char*)workspace, pl, B, H, W, flags,
+                            first_row8, first_col32, col_gate, (hipStream_t)stream);
+  }
   if (dtype == HLA_BF16)
     return vgg_forward_t<bf16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
                                B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
@@ -435,6 +494,23 @@ extern "C" int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vg
                                   B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
   return vgg_forward_t<float>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
                               B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
+}
+
+extern "C" int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
+                                    void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
+                                    size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
+                                    int first_row8, int first_col32, const int* col_gate, hla_stream_t stream) {
+  return vgg_forward_cols_impl(x, x_plane, params, packed_weights, feat, conf, inv_norm, workspace, workspace_bytes, B, H, W, level, dtype,
+                               flags, first_row8, first_col32, col_gate, true, stream);
+}
+
+extern "C" int hla_vgg_fixup(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
+                             void* const feat[4], double* inv_norm, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                             int level, int dtype, int flags, int first_row8, int first_col32, const int* col_gate, int one_launch,
+                             hla_stream_t stream) {
+  HLA_REQUIRE(col_gate, "hla_vgg_fixup: col_gate is required");
+  return vgg_forward_cols_impl(x, x_plane, params, packed_weights, feat, nullptr, inv_norm, workspace, workspace_bytes, B, H, W, level,
+                               dtype, flags, first_row8, first_col32, col_gate, one_launch != 0, stream);
 }
 
 extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level, int dtype, int flags, int* paired_out, hla_stream_t stream) {

@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 30
+#define HLA_ABI_VERSION 31
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -161,6 +161,16 @@ int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vgg_params* p
                          void* const feat[4], float* const conf[4], double* inv_norm, void* workspace, size_t workspace_bytes,
                          int B, int H, int W, int level, int dtype, int flags, int first_row8, int first_col32,
                          const int* col_gate, hla_stream_t stream);
+
+/* The fix-up pass alone: hla_vgg_forward_cols with a col_gate (required here) and the choice of how it is launched.
+ * one_launch  non-zero (what hla_vgg_forward_cols does): for HLA_BF16 / HLA_F16, and with no hla_prof session open, the pass is ONE
+ *          launch with a workgroup per sample -- a flagged sample's workgroup walks the ten layers over its columns and forms its
+ *          inv_norm -- so that the usual case, no sample flagged, costs one launch and not eleven in a dependent chain; a flagged
+ *          sample is then carried by one compute unit and takes milliseconds.  0, HLA_F32 or a profiled run: ten gated conv
+ *          launches and a gated inv_norm.  The results are the same, bit for bit. */
+int hla_vgg_fixup(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights, void* const feat[4],
+                  double* inv_norm, void* workspace, size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
+                  int first_row8, int first_col32, const int* col_gate, int one_launch, hla_stream_t stream);
 
 /* One network of hla_vgg_forward_pair: the per-network arguments of hla_vgg_forward, with the same meaning. */
 typedef struct hla_vgg_branch {
