@@ -40,6 +40,16 @@ extern HlaStampCfg g_hla_stamp;      // prof.hip
 
 static inline bool hla_dtype_ok(int dtype) { return dtype == HLA_F32 || dtype == HLA_BF16 || dtype == HLA_F16 || dtype == HLA_F16X3; }
 
+// f(HlaType<T>{}) with the element type of dtype code `dtype` (one the caller has checked with hla_dtype_ok); returns what f returns
+struct split32;      // conv_kernels.h
+template <typename T> struct HlaType { using type = T; };
+template <typename F> static inline auto hla_dispatch_dtype(int dtype, F&& f) {
+  if (dtype == HLA_BF16) return f(HlaType<__bf16>{});
+  if (dtype == HLA_F16) return f(HlaType<_Float16>{});
+  if (dtype == HLA_F16X3) return f(HlaType<split32>{});
+  return f(HlaType<float>{});
+}
+
 #define HLA_REQUIRE(cond, ...)      \
   do {                              \
     if (!(cond)) {                  \

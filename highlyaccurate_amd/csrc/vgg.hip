@@ -5,174 +5,118 @@
 
 template <typename T>
 void vgg_pack_all(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st) {
-  // split mode: the tail behind the last layer holds float[16] per-layer weight scales, float[16..31] (slot 16 = conv0's
-  // L1 bound) and 32 scratch words for the two reductions
-  float* tail = (float*)(packed + packed_offset(kAllLayers, dtype));
-  unsigned* scratch = (unsigned*)tail + 32;
-  if (Prec<T>::SPLIT) (void)hipMemsetAsync(tail, 0, kPackTailBytes, st);
-  if constexpr (!Prec<T>::SPLIT) {
-    PackTable tb{};
-    tb.b0 = prm->b[0];
-    int n = 0;
-    for (int l = 0; l < kAllLayers; ++l) {
-      if (l >= kPackedLayers && !prm->w[l]) continue;      // conv_dec3.* only when the caller supplies its padded weights
-      tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cout; tb.cin[n] = kLayers[l].cin;
-      tb.first[n] = l == 0 ? 1 : 0;
-      // the layout of the MFMA shape the layer's forward kernel class runs on; conv0 / conv2 (conv02_kernel) keep 32x32x16
-      tb.shape[n] = l >= 2 ? conv_shape<T, false>(conv_class(kLayers[l].cout, kLayers[l].pool != 0)) : SHAPE_32x32x16;
-      ++n;
-    }
+  constexpr bool SPLIT = Prec<T>::SPLIT;
+  std::conditional_t<SPLIT, SplitPackTable, PackTable> tb{};
+  if constexpr (!SPLIT) tb.b0 = prm->b[0];
+  int n = 0;
+  for (int l = 0; l < kAllLayers; ++l) {
+    if (l >= kPackedLayers && !prm->w[l]) continue;      // conv_dec3.* only when the caller supplies its padded weights
+    tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cout; tb.cin[n] = kLayers[l].cin;
+    tb.first[n] = l == 0 ? 1 : 0;
+    if constexpr (SPLIT) tb.slot[n] = l;
+    // the layout of the MFMA shape the layer's forward kernel class runs on; conv0 / conv2 (conv02_kernel) keep 32x32x16
+    else tb.shape[n] = l >= 2 ? conv_shape<T, false>(conv_class(kLayers[l].cout, vgg_layer_pools(l))) : SHAPE_32x32x16;
+    ++n;
+  }
+  if constexpr (!SPLIT) {
     hla_prof_begin(K_PACK, 0, (double)packed_offset(kAllLayers, dtype) * (1.0 + 4.0 / sizeof(T)), st);
     hipLaunchKernelGGL((pack_weights_multi_kernel<T>), dim3(256, n), dim3(256), 0, st, tb, packed);
-    hla_prof_end(st);
-    return;
-  }
-  if constexpr (Prec<T>::SPLIT) {      // two launches for the whole network: the |w| maxima, then the (hi, lo) fragments scaled by them
-    SplitPackTable tb{};
-    int n = 0;
-    for (int l = 0; l < kAllLayers; ++l) {
-      if (l >= kPackedLayers && !prm->w[l]) continue;        // conv_dec3.* only when the caller supplies its padded weights
-      tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cout; tb.cin[n] = kLayers[l].cin;
-      tb.first[n] = l == 0 ? 1 : 0; tb.slot[n] = l;
-      ++n;
-    }
+  } else {      // two launches for the whole network: the |w| maxima, then the (hi, lo) fragments scaled by them
+    // the tail behind the last layer holds float[16] per-layer weight scales, float[16..31] (slot 16 = conv0's L1 bound) and
+    // 32 scratch words for the two reductions
+    float* tail = (float*)(packed + packed_offset(kAllLayers, dtype));
+    unsigned* scratch = (unsigned*)tail + 32;
+    (void)hipMemsetAsync(tail, 0, kPackTailBytes, st);
     hla_prof_begin(K_PACK, 0, (double)packed_offset(kAllLayers, dtype) * 3.0, st);
     hipLaunchKernelGGL(absmax_multi_kernel, dim3(64, n), dim3(256), 0, st, tb, scratch, (unsigned*)tail + 16);
     hipLaunchKernelGGL(pack_weights_split_multi_kernel, dim3(256, n), dim3(256), 0, st, tb, packed, (const unsigned*)scratch, tail);
-    hla_prof_end(st);
   }
+  hla_prof_end(st);
 }
 
+// One forward call: what hla_vgg_forward_cols, hla_vgg_fixup or one branch of hla_vgg_forward_pair was given, checked and
+// completed (first_col32 where it applies, the plan) by vgg_forward_check
+struct VggFwdCall {
+  const float* x; size_t x_plane; const hla_vgg_params* prm; const char* packed;
+  void* const* feat; float* const* conf; double* inv_norm; char* ws; size_t ws_bytes;
+  int B, H, W, level, dtype, flags, first_row8, first_col32;
+  const int* col_gate;            // the fix-up pass of a forward made with first_col32 > 0
+  hipStream_t st;
+  VggPlan pl;
+};
+
 // Everything a forward launches for its convolution layers, as argument blocks.  The geometry (which rows a layer computes, its
-// sources, its epilogue's outputs) is decided once, here, for the plain forward and for the paired one (vgg_forward_pair_t).
+// sources, its epilogue's outputs: vgg_graph.h) is applied once, here, for the plain forward and for the paired one.
 struct VggConvSet {
   Conv02Args c02;
-  ConvArgs conv[kAllLayers];      // by layer index (vgg_layers.h); [0], [1] unused: conv0 + conv2 are c02
+  ConvArgs conv[kAllLayers];      // by layer index (vgg_graph.h); [0], [1] unused: conv0 + conv2 are c02
   bool used[kAllLayers], pool[kAllLayers];
   int np_used[4];                 // sum-of-squares partials per sample the feature layers actually write
-  bool ok;
 };
 template <typename T>
-static void vgg_build_convs(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                            bool want_conf, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
-                            const int* col_gate, VggConvSet& S) {
-  const bool level4 = pl.x2r != 0;
-  // HLA_VGG_FOLD_DECODER (VGGUnet_G2S, VGG.py:278-310): the maps behind the encoder are read as [2h, w/2].  On NHWC storage
-  // that is the same buffer, so only the geometry the decoder launches are given changes: dH(d), dW(d) for the 1/d maps.
-  const bool fold = (flags & HLA_VGG_FOLD_DECODER) != 0;
-  auto dH = [&](int d) { return fold ? 2 * (H / d) : H / d; };
-  auto dW = [&](int d) { return fold ? (W / d) / 2 : W / d; };
-  auto W_ = [&](int l) { return (const uint4*)(packed + packed_offset(l, dtype)); };
-  char* w = ws;
+static void vgg_build_convs(const VggFwdCall& c, bool want_conf, VggConvSet& S) {
+  const VggPlan& pl = c.pl;
+  const int B = c.B, H = c.H, W = c.W, flags = c.flags;
+  const bool level4 = c.level == 4, fold = (flags & HLA_VGG_FOLD_DECODER) != 0, train = (flags & HLA_VGG_SAVE_FOR_BACKWARD) != 0;
+  const bool fixup = c.col_gate != nullptr;
+  auto W_ = [&](int l) { return (const uint4*)(c.packed + packed_offset(l, c.dtype)); };
+  char* w = c.ws;
+  auto act = [&](int m) { return m >= 0 ? w + pl.act[m] : (char*)nullptr; };
   constexpr bool SPLIT = Prec<T>::SPLIT;
-  const float* wtail = (const float*)(packed + packed_offset(kAllLayers, dtype));       // split mode: weight scales
+  const float* wtail = (const float*)(c.packed + packed_offset(kAllLayers, c.dtype));   // split mode: weight scales
   unsigned* amax = (unsigned*)(w + pl.amax);                                           // split mode: [slot][B]
   auto AM = [&](int slot) { return (SPLIT && slot >= 0) ? amax + (size_t)slot * B : (unsigned*)nullptr; };
-  const bool train = flags & HLA_VGG_SAVE_FOR_BACKWARD;
-  // first_col32 = c > 0 (hla_vgg_forward has checked that nothing else reads the maps): every layer starts at tile column c, 2c or
-  // 4c of its own resolution -- the same COLUMN of the image at every resolution, so the three 2x2 pools and the 32-pixel tiles
-  // stay aligned.  A layer's left halo column was then never written by its producer and is read as zero (ConvArgs::col_begin),
-  // so its first columns are not the full run's: with conv2 exact from its first column (it computes conv0's halo itself) the
-  // first exact column is 64c (x3), 64c+1 (conv5), 64c+2 (conv7) -> 32c+1 (x8), 32c+2 / +3 / +4 (conv10 / 12 / 14) -> 16c+2 (x15),
-  // 32c+5 / +6 (dec1.1 / dec1.3 = x18), 64c+13 / +14 (dec2.1 / dec2.3 = x21).
-  // col_gate (the fix-up pass): the same layers over the columns that pass left wrong -- the skipped strip and, but for conv2, the
-  // tile column behind it -- for the samples whose gate is set.  Every map is then the full run's in every column.
-  const int c = first_col32;
-  auto cols = [&](int scale, bool exact_from_start, int& begin, int& tiles) {
-    begin = col_gate ? 0 : c * scale;
-    tiles = col_gate ? c * scale + (exact_from_start ? 0 : 1) : 0;
-  };
+  const VggFwdRows rows = vgg_fwd_rows(c.first_row8, level4, train, want_conf);
   S = VggConvSet{};
-  S.ok = true;
   for (int l = 0; l < 4; ++l) S.np_used[l] = pl.np[l];
   // conv0 + conv2 + pool fused (VGG.py:123-128): relu(x3)
   {
     Conv02Args& a = S.c02;
-    a.x_plane = x_plane ? x_plane : (size_t)H * W;
-    a.x = x; a.w0 = W_(0); a.b0 = prm->b[0]; a.w2 = W_(1); a.b2 = prm->b[1];
-    a.out_act = w + pl.x3;
+    a.x_plane = c.x_plane ? c.x_plane : (size_t)H * W;
+    a.x = c.x; a.w0 = W_(0); a.b0 = c.prm->b[0]; a.w2 = W_(1); a.b2 = c.prm->b[1];
+    a.out_act = act(AM_X3);
     if (train) {
-      a.a0_out = w + pl.a0;
-      a.idx_out = (unsigned char*)(w + pl.idx3);
+      a.a0_out = act(AM_A0);
+      a.idx_out = (unsigned char*)(w + pl.idx[IDX_3]);
     }
-    if (level4) a.a2_out = w + pl.x2r;
+    if (level4) a.a2_out = act(AM_X2);
     a.wtail = wtail; a.amax_out = AM(AM_X3); a.amax_a2_out = level4 ? AM(AM_X2) : nullptr;
     a.amax_a0_out = train ? AM(AM_A0) : nullptr;
-    // (first_row8, see below: x3 is needed from row 4f-16 on = conv2 row 8f-32)
-    const int f0 = (level4 || train) ? 0 : first_row8;
-    a.row_begin = f0 ? 8 * f0 - 32 : 0;
-    int ct;
-    cols(4, true, a.col_begin, ct);
-    a.gate = col_gate;
+    a.row_begin = rows.row[1];
+    const VggCols cc = vgg_cols(1, c.first_col32, fixup);
+    a.col_begin = cc.begin;
+    a.gate = c.col_gate;
     const int txf = (W + 31) / 32;
-    a.B = B; a.H = H; a.W = W; a.tiles_x = ct ? (ct < txf ? ct : txf) : txf - a.col_begin; a.tiles_y = (H - a.row_begin + 7) / 8;
+    a.B = B; a.H = H; a.W = W; a.tiles_y = (H - a.row_begin + 7) / 8;
+    a.tiles_x = cc.tiles ? (cc.tiles < txf ? cc.tiles : txf) : txf - a.col_begin;
   }
-  auto conv = [&](int l, const void* s1, int C1, int H_, int W_h, void* act, int relu, bool pool, const void* s2 = nullptr,
-                  int C2 = 0, int up1 = 0, void* raw = nullptr, double* ss = nullptr, unsigned char* idx = nullptr,
-                  int row_begin = 0, int norm_level = -1) {
-    // the packer laid the layer's weights out for the kernel class kLayers[l].pool puts it in: the launch must pick the same one
-    if (pool != (kLayers[l].pool != 0)) {
-      hla_set_error("vgg_forward: layer %d launched with pool = %d, the layer table says %d", l, (int)pool, kLayers[l].pool);
-      S.ok = false;
-      return;
-    }
-    ConvArgs& a = S.conv[l];
-    S.used[l] = true; S.pool[l] = pool;
-    a.raw16 = (raw && (flags & HLA_VGG_FEAT16)) ? 1 : 0;
-    a.row_begin = row_begin < 0 ? 0 : row_begin;
-    cols(c ? W_h / (W / 4) : 1, false, a.col_begin, a.col_tiles);      // (c > 0: never the folded or the level-4 geometry)
-    a.gate = col_gate;
-    a.idx_out = train ? idx : nullptr;
-    a.src1 = s1; a.src2 = s2;
-    a.C1 = C1; a.C2 = C2; a.up1 = up1; a.wpk = W_(l);
-    a.bias = kLayers[l].has_bias ? prm->b[l] : nullptr;
-    a.out_act = act; a.out_raw = (float*)raw; a.sumsq = ss;
-    a.B = B; a.H = H_; a.W = W_h; a.Cout = kLayers[l].cout;
-    a.relu_act = relu;
-    if (SPLIT) {      // which per-sample maxima the layer reads (its one or two sources) and writes (its activation output)
-      static const signed char kAm[13][3] = {{-1, -1, -1}, {-1, -1, -1}, {AM_X3, -1, AM_A5}, {AM_A5, -1, AM_X8}, {AM_X8, -1, AM_A10},
-                                             {AM_A10, -1, AM_A12}, {AM_A12, -1, AM_X15}, {AM_X15, AM_X8, AM_D1A}, {AM_D1A, -1, AM_X18},
-                                             {AM_X18, AM_X3, AM_D2A}, {AM_D2A, -1, AM_X21}, {AM_X21, AM_X2, AM_D3A}, {AM_D3A, -1, AM_X24}};
-      a.amax1 = AM(kAm[l][0]); a.amax2 = AM(kAm[l][1]); a.amax_out = AM(kAm[l][2]); a.wscale = wtail + l;
-    }
-    if (norm_level >= 0)      // sum-of-squares partials actually written by this launch: one per (tile, 128-cout block)
-      S.np_used[norm_level] = ((W_h + 31) / 32) * ((H_ - a.row_begin + 7) / 8) * (a.Cout >= 128 ? a.Cout / 128 : 1);
-  };
-  // first_row8 = f > 0: the caller reads the returned maps only from rows f (x15), 2f (x18), 4f (x21) on, so every layer only
-  // has to produce the rows those depend on -- a 3x3 conv needs one more input row, a 2x upsample halves, a 2x2 pool doubles:
-  //   x21 <- dec2.3 [4f..] <- dec2.1 [4f-1..] <- {up(x18) [2f-1..], x3 [4f-2..]};  x18 <- dec1.3 [2f-1..] <- dec1.1 [2f-2..] <-
-  //   {up(x15) [f-2..], x8 [2f-3..]};  x15 [f-2..] <- pool(conv14 [2f-4..]) <- conv12 [2f-5..] <- conv10 [2f-6..] <- x8 [2f-7..]
-  //   <- pool(conv7 [4f-14..]) <- conv5 [4f-15..] <- x3 [4f-16..]  (<- image row 8f-34: `dead_ground_rows`).
-  // Each launch starts exactly at its first needed row, so the one halo row above it is the first row its producer wrote.
-  // The 3x3 confidence heads read one row above the first confidence row that is used, so with them the decoder starts one
-  // row earlier (the encoder's needs do not change: x15 [f-2..] and x8 [2f-4..] are covered).
-  const int f = (level4 || train) ? 0 : first_row8;
-  const int wc = want_conf ? 1 : 0;
-  const int r_c5 = f ? 4 * f - 15 : 0, r_c7 = f ? 4 * f - 14 : 0, r_c10 = f ? 2 * f - 6 : 0, r_c12 = f ? 2 * f - 5 : 0,
-            r_c14 = f ? 2 * f - 4 : 0, r_d11 = f ? 2 * f - 2 - wc : 0, r_d13 = f ? 2 * f - 1 - wc : 0,
-            r_d21 = f ? 4 * f - 1 - wc : 0, r_d23 = f ? 4 * f - wc : 0;
-  // encoder (VGG.py:129-141).  ReLU commutes with max-pool, so pooled maps are stored post-ReLU.
-  conv(2, w + pl.x3, 64, H / 2, W / 2, w + pl.a5, 1, false, nullptr, 0, 0, nullptr, nullptr, nullptr, r_c5);      // conv5
-  conv(3, w + pl.a5, 128, H / 2, W / 2, w + pl.x8, 1, true, nullptr, 0, 0, nullptr, nullptr,
-       (unsigned char*)(w + pl.idx8), r_c7);                                          // conv7 + pool -> relu(x8)
-  conv(4, w + pl.x8, 128, H / 4, W / 4, w + pl.a10, 1, false, nullptr, 0, 0, nullptr, nullptr, nullptr, r_c10);   // conv10
-  conv(5, w + pl.a10, 256, H / 4, W / 4, w + pl.a12, 1, false, nullptr, 0, 0, nullptr, nullptr, nullptr, r_c12);  // conv12
-  conv(6, w + pl.a12, 256, H / 4, W / 4, w + pl.x15r, 1, true, nullptr, 0, 0, feat[0],
-       (double*)(w + pl.ss[0]), (unsigned char*)(w + pl.idx15), r_c14, 0);            // conv14 + pool -> x15
-  // decoder (VGG.py:144-151): conv(relu(cat(up(a), skip))) with both inputs stored post-ReLU
-  conv(7, w + pl.x15r, 256, dH(4), dW(4), w + pl.d1a, 1, false, w + pl.x8, 128, 1, nullptr, nullptr, nullptr, r_d11);   // dec1.1
-  conv(8, w + pl.d1a, 128, dH(4), dW(4), w + pl.x18r, 1, false, nullptr, 0, 0, feat[1],
-       (double*)(w + pl.ss[1]), nullptr, r_d13, 1);                                   // dec1.3 -> x18
   // relu(x21) feeds conv_dec3 (level 4), the conf2 head and the training backward only: without them the 16-bit feature path
   // stores just the raw map
-  const bool x21r_dead = !level4 && !wc && !train && (flags & HLA_VGG_FEAT16) && sizeof(T) == 2;
-  conv(9, w + pl.x18r, 128, dH(2), dW(2), w + pl.d2a, 1, false, w + pl.x3, 64, 1, nullptr, nullptr, nullptr, r_d21);    // dec2.1
-  conv(10, w + pl.d2a, 64, dH(2), dW(2), x21r_dead ? (char*)nullptr : w + pl.x21r, 1, false, nullptr, 0, 0, feat[2],
-       (double*)(w + pl.ss[2]), nullptr, r_d23, 2);                                   // dec2.3 -> x21
-  if (level4) {      // VGG.py:153-155: conv_dec3 on cat(up(x21), x2), zero-padded to 64 channels (vgg_layers.h)
-    conv(11, w + pl.x21r, 64, dH(1), dW(1), w + pl.d3a, 1, false, w + pl.x2r, 64, 1);          // dec3.1
-    conv(12, w + pl.d3a, 64, dH(1), dW(1), w + pl.x24r, 1, false, nullptr, 0, 0, feat[3],
-         (double*)(w + pl.ss[3]), nullptr, 0, 3);                                      // dec3.3 -> x24 (16 real channels)
+  const bool x21r_dead = !level4 && !want_conf && !train && (flags & HLA_VGG_FEAT16) && sizeof(T) == 2;
+  // encoder (VGG.py:129-141; ReLU commutes with max-pool, so pooled maps are stored post-ReLU), then the decoder (VGG.py:144-155)
+  for (int l = 2; l < (level4 ? kAllLayers : kPackedLayers); ++l) {
+    const VggFwdLaunch& f = kFwd[l];
+    const VggHW g = vgg_layer_hw(l, H, W, fold);
+    ConvArgs& a = S.conv[l];
+    S.used[l] = true; S.pool[l] = vgg_layer_pools(l);
+    void* raw = f.level >= 0 ? c.feat[f.level] : nullptr;
+    a.raw16 = (raw && (flags & HLA_VGG_FEAT16)) ? 1 : 0;
+    a.row_begin = rows.row[l];
+    const VggCols cc = vgg_cols(l, c.first_col32, fixup);
+    a.col_begin = cc.begin; a.col_tiles = cc.tiles;
+    a.gate = c.col_gate;
+    a.idx_out = (train && f.idx >= 0) ? (unsigned char*)(w + pl.idx[f.idx]) : nullptr;
+    a.src1 = act(f.src); a.src2 = act(f.skip);
+    a.C1 = kActMaps[f.src].C; a.C2 = f.skip >= 0 ? kActMaps[f.skip].C : 0; a.up1 = f.skip >= 0 ? 1 : 0; a.wpk = W_(l);
+    a.bias = kLayers[l].has_bias ? c.prm->b[l] : nullptr;
+    a.out_act = (f.out == AM_X21 && x21r_dead) ? (char*)nullptr : act(f.out); a.out_raw = (float*)raw;
+    a.sumsq = f.level >= 0 ? (double*)(w + pl.ss[f.level]) : nullptr;
+    a.B = B; a.H = g.h; a.W = g.w; a.Cout = kLayers[l].cout;
+    a.relu_act = 1;
+    if (SPLIT) {      // which per-sample maxima the layer reads (its one or two sources) and writes (its activation output)
+      a.amax1 = AM(f.src); a.amax2 = AM(f.skip); a.amax_out = AM(f.out); a.wscale = wtail + l;
+    }
+    if (f.level >= 0) S.np_used[f.level] = vgg_level_partials(l, H, W, fold, a.row_begin);      // the partials this launch writes
   }
 }
 
@@ -192,78 +136,66 @@ static int launch_conv02(hipStream_t st, Conv02Args a, const Conv02Args* a1) {
     return (double)c.B * (c.H - c.row_begin) * ((x1 < c.W ? x1 : c.W) - c.col_begin * 32);
   };
   const double Pt = P(a) + (a1 ? P(*a1) : 0.0);
+  static HlaPerDeviceOnce attr_once[2];
+  HLA_CHECK_HIP(attr_once[a1 ? 1 : 0].run([a1] {
+    const void* fn = a1 ? (const void*)conv02_pair_kernel<T, 2> : (const void*)conv02_kernel<T, 2>;
+    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  }));
+  hla_prof_begin(K_CONV02, 2.0 * 9 * (3 + 64) * 64 * Pt, Pt * (3 * 4 + 16 * sizeof(T)), st);
   if (a1) {
-    static HlaPerDeviceOnce attr_once;
-    HLA_CHECK_HIP(attr_once.run([] {
-      return hipFuncSetAttribute((const void*)conv02_pair_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    }));
     PairArgs<Conv02Args> pa{{a, *a1}, a.tiles_x * a.tiles_y * a.B};
 #if HLA_CONV_STAMPS
     pa.s[1].stamps = nullptr;
 #endif
-    hla_prof_begin(K_CONV02, 2.0 * 9 * (3 + 64) * 64 * Pt, Pt * (3 * 4 + 16 * sizeof(T)), st);
     hipLaunchKernelGGL((conv02_pair_kernel<T, 2>), dim3(pa.n0 + a1->tiles_x * a1->tiles_y * a1->B), dim3(256), lds_bytes, st, pa);
-    hla_prof_end(st);
-    return HLA_OK;
-  }
-  static HlaPerDeviceOnce attr_once;
-  HLA_CHECK_HIP(attr_once.run([] {
-    return hipFuncSetAttribute((const void*)conv02_kernel<T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  }));
-  hla_prof_begin(K_CONV02, 2.0 * 9 * (3 + 64) * 64 * Pt, Pt * (3 * 4 + 16 * sizeof(T)), st);
-  hipLaunchKernelGGL((conv02_kernel<T, 2>), dim3(a.tiles_x * a.tiles_y * a.B), dim3(256), lds_bytes, st, a);
+  } else
+    hipLaunchKernelGGL((conv02_kernel<T, 2>), dim3(a.tiles_x * a.tiles_y * a.B), dim3(256), lds_bytes, st, a);
   hla_prof_end(st);
   return HLA_OK;
 }
 
 // L2 normalisation: 1/||x|| per sample (always) for the NL levels of `nb` networks in one launch, then the in-place scaling unless
 // the caller folds it downstream
-struct VggNormNet { const VggConvSet* S; char* ws; const VggPlan* pl; double* inv_norm; void* const* feat; int H, W; };
-static int vgg_norms(hipStream_t st, int nb, const VggNormNet* net, int B, int NL, int flags, const int* gate = nullptr) {
+static int vgg_norms(int nb, const VggFwdCall* const* net, const VggConvSet* S, int NL) {
+  const VggFwdCall& c0 = *net[0];
+  const int B = c0.B;
+  hipStream_t st = c0.st;
   InvNormArgs ia{};
-  ia.gate = gate;
+  ia.gate = c0.col_gate;
   double bytes = 0;
   for (int k = 0; k < nb; ++k)
     for (int l = 0; l < NL; ++l) {
-      const VggNormNet& n = net[k];
-      ia.ss[k * NL + l] = (const double*)(n.ws + n.pl->ss[l]); ia.np[k * NL + l] = n.S->np_used[l];
-      ia.inv[k * NL + l] = (n.inv_norm ? n.inv_norm : (double*)(n.ws + n.pl->inv)) + (size_t)l * B;
-      bytes += (double)B * n.pl->np[l] * 8;
+      const VggFwdCall& n = *net[k];
+      ia.ss[k * NL + l] = (const double*)(n.ws + n.pl.ss[l]); ia.np[k * NL + l] = S[k].np_used[l];
+      ia.inv[k * NL + l] = (n.inv_norm ? n.inv_norm : (double*)(n.ws + n.pl.inv)) + (size_t)l * B;
+      bytes += (double)B * n.pl.np[l] * 8;
     }
   hla_prof_begin(K_L2NORM, 0, bytes, st);
   hipLaunchKernelGGL(inv_norm_multi_kernel, dim3(B, nb * NL), dim3(256), 0, st, ia);
   hla_prof_end(st);
-  for (int k = 0; k < nb; ++k) {
-    const int H = net[k].H, W = net[k].W;
-    const size_t per[4] = {(size_t)(H / 8) * (W / 8) * 256, (size_t)(H / 4) * (W / 4) * 128, (size_t)(H / 2) * (W / 2) * 64, (size_t)H * W * 64};
+  for (int k = 0; k < nb; ++k)
     for (int l = 0; l < NL; ++l) {
-      if (flags & HLA_VGG_DEFER_NORM) continue;
-      int bps = (int)(per[l] / 4 / 256 / 4);
+      if (c0.flags & HLA_VGG_DEFER_NORM) continue;
+      const size_t per = vgg_map_elems(kActMaps[kLevelMap[l]], net[k]->H, net[k]->W);
+      int bps = (int)(per / 4 / 256 / 4);
       bps = bps < 1 ? 1 : (bps > 64 ? 64 : bps);
-      hla_prof_begin(K_L2NORM, 0, (double)B * per[l] * 8, st);
-      hipLaunchKernelGGL(scale_kernel, dim3(B * bps), dim3(256), 0, st, (float*)net[k].feat[l], ia.inv[k * NL + l], per[l], bps);
+      hla_prof_begin(K_L2NORM, 0, (double)B * per * 8, st);
+      hipLaunchKernelGGL(scale_kernel, dim3(B * bps), dim3(256), 0, st, (float*)net[k]->feat[l], ia.inv[k * NL + l], per, bps);
       hla_prof_end(st);
     }
-  }
   return HLA_OK;
 }
 
 template <typename T>
-int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                         float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
-                         int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st) {
-  const bool level4 = pl.x2r != 0;
-  const int NL = level4 ? 4 : 3;
-  const bool fold = (flags & HLA_VGG_FOLD_DECODER) != 0;
-  auto dH = [&](int d) { return fold ? 2 * (H / d) : H / d; };
-  auto dW = [&](int d) { return fold ? (W / d) / 2 : W / d; };
-  char* w = ws;
+int vgg_forward_t(const VggFwdCall& c) {
+  const VggPlan& pl = c.pl;
+  const int NL = c.level == 4 ? 4 : 3, B = c.B;
+  hipStream_t st = c.st;
   constexpr bool SPLIT = Prec<T>::SPLIT;
-  if (SPLIT) HLA_CHECK_HIP(hipMemsetAsync(w + pl.amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
-  const bool want_conf = (flags & HLA_VGG_WANT_CONF) && conf;
+  if (SPLIT) HLA_CHECK_HIP(hipMemsetAsync(c.ws + pl.amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
+  const bool want_conf = (c.flags & HLA_VGG_WANT_CONF) && c.conf;
   VggConvSet S;
-  vgg_build_convs<T>(x, x_plane, prm, packed, dtype, feat, want_conf, ws, pl, B, H, W, flags, first_row8, first_col32, col_gate, S);
-  if (!S.ok) return HLA_ERR_ARG;
+  vgg_build_convs<T>(c, want_conf, S);
   if (const int rc = launch_conv02<T>(st, S.c02, nullptr)) return rc;
   bool launch_ok = true;
   for (int l = 2; l < kAllLayers; ++l)
@@ -271,24 +203,22 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
   // confidence heads on the ReLU'd maps
   if (want_conf) {
     using CT = std::conditional_t<SPLIT, float, T>;      // split mode stores fp32 activations: the heads run in plain fp32
-    const CT* acts[4] = {(const CT*)(w + pl.x15r), (const CT*)(w + pl.x18r), (const CT*)(w + pl.x21r), (const CT*)(w + pl.x24r)};
-    // (conf0 reads the UNFOLDED x15 also under HLA_VGG_FOLD_DECODER: VGG.py:322)
-    const int Cs[4] = {256, 128, 64, 64}, hs[4] = {H / 8, dH(4), dH(2), dH(1)}, wsz[4] = {W / 8, dW(4), dW(2), dW(1)};
     for (int l = 0; l < NL; ++l) {
-      if (!conf[l]) continue;
-      const size_t npix = (size_t)B * hs[l] * wsz[l];
-      const int grid = B * ((hs[l] + CONF_TH - 1) / CONF_TH) * ((wsz[l] + CONF_TW - 1) / CONF_TW);
-      hla_prof_begin(K_CONF, 2.0 * 9 * Cs[l] * (double)npix, (double)npix * (Cs[l] * sizeof(CT) + 4), st);
-      if (Cs[l] == 256) hipLaunchKernelGGL((conf_kernel<CT, 256>), dim3(grid), dim3(256), 0, st, acts[l], prm->w[13 + l], conf[l], B, hs[l], wsz[l]);
-      else if (Cs[l] == 128) hipLaunchKernelGGL((conf_kernel<CT, 128>), dim3(grid), dim3(256), 0, st, acts[l], prm->w[13 + l], conf[l], B, hs[l], wsz[l]);
-      else hipLaunchKernelGGL((conf_kernel<CT, 64>), dim3(grid), dim3(256), 0, st, acts[l], prm->w[13 + l], conf[l], B, hs[l], wsz[l]);
+      if (!c.conf[l]) continue;
+      const VggMapDef& m = kActMaps[kLevelMap[l]];
+      const VggHW g = vgg_map_hw(m, c.H, c.W, (c.flags & HLA_VGG_FOLD_DECODER) != 0);
+      const CT* act = (const CT*)(c.ws + pl.act[kLevelMap[l]]);
+      const size_t npix = (size_t)B * g.h * g.w;
+      const int grid = B * ((g.h + CONF_TH - 1) / CONF_TH) * ((g.w + CONF_TW - 1) / CONF_TW);
+      hla_prof_begin(K_CONF, 2.0 * 9 * m.C * (double)npix, (double)npix * (m.C * sizeof(CT) + 4), st);
+      if (m.C == 256) hipLaunchKernelGGL((conf_kernel<CT, 256>), dim3(grid), dim3(256), 0, st, act, c.prm->w[13 + l], c.conf[l], B, g.h, g.w);
+      else if (m.C == 128) hipLaunchKernelGGL((conf_kernel<CT, 128>), dim3(grid), dim3(256), 0, st, act, c.prm->w[13 + l], c.conf[l], B, g.h, g.w);
+      else hipLaunchKernelGGL((conf_kernel<CT, 64>), dim3(grid), dim3(256), 0, st, act, c.prm->w[13 + l], c.conf[l], B, g.h, g.w);
       hla_prof_end(st);
     }
   }
-  {
-    const VggNormNet net{&S, ws, &pl, inv_norm, feat, H, W};
-    if (const int rc = vgg_norms(st, 1, &net, B, NL, flags, col_gate)) return rc;
-  }
+  const VggFwdCall* net = &c;
+  if (const int rc = vgg_norms(1, &net, &S, NL)) return rc;
   HLA_CHECK_HIP(hipGetLastError());
   return launch_ok ? HLA_OK : HLA_ERR_ARG;
 }
@@ -297,13 +227,10 @@ int vgg_forward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, con
 // vgg_forward_t would have launched one by one, with the tile counts conv_plan gives them, and forms inv_norm at its end.  The
 // caller has checked that the column trim applies (vgg_first_col32: level 3, inference, deferred norm, no heads, no fold).
 template <typename T>
-int vgg_fixup_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
-                const int* col_gate, hipStream_t st) {
+int vgg_fixup_t(const VggFwdCall& c) {
   static_assert(sizeof(T) == 2, "vgg_fixup_loop: bf16 / fp16");
   VggConvSet S;
-  vgg_build_convs<T>(x, x_plane, prm, packed, dtype, feat, false, ws, pl, B, H, W, flags, first_row8, first_col32, col_gate, S);
-  if (!S.ok) return HLA_ERR_ARG;
+  vgg_build_convs<T>(c, false, S);
   VggFixupArgs fa{};
   fa.c02 = S.c02;
   for (int k = 0; k < kFixupConvs; ++k) {
@@ -317,41 +244,30 @@ int vgg_fixup_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const
   }
   for (int l = kFixupConvs + 2; l < kAllLayers; ++l) HLA_REQUIRE(!S.used[l], "vgg_fixup: level 3 only");
   for (int l = 0; l < 3; ++l) {      // (as vgg_norms fills inv_norm_multi_kernel's rows)
-    fa.ss[l] = (const double*)(ws + pl.ss[l]); fa.np[l] = S.np_used[l];
-    fa.inv[l] = (inv_norm ? inv_norm : (double*)(ws + pl.inv)) + (size_t)l * B;
+    fa.ss[l] = (const double*)(c.ws + c.pl.ss[l]); fa.np[l] = S.np_used[l];
+    fa.inv[l] = (c.inv_norm ? c.inv_norm : (double*)(c.ws + c.pl.inv)) + (size_t)l * c.B;
   }
-  fa.gate = col_gate;
+  fa.gate = c.col_gate;
   constexpr int lds_bytes = vgg_fixup_lds_bytes<T>();
   static HlaPerDeviceOnce attr_once;
   HLA_CHECK_HIP(attr_once.run([] {
     return hipFuncSetAttribute((const void*)vgg_fixup_loop<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   }));
-  hipLaunchKernelGGL((vgg_fixup_loop<T>), dim3(B), dim3(256), lds_bytes, st, fa);
+  hipLaunchKernelGGL((vgg_fixup_loop<T>), dim3(c.B), dim3(256), lds_bytes, c.st, fa);
   HLA_CHECK_HIP(hipGetLastError());
   return HLA_OK;
 }
 
 // Inference forward of TWO networks (the satellite and the ground extractor) whose every convolution layer runs as ONE launch of
-// two segments.  The caller (hla_vgg_forward_pair) has checked the flags; returns HLA_PAIR_FALLBACK with nothing launched when a
+// two segments.  The caller (hla_vgg_forward_pair) has checked both calls; returns HLA_PAIR_FALLBACK with nothing launched when a
 // layer's two segments would not take the same kernel instantiation (the two sides of CONV_SMALL_GRID).
 constexpr int HLA_PAIR_FALLBACK = -1000;
-// Where first_col32 applies (include/hla.h); 0 elsewhere.  Not in split-fp16 mode: there every layer scales its operands by the
-// per-sample maximum of the WHOLE source map, which a trimmed forward does not know.
-static inline int vgg_first_col32(int first_col32, int level, int dtype, int flags) {
-  const bool ok = level == 3 && dtype != HLA_F16X3 && (flags & HLA_VGG_DEFER_NORM) &&
-                  !(flags & (HLA_VGG_SAVE_FOR_BACKWARD | HLA_VGG_FOLD_DECODER | HLA_VGG_WANT_CONF));
-  return ok ? first_col32 : 0;
-}
-static inline int pair_first_col32(const hla_vgg_branch& b, int dtype, int flags) { return vgg_first_col32(b.first_col32, 3, dtype, flags); }
 template <typename T>
-int vgg_forward_pair_t(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st) {
+int vgg_forward_pair_t(const VggFwdCall c[2]) {
   constexpr bool SPLIT = Prec<T>::SPLIT;
+  hipStream_t st = c[0].st;
   VggConvSet S[2];
-  for (int k = 0; k < 2; ++k) {
-    vgg_build_convs<T>(br[k].x, br[k].x_plane, br[k].params, (const char*)br[k].packed_weights, dtype, br[k].feat, false,
-                       (char*)br[k].workspace, pl[k], B, br[k].H, br[k].W, flags, br[k].first_row8, pair_first_col32(br[k], dtype, flags), nullptr, S[k]);
-    if (!S[k].ok) return HLA_ERR_ARG;
-  }
+  for (int k = 0; k < 2; ++k) vgg_build_convs<T>(c[k], false, S[k]);
   for (int l = 2; l < kAllLayers; ++l) {
     if (S[0].used[l] != S[1].used[l]) return HLA_PAIR_FALLBACK;
     if (!S[0].used[l]) continue;
@@ -360,45 +276,32 @@ int vgg_forward_pair_t(const hla_vgg_branch br[2], const VggPlan pl[2], int B, i
   }
   if (SPLIT)
     for (int k = 0; k < 2; ++k)
-      HLA_CHECK_HIP(hipMemsetAsync((char*)br[k].workspace + pl[k].amax, 0, (size_t)kAmaxSlots * B * sizeof(unsigned), st));
+      HLA_CHECK_HIP(hipMemsetAsync(c[k].ws + c[k].pl.amax, 0, (size_t)kAmaxSlots * c[k].B * sizeof(unsigned), st));
   if (const int rc = launch_conv02<T>(st, S[0].c02, &S[1].c02)) return rc;
   bool launch_ok = true;
   for (int l = 2; l < kAllLayers; ++l)
     if (S[0].used[l] && !launch_conv_pair<T>(st, S[0].conv[l], S[1].conv[l], S[0].pool[l])) launch_ok = false;
-  {
-    const VggNormNet nets[2] = {{&S[0], (char*)br[0].workspace, &pl[0], br[0].inv_norm, br[0].feat, br[0].H, br[0].W},
-                                {&S[1], (char*)br[1].workspace, &pl[1], br[1].inv_norm, br[1].feat, br[1].H, br[1].W}};
-    if (const int rc = vgg_norms(st, 2, nets, B, 3, flags)) return rc;
-  }
+  const VggFwdCall* nets[2] = {&c[0], &c[1]};
+  if (const int rc = vgg_norms(2, nets, S, 3)) return rc;
   HLA_CHECK_HIP(hipGetLastError());
   return launch_ok ? HLA_OK : HLA_ERR_ARG;
 }
 
 #if HLA_TU_DTYPE >= 0
 template void vgg_pack_all<TuT>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st);
-template int vgg_forward_t<TuT>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                              float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,
-                              int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st);
-template int vgg_forward_pair_t<TuT>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
+template int vgg_forward_t<TuT>(const VggFwdCall& c);
+template int vgg_forward_pair_t<TuT>(const VggFwdCall c[2]);
 #if HLA_TU_DTYPE == 1 || HLA_TU_DTYPE == 2
-template int vgg_fixup_t<TuT>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
-                const int* col_gate, hipStream_t st);
+template int vgg_fixup_t<TuT>(const VggFwdCall& c);
 #endif
 #else
 #define HLA_EXTERN_T(T) \
   extern template void vgg_pack_all<T>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st); \
-  extern template int vgg_forward_t<T>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],                               float* const conf[4], double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W,                               int flags, int first_row8, int first_col32, const int* col_gate, hipStream_t st);
+  extern template int vgg_forward_t<T>(const VggFwdCall& c); \
+  extern template int vgg_forward_pair_t<T>(const VggFwdCall c[2]);
 HLA_EXTERN_T(float) HLA_EXTERN_T(bf16) HLA_EXTERN_T(f16) HLA_EXTERN_T(split32)
-#define HLA_EXTERN_PAIR_T(T) \
-  extern template int vgg_forward_pair_t<T>(const hla_vgg_branch br[2], const VggPlan pl[2], int B, int dtype, int flags, hipStream_t st);
-HLA_EXTERN_PAIR_T(float) HLA_EXTERN_PAIR_T(bf16) HLA_EXTERN_PAIR_T(f16) HLA_EXTERN_PAIR_T(split32)
-extern template int vgg_fixup_t<bf16>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
-                const int* col_gate, hipStream_t st);
-extern template int vgg_fixup_t<f16>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packed, int dtype, void* const feat[4],
-                double* inv_norm, char* ws, const VggPlan& pl, int B, int H, int W, int flags, int first_row8, int first_col32,
-                const int* col_gate, hipStream_t st);
+extern template int vgg_fixup_t<bf16>(const VggFwdCall& c);
+extern template int vgg_fixup_t<f16>(const VggFwdCall& c);
 
 extern "C" size_t hla_vgg_packed_weight_bytes(int dtype) {
   return packed_offset(kAllLayers, dtype) + (dtype == HLA_F16X3 ? kPackTailBytes : 0);
@@ -408,10 +311,7 @@ extern "C" int hla_vgg_pack_weights(const hla_vgg_params* params, void* packed, 
   HLA_REQUIRE(params && packed, "hla_vgg_pack_weights: null argument");
   HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_pack_weights: bad dtype %d", dtype);
   HLA_REQUIRE(params->w[0] && params->b[0], "hla_vgg_pack_weights: conv0's weight and bias are required (the bias is packed with it)");
-  if (dtype == HLA_BF16) vgg_pack_all<bf16>(params, (char*)packed, dtype, (hipStream_t)stream);
-  else if (dtype == HLA_F16) vgg_pack_all<f16>(params, (char*)packed, dtype, (hipStream_t)stream);
-  else if (dtype == HLA_F16X3) vgg_pack_all<split32>(params, (char*)packed, dtype, (hipStream_t)stream);
-  else vgg_pack_all<float>(params, (char*)packed, dtype, (hipStream_t)stream);
+  hla_dispatch_dtype(dtype, [&](auto t) { vgg_pack_all<typename decltype(t)::type>(params, (char*)packed, dtype, (hipStream_t)stream); });
   HLA_CHECK_HIP(hipGetLastError());
   return HLA_OK;
 }
@@ -428,6 +328,72 @@ extern "C" size_t hla_vgg_workspace_bytes_flags(int B, int H, int W, int level, 
   return p.total;
 }
 
+// Where first_col32 applies (include/hla.h); 0 elsewhere.  Not in split-fp16 mode: there every layer scales its operands by the
+// per-sample maximum of the WHOLE source map, which a trimmed forward does not know.
+static inline int vgg_first_col32(int first_col32, int level, int dtype, int flags) {
+  const bool ok = level == 3 && dtype != HLA_F16X3 && (flags & HLA_VGG_DEFER_NORM) &&
+                  !(flags & (HLA_VGG_SAVE_FOR_BACKWARD | HLA_VGG_FOLD_DECODER | HLA_VGG_WANT_CONF));
+  return ok ? first_col32 : 0;
+}
+
+// The argument checks of a forward call; then its column trim where that applies, its plan and the workspace check.  Returns
+// HLA_OK or the code to return, with the message set unless `silent` (hla_vgg_forward_pair: a call that fails here is made, and
+// reported, by the plain entry).  A fix-up pass with nothing to fix (col_gate && !first_col32 on return) is not planned.
+static int vgg_forward_check(VggFwdCall& c, bool silent) {
+#define VGG_REQUIRE(cond, ...) \
+  do { if (!(cond)) { if (!silent) hla_set_error(__VA_ARGS__); return HLA_ERR_ARG; } } while (0)
+  const int H = c.H, W = c.W, level = c.level, dtype = c.dtype, flags = c.flags, first_row8 = c.first_row8, first_col32 = c.first_col32;
+  VGG_REQUIRE(c.x && c.prm && c.packed && c.feat && c.ws, "hla_vgg_forward: null argument");
+  VGG_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_forward: dtype must be HLA_F32, HLA_BF16, HLA_F16 or HLA_F16X3 (got %d)", dtype);
+  VGG_REQUIRE(c.B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, "hla_vgg_forward: H and W must be multiples of 8");
+  VGG_REQUIRE(c.x_plane == 0 || c.x_plane >= (size_t)H * W, "hla_vgg_forward: x_plane (%zu) must be 0 or >= H*W", c.x_plane);
+  // the conv kernels address a sample's activation map with signed 32-bit byte offsets (largest map: H x W x 64 fp32)
+  VGG_REQUIRE((size_t)H * W * 64 * 4 < ((size_t)1 << 31), "hla_vgg_forward: image too large (H*W must be below 2^23 pixels)");
+  VGG_REQUIRE(level == 3 || level == 4, "hla_vgg_forward: level must be 3 (x15,x18,x21) or 4 (+x24), got %d", level);
+  VGG_REQUIRE(c.feat[0] && c.feat[1] && c.feat[2], "hla_vgg_forward: feat[0..2] are required");
+  VGG_REQUIRE(level == 3 || (c.feat[3] && c.prm->w[11] && c.prm->w[12]),
+              "hla_vgg_forward: level 4 needs feat[3] ([B,H,W,64], 16 real channels) and the zero-padded conv_dec3 weights in w[11], w[12]");
+  VGG_REQUIRE(level == 3 || !(flags & HLA_VGG_WANT_CONF) || !c.conf || !c.conf[3] || c.prm->w[16], "hla_vgg_forward: conf[3] needs w[16]");
+  VGG_REQUIRE(!(flags & HLA_VGG_DEFER_NORM) || c.inv_norm, "hla_vgg_forward: HLA_VGG_DEFER_NORM needs inv_norm");
+  VGG_REQUIRE(!(flags & HLA_VGG_FEAT16) || ((dtype == HLA_BF16 || dtype == HLA_F16) && (flags & HLA_VGG_DEFER_NORM) &&
+                                            !(flags & HLA_VGG_SAVE_FOR_BACKWARD) && level == 3),
+              "hla_vgg_forward: HLA_VGG_FEAT16 needs dtype HLA_BF16 / HLA_F16, HLA_VGG_DEFER_NORM, level 3 and no HLA_VGG_SAVE_FOR_BACKWARD");
+  VGG_REQUIRE(first_row8 == 0 || (first_row8 >= 4 && first_row8 < H / 8), "hla_vgg_forward: first_row8 must be 0 or in [4, H/8)");
+  // folded decoder: the narrowest folded map (x15, W/16 wide) is up-sampled 2x into the W/8-wide dec1 geometry, so W/8 must be
+  // even; the 32-px / 8-row conv tiles take partial tiles at the right / bottom edge as for any other width (the partial-sum
+  // slots of the folded tile counts are planned by hla_vgg_workspace_bytes_flags, vgg_layers.h); every row of every map is read
+  VGG_REQUIRE(!(flags & HLA_VGG_FOLD_DECODER) || (W % 16 == 0 && first_row8 == 0 && !(flags & HLA_VGG_FEAT16)),
+              "hla_vgg_forward: HLA_VGG_FOLD_DECODER needs W %% 16 == 0 (folded maps are W/16, W/8, W/4 wide), first_row8 == 0 and no "
+              "HLA_VGG_FEAT16 (got W = %d, first_row8 = %d)", W, first_row8);
+  VGG_REQUIRE(first_col32 >= 0 && (first_col32 == 0 || 128 * first_col32 < W),
+              "hla_vgg_forward_cols: first_col32 must be 0 or leave a column of the map (128 * first_col32 < W; got %d, W = %d)", first_col32, W);
+  VGG_REQUIRE(!c.col_gate || first_col32 > 0, "hla_vgg_forward_cols: col_gate is the fix-up pass of a forward made with first_col32 > 0");
+#undef VGG_REQUIRE
+  c.first_col32 = vgg_first_col32(first_col32, level, dtype, flags);
+  if (c.col_gate && !c.first_col32) return HLA_OK;      // that forward computed every column: nothing to fix
+  vgg_plan(c.B, H, W, dtype, (flags & HLA_VGG_SAVE_FOR_BACKWARD) != 0, &c.pl, level == 4, (flags & HLA_VGG_FOLD_DECODER) != 0);
+  if (c.ws_bytes < c.pl.total) {
+    if (!silent) hla_set_error("hla_vgg_forward: workspace %zu < %zu", c.ws_bytes, c.pl.total);
+    return HLA_ERR_WORKSPACE;
+  }
+  return HLA_OK;
+}
+
+// hla_vgg_forward_cols; fixup_one_launch: a fix-up pass (col_gate) may run as vgg_fixup_loop
+static int vgg_forward_cols_impl(VggFwdCall c, bool fixup_one_launch) {
+  if (const int rc = vgg_forward_check(c, false)) return rc;
+  if (c.col_gate && !c.first_col32) return HLA_OK;
+  // The fix-up pass as one launch: the 16-bit types (first_col32 > 0 here says the rest: level 3, inference, deferred norm, no
+  // confidence heads, no folded decoder).  fp32 and a profiled run, whose records are per layer, keep the ten gated launches.
+  const bool one_launch = c.col_gate && fixup_one_launch && !hla_prof_on();
+  return hla_dispatch_dtype(c.dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (std::is_same_v<T, bf16> || std::is_same_v<T, f16>)
+      if (one_launch) return vgg_fixup_t<T>(c);
+    return vgg_forward_t<T>(c);
+  });
+}
+
 extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
                                void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
                                size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
@@ -436,72 +402,13 @@ extern "C" int hla_vgg_forward(const float* x, size_t x_plane, const hla_vgg_par
                               flags, first_row8, 0, nullptr, stream);
 }
 
-// hla_vgg_forward_cols; fixup_one_launch: a fix-up pass (col_gate) may run as vgg_fixup_loop
-static int vgg_forward_cols_impl(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
-                                 void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
-                                 size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
-                                 int first_row8, int first_col32, const int* col_gate, bool fixup_one_launch, hla_stream_t stream) {
-  HLA_REQUIRE(x && params && packed_weights && feat && workspace, "hla_vgg_forward: null argument");
-  HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_forward: dtype must be HLA_F32, HLA_BF16, HLA_F16 or HLA_F16X3 (got %d)", dtype);
-  HLA_REQUIRE(B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0, "hla_vgg_forward: H and W must be multiples of 8");
-  HLA_REQUIRE(x_plane == 0 || x_plane >= (size_t)H * W, "hla_vgg_forward: x_plane (%zu) must be 0 or >= H*W", x_plane);
-  // the conv kernels address a sample's activation map with signed 32-bit byte offsets (largest map: H x W x 64 fp32)
-  HLA_REQUIRE((size_t)H * W * 64 * 4 < ((size_t)1 << 31), "hla_vgg_forward: image too large (H*W must be below 2^23 pixels)");
-  HLA_REQUIRE(level == 3 || level == 4, "hla_vgg_forward: level must be 3 (x15,x18,x21) or 4 (+x24), got %d", level);
-  HLA_REQUIRE(feat[0] && feat[1] && feat[2], "hla_vgg_forward: feat[0..2] are required");
-  HLA_REQUIRE(level == 3 || (feat[3] && params->w[11] && params->w[12]),
-              "hla_vgg_forward: level 4 needs feat[3] ([B,H,W,64], 16 real channels) and the zero-padded conv_dec3 weights in w[11], w[12]");
-  HLA_REQUIRE(level == 3 || !(flags & HLA_VGG_WANT_CONF) || !conf || !conf[3] || params->w[16], "hla_vgg_forward: conf[3] needs w[16]");
-  HLA_REQUIRE(!(flags & HLA_VGG_DEFER_NORM) || inv_norm, "hla_vgg_forward: HLA_VGG_DEFER_NORM needs inv_norm");
-  HLA_REQUIRE(!(flags & HLA_VGG_FEAT16) || ((dtype == HLA_BF16 || dtype == HLA_F16) && (flags & HLA_VGG_DEFER_NORM) &&
-                                            !(flags & HLA_VGG_SAVE_FOR_BACKWARD) && level == 3),
-              "hla_vgg_forward: HLA_VGG_FEAT16 needs dtype HLA_BF16 / HLA_F16, HLA_VGG_DEFER_NORM, level 3 and no HLA_VGG_SAVE_FOR_BACKWARD");
-  HLA_REQUIRE(first_row8 == 0 || (first_row8 >= 4 && first_row8 < H / 8), "hla_vgg_forward: first_row8 must be 0 or in [4, H/8)");
-  // folded decoder: the narrowest folded map (x15, W/16 wide) is up-sampled 2x into the W/8-wide dec1 geometry, so W/8 must be
-  // even; the 32-px / 8-row conv tiles take partial tiles at the right / bottom edge as for any other width (the partial-sum
-  // slots of the folded tile counts are planned by hla_vgg_workspace_bytes_flags, vgg_layers.h); every row of every map is read
-  HLA_REQUIRE(!(flags & HLA_VGG_FOLD_DECODER) || (W % 16 == 0 && first_row8 == 0 && !(flags & HLA_VGG_FEAT16)),
-              "hla_vgg_forward: HLA_VGG_FOLD_DECODER needs W %% 16 == 0 (folded maps are W/16, W/8, W/4 wide), first_row8 == 0 and no "
-              "HLA_VGG_FEAT16 (got W = %d, first_row8 = %d)", W, first_row8);
-  HLA_REQUIRE(first_col32 >= 0 && (first_col32 == 0 || 128 * first_col32 < W),
-              "hla_vgg_forward_cols: first_col32 must be 0 or leave a column of the map (128 * first_col32 < W; got %d, W = %d)", first_col32, W);
-  HLA_REQUIRE(!col_gate || first_col32 > 0, "hla_vgg_forward_cols: col_gate is the fix-up pass of a forward made with first_col32 > 0");
-  first_col32 = vgg_first_col32(first_col32, level, dtype, flags);
-  if (col_gate && !first_col32) return HLA_OK;      // that forward computed every column: nothing to fix
-  VggPlan pl;
-  vgg_plan(B, H, W, dtype, (flags & HLA_VGG_SAVE_FOR_BACKWARD) != 0, &pl, level == 4, (flags & HLA_VGG_FOLD_DECODER) != 0);
-  if (workspace_bytes < pl.total) {
-    hla_set_error("hla_vgg_forward: workspace %zu < %zu", workspace_bytes, pl.total);
-    return HLA_ERR_WORKSPACE;
-  }
-  // The fix-up pass as one launch: the 16-bit types (first_col32 > 0 here says the rest: level 3, inference, deferred norm, no
-  // confidence heads, no folded decoder).  fp32 and a profiled run, whose records are per layer, keep the ten gated launches.
-  if (col_gate && fixup_one_launch && (dtype == HLA_BF16 || dtype == HLA_F16) && !hla_prof_on()) {
-    if (dtype == HLA_BF16)
-      return vgg_fixup_t<bf16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, inv_norm, (char*)workspace, pl, B, H, W, flags,
-                               first_row8, first_col32, col_gate, (hipStream_t)stream);
-    return vgg_fixup_t<f16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, inv_norm, (char*)workspace, pl, B, H, W, flags,
-                            first_row8, first_col32, col_gate, (hipStream_t)stream);
-  }
-  if (dtype == HLA_BF16)
-    return vgg_forward_t<bf16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                               B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
-  if (dtype == HLA_F16)
-    return vgg_forward_t<f16>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                              B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
-  if (dtype == HLA_F16X3)
-    return vgg_forward_t<split32>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                                  B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
-  return vgg_forward_t<float>(x, x_plane, params, (const char*)packed_weights, dtype, feat, conf, inv_norm, (char*)workspace, pl,
-                              B, H, W, flags, first_row8, first_col32, col_gate, (hipStream_t)stream);
-}
-
 extern "C" int hla_vgg_forward_cols(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
                                     void* const feat[4], float* const conf[4], double* inv_norm, void* workspace,
                                     size_t workspace_bytes, int B, int H, int W, int level, int dtype, int flags,
                                     int first_row8, int first_col32, const int* col_gate, hla_stream_t stream) {
-  return vgg_forward_cols_impl(x, x_plane, params, packed_weights, feat, conf, inv_norm, workspace, workspace_bytes, B, H, W, level, dtype,
-                               flags, first_row8, first_col32, col_gate, true, stream);
+  return vgg_forward_cols_impl(VggFwdCall{x, x_plane, params, (const char*)packed_weights, feat, conf, inv_norm, (char*)workspace,
+                                          workspace_bytes, B, H, W, level, dtype, flags, first_row8, first_col32, col_gate,
+                                          (hipStream_t)stream, {}}, true);
 }
 
 extern "C" int hla_vgg_fixup(const float* x, size_t x_plane, const hla_vgg_params* params, const void* packed_weights,
@@ -509,8 +416,9 @@ extern "C" int hla_vgg_fixup(const float* x, size_t x_plane, const hla_vgg_param
                              int level, int dtype, int flags, int first_row8, int first_col32, const int* col_gate, int one_launch,
                              hla_stream_t stream) {
   HLA_REQUIRE(col_gate, "hla_vgg_fixup: col_gate is required");
-  return vgg_forward_cols_impl(x, x_plane, params, packed_weights, feat, nullptr, inv_norm, workspace, workspace_bytes, B, H, W, level,
-                               dtype, flags, first_row8, first_col32, col_gate, one_launch != 0, stream);
+  return vgg_forward_cols_impl(VggFwdCall{x, x_plane, params, (const char*)packed_weights, feat, nullptr, inv_norm, (char*)workspace,
+                                          workspace_bytes, B, H, W, level, dtype, flags, first_row8, first_col32, col_gate,
+                                          (hipStream_t)stream, {}}, one_launch != 0);
 }
 
 extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level, int dtype, int flags, int* paired_out, hla_stream_t stream) {
@@ -526,24 +434,14 @@ extern "C" int hla_vgg_forward_pair(const hla_vgg_branch br[2], int B, int level
   };
   if (level != 3 || (flags & (HLA_VGG_SAVE_FOR_BACKWARD | HLA_VGG_FOLD_DECODER | HLA_VGG_WANT_CONF)) || !hla_dtype_ok(dtype)) return plain();
   // the argument checks of hla_vgg_forward, per network (a failed one is reported by the plain call)
-  VggPlan pl[2];
+  VggFwdCall c[2];
   for (int k = 0; k < 2; ++k) {
     const hla_vgg_branch& b = br[k];
-    const bool ok = b.x && b.params && b.packed_weights && b.workspace && B > 0 && b.H >= 8 && b.W >= 8 && b.H % 8 == 0 && b.W % 8 == 0 &&
-                    (b.x_plane == 0 || b.x_plane >= (size_t)b.H * b.W) && (size_t)b.H * b.W * 64 * 4 < ((size_t)1 << 31) &&
-                    b.feat[0] && b.feat[1] && b.feat[2] && (!(flags & HLA_VGG_DEFER_NORM) || b.inv_norm) &&
-                    (!(flags & HLA_VGG_FEAT16) || ((dtype == HLA_BF16 || dtype == HLA_F16) && (flags & HLA_VGG_DEFER_NORM))) &&
-                    (b.first_row8 == 0 || (b.first_row8 >= 4 && b.first_row8 < b.H / 8)) &&
-                    b.first_col32 >= 0 && (b.first_col32 == 0 || 128 * b.first_col32 < b.W);
-    if (!ok) return plain();
-    vgg_plan(B, b.H, b.W, dtype, false, &pl[k], false, false);
-    if (b.workspace_bytes < pl[k].total) return plain();
+    c[k] = VggFwdCall{b.x, b.x_plane, b.params, (const char*)b.packed_weights, b.feat, nullptr, b.inv_norm, (char*)b.workspace,
+                      b.workspace_bytes, B, b.H, b.W, level, dtype, flags, b.first_row8, b.first_col32, nullptr, (hipStream_t)stream, {}};
+    if (vgg_forward_check(c[k], true) != HLA_OK) return plain();
   }
-  int rc;
-  if (dtype == HLA_BF16) rc = vgg_forward_pair_t<bf16>(br, pl, B, dtype, flags, (hipStream_t)stream);
-  else if (dtype == HLA_F16) rc = vgg_forward_pair_t<f16>(br, pl, B, dtype, flags, (hipStream_t)stream);
-  else if (dtype == HLA_F16X3) rc = vgg_forward_pair_t<split32>(br, pl, B, dtype, flags, (hipStream_t)stream);
-  else rc = vgg_forward_pair_t<float>(br, pl, B, dtype, flags, (hipStream_t)stream);
+  const int rc = hla_dispatch_dtype(dtype, [&](auto t) { return vgg_forward_pair_t<typename decltype(t)::type>(c); });
   if (rc == HLA_PAIR_FALLBACK) return plain();
   if (rc == HLA_OK && paired_out) *paired_out = 1;
   return rc;

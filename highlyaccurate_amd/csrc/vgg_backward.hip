@@ -313,10 +313,11 @@ __global__ __launch_bounds__(256) void conf_bwd_kernel(const T* __restrict__ act
 // it builds the list of live tiles of every data- and weight-gradient launch.  A launch visits only its live tiles and reads a
 // source as zero outside the part its producer wrote.  Nothing is promised by the caller and nothing is approximated: outside
 // its support a gradient is exactly zero, so no value changes (only the weight-gradient summation order).
-enum { DC_10, DC_9U, DC_9S, DC_8, DC_7U, DC_7S, DC_6, DC_5, DC_4, DC_3, DC_2, DC_1, DC_N };
-enum { DW_10, DW_9, DW_8, DW_7, DW_6, DW_5, DW_4, DW_3, DW_2, DW_1, DW_0, DW_N };
-// gradient maps (their resolution divisor): what a dgrad launch writes / a later launch reads
-enum { M_X21, M_D2A, M_X3P, M_X18, M_D1A, M_X8P, M_X15, M_A12, M_A10, M_X8, M_A5, M_X3, M_A0, M_N };
+// (the maps M_*, the launches DC_* / DW_* and what each reads and writes: vgg_graph.h)
+// What bwd_fan_kernel needs to list the live tiles of one launch: the launch's resolution divisor and tile height, sh = 1 where it
+// runs at twice the resolution of the map whose bands bound it (a pool_sum data gradient, a weight gradient through an unpool),
+// and its descriptor's words 2 and 3 (band offsets of the maps it reads, -1: dense)
+struct FanJob { int div, th, sh, bands, list, desc, d2, d3; };
 struct DynLayout {
   int seed[3];              // per-row {-lo, hi} atomicMax targets of d_feat[l] (memset to 0x80 bytes = "nothing yet")
   int seed_ints;
@@ -327,28 +328,40 @@ struct DynLayout {
   int wg_list[DW_N];
   int used;
   int total;                // ints
+  FanJob fan[DC_N + DW_N];
 };
+// tiles per sample of the dense walk of a data-gradient (8 rows) / weight-gradient (WG_TH rows) launch of layer l
+static inline int bwd_tiles(int l, int H, int W, int th) {
+  const int div = vgg_layer_div(l);
+  return ((H / div + th - 1) / th) * ((W / div + 31) / 32);
+}
 static DynLayout dyn_layout(int H, int W) {
   DynLayout L{};
   int o = 0;
   auto take = [&](int n) { const int r = o; o += (n + 3) & ~3; return r; };
-  const int hs[3] = {H / 8, H / 4, H / 2};
-  for (int l = 0; l < 3; ++l) L.seed[l] = take(2 * hs[l]);
+  for (int l = 0; l < 3; ++l) L.seed[l] = take(2 * (H / kActMaps[kLevelMap[l]].div));
   L.seed_ints = o;
-  const int mdiv[M_N] = {2, 2, 2, 4, 4, 4, 8, 4, 4, 4, 2, 2, 1};
-  for (int m = 0; m < M_N; ++m) L.bands[m] = take(2 * ((H / mdiv[m] + 7) / 8));
-  const int cdiv[DC_N] = {2, 2, 2, 4, 4, 4, 4, 4, 4, 2, 2, 1};        // resolution divisor of each launch
+  for (int m = 0; m < M_N; ++m) L.bands[m] = take(2 * ((H / kGradMaps[m].m.div + 7) / 8));
   for (int i = 0; i < DC_N; ++i) {
     L.conv_desc[i] = take(4);
-    L.conv_list[i] = take(((H / cdiv[i] + 7) / 8) * ((W / cdiv[i] + 31) / 32));
+    L.conv_list[i] = take(bwd_tiles(kDgrad[i].layer, H, W, 8));
   }
-  const int wdiv[DW_N] = {2, 2, 4, 4, 4, 4, 4, 2, 2, 1, 1};
   for (int i = 0; i < DW_N; ++i) {
     L.wg_desc[i] = take(4);
-    L.wg_list[i] = take(((H / wdiv[i] + WG_TH - 1) / WG_TH) * ((W / wdiv[i] + 31) / 32));
+    L.wg_list[i] = take(bwd_tiles(kWgrad[i].layer, H, W, WG_TH));
   }
   L.used = take(4);         // [0] = 1 when the last call trimmed
   L.total = o;
+  // g_x21 (l2bwd_apply writes every element) and the L2 side buffers are dense
+  auto band_of = [&](int m) { return (m < 0 || m >= M_N || m == M_X21) ? -1 : L.bands[m]; };
+  for (int i = 0; i < DC_N; ++i) {
+    const VggDgradLaunch& d = kDgrad[i];
+    L.fan[i] = FanJob{vgg_layer_div(d.layer), 8, d.pool_sum, L.bands[d.out], L.conv_list[i], L.conv_desc[i], band_of(d.src), band_of(d.add)};
+  }
+  for (int i = 0; i < DW_N; ++i) {
+    const VggWgradLaunch& w = kWgrad[i];
+    L.fan[DC_N + i] = FanJob{vgg_layer_div(w.layer), WG_TH, w.unpool >= 0 ? 1 : 0, L.bands[w.g], L.wg_list[i], L.wg_desc[i], band_of(w.g), 0};
+  }
   return L;
 }
 
@@ -414,39 +427,23 @@ static __global__ __launch_bounds__(1024) void bwd_fan_kernel(int* __restrict__ 
   __threadfence_block();
   __syncthreads();
 
-  // ---- live-tile lists: one wave per launch.  entry = (tile row << 16) | tile column
+  // ---- live-tile lists: one wave per launch (L.fan: the data gradients, then the weight gradients).  entry = (tile row << 16) | tile column
   const int lane = t & 63, wv = t >> 6;
-  // dgrad launch i: out map, resolution divisor, pooled (the sum-pool launches run at twice the out map's resolution),
-  // source map (-1: dense, written by l2bwd_apply), add map (-1: none / dense)
-  const int c_out[DC_N] = {M_D2A, M_X18, M_X3P, M_D1A, M_X15, M_X8P, M_A12, M_A10, M_X8, M_A5, M_X3, M_A0};
-  const int c_div[DC_N] = {2, 2, 2, 4, 4, 4, 4, 4, 4, 2, 2, 1};
-  const int c_pool[DC_N] = {0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0};
-  const int c_src[DC_N] = {-1, M_D2A, M_D2A, M_X18, M_D1A, M_D1A, M_X15, M_A12, M_A10, M_X8, M_A5, M_X3};
-  const int c_add[DC_N] = {-1, -1, -1, -1, -1, -1, -1, -1, M_X8P, -1, M_X3P, -1};
-  // wgrad launch i: gradient map, launch resolution divisor, g at half the launch resolution (virtual unpool)
-  const int w_g[DW_N] = {M_X21, M_D2A, M_X18, M_D1A, M_X15, M_A12, M_A10, M_X8, M_A5, M_X3, M_A0};
-  const int w_div[DW_N] = {2, 2, 4, 4, 4, 4, 4, 2, 2, 1, 1};
-  const int w_sh[DW_N] = {0, 0, 0, 0, 1, 0, 0, 1, 0, 1, 0};
   for (int job = wv; job < DC_N + DW_N; job += 16) {
-    const bool isw = job >= DC_N;
-    const int i = isw ? job - DC_N : job;
-    const int div = isw ? w_div[i] : c_div[i], th = isw ? WG_TH : 8;
-    const int Hl = H / div, Wl = W / div, tiles_y = (Hl + th - 1) / th, tiles_x = (Wl + 31) / 32;
-    const int map = isw ? w_g[i] : c_out[i];
-    const int* bd = dyn + L.bands[map];
-    int* list = dyn + (isw ? L.wg_list[i] : L.conv_list[i]);
+    const FanJob& J = L.fan[job];
+    const int Hl = H / J.div, Wl = W / J.div, tiles_y = (Hl + J.th - 1) / J.th, tiles_x = (Wl + 31) / 32;
+    const int* bd = dyn + J.bands;
+    int* list = dyn + J.list;
     int base = 0;
     for (int ty0 = 0; ty0 < tiles_y; ty0 += 64) {
       const int ty = ty0 + lane;
       int tx0 = 0, tx1 = 0;
       if (ty < tiles_y) {
-        // band of the map this tile row belongs to, and the map -> launch column scale
-        const int sh = isw ? w_sh[i] : 0, pool = isw ? 0 : c_pool[i];
-        const int band = pool ? (ty * 8 / 2) >> 3 : ((ty * th) >> sh) >> 3;
+        // band of the map this tile row belongs to; map columns -> launch columns: << sh
+        const int band = ((ty * J.th) >> J.sh) >> 3;
         const int lo = bd[2 * band], hi = bd[2 * band + 1];
-        const int up = pool ? 1 : sh;                        // map columns -> launch columns: << up
-        tx0 = (lo << up) / 32;
-        tx1 = min(((hi << up) + 31) / 32, tiles_x);
+        tx0 = (lo << J.sh) / 32;
+        tx1 = min(((hi << J.sh) + 31) / 32, tiles_x);
       }
       const int cnt = max(tx1 - tx0, 0);
       int inc = cnt;
@@ -457,31 +454,18 @@ static __global__ __launch_bounds__(1024) void bwd_fan_kernel(int* __restrict__ 
       base += __shfl(inc, 63, 64);
     }
     if (lane == 0) {
-      int* d = dyn + (isw ? L.wg_desc[i] : L.conv_desc[i]);
-      d[0] = base;
-      d[1] = isw ? L.wg_list[i] : L.conv_list[i];
-      if (isw) {
-        d[2] = map == M_X21 ? -1 : L.bands[map];             // g_x21 is dense (l2bwd_apply writes every element)
-        d[3] = 0;
-      } else {
-        d[2] = c_src[i] < 0 ? -1 : L.bands[c_src[i]];
-        d[3] = c_add[i] < 0 ? -1 : L.bands[c_add[i]];
-      }
+      int* d = dyn + J.desc;
+      d[0] = base; d[1] = J.list; d[2] = J.d2; d[3] = J.d3;
     }
   }
 }
 
 struct BwdPlan {
-  size_t g_x21, g_d2a, g_x18, l2_18, g_d1a, g_x15, l2_15, g_a12, g_a10, g_x8, g_x8p, g_a5, g_x3, g_x3p, g_a0;
+  size_t g[M_ALL];                              // the gradient maps (vgg_graph.h); the level-4 ones 0 at level 3
   size_t dot, part, bpart, dz, dyn;
   size_t gamax;                                 // split mode: [kGradAmaxSlots][B] per-sample max |gradient map| (fp32 bits)
-  size_t g_x24, g_d3a, g_x2p, g_c2, l2_21;      // level 4 only
   size_t total;
 };
-
-// split mode: one per-sample maximum per gradient map that a data- or weight-gradient launch reads
-enum { GA_X21 = 0, GA_D2A, GA_X18, GA_X3P, GA_D1A, GA_X15, GA_X8P, GA_A12, GA_A10, GA_X8, GA_A5, GA_X3, GA_A0, GA_X24, GA_D3A,
-       GA_X2P, GA_C2, kGradAmaxSlots = 24 };
 
 // per device (bit = device id; ids >= 64 never set a bit and take the fallback kernels): the wave-specialised weight-gradient
 // kernel's LDS request was accepted.  One word per kernel -- wgrad_split_ws_kernel asks for 115 KB, wgrad_ws_kernel<T> for 96 KB:
@@ -502,22 +486,13 @@ static void bwd_plan(int B, int H, int W, int dtype, BwdPlan* p, bool level4 = f
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += hla_align_up(bytes, 256); return r; };
   const size_t P = (size_t)B * H * W;
-  p->g_x21 = take(P / 4 * 64 * es);  p->g_d2a = take(P / 4 * 64 * es);
-  p->g_x18 = take(P / 16 * 128 * es); p->l2_18 = take(P / 16 * 128 * es); p->g_d1a = take(P / 16 * 128 * es);
-  p->g_x15 = take(P / 64 * 256 * es); p->l2_15 = take(P / 64 * 256 * es);
-  p->g_a12 = take(P / 16 * 256 * es); p->g_a10 = take(P / 16 * 256 * es);
-  p->g_x8 = take(P / 16 * 128 * es);  p->g_x8p = take(P / 16 * 128 * es);
-  p->g_a5 = take(P / 4 * 128 * es);
-  p->g_x3 = take(P / 4 * 64 * es);    p->g_x3p = take(P / 4 * 64 * es);
-  p->g_a0 = take(P * 64 * es);
+  *p = BwdPlan{};
+  for (int m : kBwdPlanOrder) p->g[m] = take((size_t)B * vgg_map_elems(kGradMaps[m].m, H, W) * es);
   p->dot = take((size_t)B * 64 * sizeof(double));
   size_t maxpart = (size_t)1024 * 2 * 64 * 32 * 4;      // conv0
-  const int hs[11] = {1, 1, 2, 2, 4, 4, 4, 4, 4, 2, 2};  // resolution divisor of each layer's output
   for (int l = 1; l < (level4 ? kAllLayers : kPackedLayers); ++l) {
-    const int div = l < 11 ? hs[l] : 1;
-    const int h = H / div, w = W / div;
-    int ntile = B * ((h + WG_TH - 1) / WG_TH) * ((w + 31) / 32);
-    if (fold && l >= 7) ntile = B * ((2 * h + WG_TH - 1) / WG_TH) * ((w / 2 + 31) / 32);      // the decoder on [2h, w/2]
+    const VggHW g = vgg_layer_hw(l, H, W, fold);
+    const int ntile = B * ((g.h + WG_TH - 1) / WG_TH) * ((g.w + 31) / 32);
     const size_t sz = (size_t)wgrad_ksplit(kLayers[l].cout, kLayers[l].cin, ntile) * kLayers[l].cout * kLayers[l].cin * 9 * 4;
     if (sz > maxpart) maxpart = sz;
   }
@@ -526,58 +501,63 @@ static void bwd_plan(int B, int H, int W, int dtype, BwdPlan* p, bool level4 = f
   p->dz = take((level4 ? P : P / 4) * sizeof(float));
   p->dyn = take((size_t)dyn_layout(H, W).total * sizeof(int));
   p->gamax = take((size_t)kGradAmaxSlots * B * sizeof(unsigned));
-  p->g_x24 = p->g_d3a = p->g_x2p = p->g_c2 = p->l2_21 = 0;
-  if (level4) {
-    p->g_x24 = take(P * 64 * es); p->g_d3a = take(P * 64 * es); p->g_x2p = take(P * 64 * es); p->g_c2 = take(P * 64 * es);
-    p->l2_21 = take(P / 4 * 64 * es);
-  }
+  if (level4)
+    for (int m : kBwdPlanOrder4) p->g[m] = take((size_t)B * vgg_map_elems(kGradMaps[m].m, H, W) * es);
   p->total = o;
 }
 
 template <typename T>
 void vgg_pack_all_T(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st) {
+  std::conditional_t<Prec<T>::SPLIT, SplitPackTable, PackTable> tb{};
+  int n = 0;
+  for (int l = 1; l < kAllLayers; ++l) {          // conv0 needs no data gradient
+    if (l >= kPackedLayers && !prm->w[l]) continue;
+    // transposed conv: Cout' = cin, Cin' = cout (pack mode 2 transposes and flips the taps)
+    tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cin; tb.cin[n] = kLayers[l].cout;
+    tb.first[n] = 2;
+    if constexpr (Prec<T>::SPLIT) tb.slot[n] = l;
+    ++n;
+  }
   if constexpr (Prec<T>::SPLIT) {
     // split mode: (hi, lo) fp16 fragments of s_w * w, transposed; the tail behind the last layer holds the per-layer scales
     // (float[16]) and 32 scratch words for the |w| maxima, as in the forward packing (vgg.hip)
     float* tail = (float*)(packed + packed_offset(kAllLayers, dtype));
     unsigned* scratch = (unsigned*)tail + 32;
     (void)hipMemsetAsync(tail, 0, kPackTailBytes, st);
-    SplitPackTable tb{};
-    int n = 0;
-    for (int l = 1; l < kAllLayers; ++l) {          // conv0 needs no data gradient
-      if (l >= kPackedLayers && !prm->w[l]) continue;
-      // transposed conv: Cout' = cin, Cin' = cout (pack mode 2 transposes and flips the taps)
-      tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cin; tb.cin[n] = kLayers[l].cout;
-      tb.first[n] = 2; tb.slot[n] = l;
-      ++n;
-    }
     hipLaunchKernelGGL(absmax_multi_kernel, dim3(64, n), dim3(256), 0, st, tb, scratch, (unsigned*)nullptr);
     hipLaunchKernelGGL(pack_weights_split_multi_kernel, dim3(256, n), dim3(256), 0, st, tb, packed, (const unsigned*)scratch, tail);
-  } else {
-    PackTable tb{};
-    int n = 0;
-    for (int l = 1; l < kAllLayers; ++l) {          // conv0 needs no data gradient
-      if (l >= kPackedLayers && !prm->w[l]) continue;
-      // transposed conv: Cout' = cin, Cin' = cout
-      tb.w[n] = prm->w[l]; tb.off[n] = packed_offset(l, dtype); tb.cout[n] = kLayers[l].cin; tb.cin[n] = kLayers[l].cout;
-      tb.first[n] = 2;
-      ++n;
-    }
+  } else
     hipLaunchKernelGGL((pack_weights_multi_kernel<T>), dim3(256, n), dim3(256), 0, st, tb, packed);
-  }
 }
 
+// One backward call: what hla_vgg_backward was given, checked, with its plan
+struct VggBwdCall {
+  const float* x; size_t x_plane; const hla_vgg_params* prm; const char* packedT; const char* fw;
+  const float* const* feat; const double* inv_norm; const float* const* d_feat; const float* const* conf; const float* const* d_conf;
+  const hla_vgg_grads* gr; char* bw;
+  int B, H, W, level, dtype, flags, first_row8;
+  hipStream_t st;
+  BwdPlan bp;
+};
+
 template <typename T>
-int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packedT, int dtype, const char* fw,
-                          const float* const feat[4], const double* inv_norm, const float* const d_feat[4],
-                          const float* const conf[4], const float* const d_conf[4], const hla_vgg_grads* gr, char* bw, const BwdPlan& bp, int B, int H, int W, int flags, int first_row8, hipStream_t st) {
-  const bool level4 = bp.g_x24 != 0;
+int vgg_backward_t(const VggBwdCall& c) {
+  const char *packedT = c.packedT, *fw = c.fw;
+  const float* const *conf = c.conf, *const *d_conf = c.d_conf;
+  const hla_vgg_grads* gr = c.gr;
+  char* bw = c.bw;
+  const BwdPlan& bp = c.bp;
+  const int B = c.B, H = c.H, W = c.W, flags = c.flags;
+  hipStream_t st = c.st;
+  const bool level4 = c.level == 4;
   // conv0's weight gradient inside the epilogue of conv2's data gradient (conv_epilogue_wg0); the two-phase flag keeps the
   // stored map + wgrad0_kernel (A/B and tests; level 4 reads conv2's gradient from a materialised map anyway)
   const bool fuse0 = !level4 && !(flags & (HLA_VGG_BWD_WGRAD_TWO_PHASE | HLA_VGG_BWD_WGRAD0_UNFUSED));
   const int NL = level4 ? 4 : 3;
+  // HLA_VGG_BWD_FOLD_DECODER: the decoder's launches run on the folded geometry [2h, w/2] (vgg_layer_hw; same buffers)
+  const bool fold = (flags & HLA_VGG_BWD_FOLD_DECODER) != 0;
   VggPlan fp;
-  vgg_plan(B, H, W, dtype, true, &fp, level4, (flags & HLA_VGG_BWD_FOLD_DECODER) != 0);
+  vgg_plan(B, H, W, c.dtype, true, &fp, level4, fold);
   constexpr int KC = SB / (int)sizeof(T);
   constexpr bool SPLIT = Prec<T>::SPLIT;
   using ET = std::conditional_t<SPLIT, float, T>;      // element type of the stored maps (split mode: fp32): the elementwise kernels
@@ -603,8 +583,9 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
       return hipFuncSetAttribute((const void*)wgrad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, wg_lds_bytes<T>());
     }
   }));
-  auto F = [&](size_t off) { return (const void*)(fw + off); };
-  auto G = [&](size_t off) { return (void*)(bw + off); };
+  auto F = [&](int m) { return m >= 0 ? (const void*)(fw + fp.act[m]) : (const void*)nullptr; };      // forward activation
+  auto G = [&](int m) { return m >= 0 ? (void*)(bw + bp.g[m]) : (void*)nullptr; };                    // gradient map
+  auto IDX = [&](int i) { return i >= 0 ? (const unsigned char*)(fw + fp.idx[i]) : (const unsigned char*)nullptr; };
   // split mode: per-sample maxima of the forward's activations (recorded by its epilogues) and of this pass's gradient maps
   // (recorded by the data-gradient epilogues, or by absmax_map_kernel for the maps no convolution produced); the transposed
   // packing's per-layer weight scales sit behind the last packed layer
@@ -612,79 +593,49 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
   unsigned* gam = (unsigned*)(bw + bp.gamax);
   auto FA = [&](int slot) { return (SPLIT && slot >= 0) ? fam + (size_t)slot * B : (const unsigned*)nullptr; };
   auto GA = [&](int slot) { return (SPLIT && slot >= 0) ? gam + (size_t)slot * B : (unsigned*)nullptr; };
-  const float* wtailT = (const float*)(packedT + packed_offset(kAllLayers, dtype));
+  const float* wtailT = (const float*)(packedT + packed_offset(kAllLayers, c.dtype));
   if (SPLIT) HLA_CHECK_HIP(hipMemsetAsync(gam, 0, (size_t)kGradAmaxSlots * B * sizeof(unsigned), st));
 
-  // ---- L2_norm backward of the three returned maps
-  const size_t per[4] = {(size_t)(H / 8) * (W / 8) * 256, (size_t)(H / 4) * (W / 4) * 128, (size_t)(H / 2) * (W / 2) * 64,
-                         (size_t)H * W * 64};
+  // ---- L2_norm backward of the returned maps
   // at level 4 x21 also feeds conv_dec3, so its L2-norm gradient goes to a side buffer and is merged by that dgrad's epilogue
-  void* l2out[4] = {G(bp.l2_15), G(bp.l2_18), level4 ? G(bp.l2_21) : G(bp.g_x21), G(bp.g_x24)};
+  const int l2map[4] = {M_L2_15, M_L2_18, level4 ? M_L2_21 : M_X21, M_X24};
   // data-dependent trimming (see bwd_fan_kernel): needs exact zeros outside the support, i.e. the one-pass L2 backward, and no
   // confidence-head gradient (which is dense).  Not combined with the caller's static first rows (the ground branch: every
-  // column of its bottom half carries gradient, so there is nothing to gain).
-  // HLA_VGG_BWD_FOLD_DECODER: the decoder's launches run on the folded geometry [2h, w/2] (dH, dW below; same buffers).  The
-  // trimming tables describe the unfolded layer graph, so that mode takes the dense walk.
-  const bool fold = (flags & HLA_VGG_BWD_FOLD_DECODER) != 0;
-  auto dH = [&](int d) { return fold ? 2 * (H / d) : H / d; };
-  auto dW = [&](int d) { return fold ? (W / d) / 2 : W / d; };
-  const bool dynamic = !level4 && (flags & HLA_VGG_BWD_SCALE_INVARIANT) && !(flags & HLA_VGG_BWD_DENSE) && !(conf && d_conf) &&
-                       first_row8 == 0 && H <= 1024 && !fold;
+  // column of its bottom half carries gradient, so there is nothing to gain).  The trimming tables describe the unfolded layer
+  // graph, so the folded decoder takes the dense walk.
+  const bool with_conf = conf && d_conf;
+  const bool dynamic = !level4 && (flags & HLA_VGG_BWD_SCALE_INVARIANT) && !(flags & HLA_VGG_BWD_DENSE) && !with_conf &&
+                       c.first_row8 == 0 && H <= 1024 && !fold;
   const DynLayout dl = dyn_layout(H, W);
   int* dynp = (int*)(bw + bp.dyn);
   if (dynamic) HLA_CHECK_HIP(hipMemsetAsync(dynp, 0x80, (size_t)dl.seed_ints * sizeof(int), st));
   HLA_CHECK_HIP(hipMemsetAsync(dynp + dl.used, dynamic ? 1 : 0, sizeof(int), st));
-  // Row ranges.  first_row8 = f > 0 is the caller's promise that d_feat[0..2] are zero above rows f / 2f / 4f (the LM loop
-  // only ever reads rows h_l/2.. of the ground maps, so that is where its gradient lives).  The gradient of every activation
-  // is then exactly zero above a first row that follows from the layer graph -- a 3x3 conv widens the support by one row, a 2x
-  // upsample / 2x2 pool halves / doubles it -- and every launch below starts at that row (ConvArgs::row_begin, even where a
-  // pool is involved), reading its sources as zero above THEIR first row (src_row_lo / add_row_lo: those rows are never
-  // written).  With confidence heads (d_conf) the support of the three raw-map gradients starts one row higher.
-  // n_* : first row of a gradient map in its own resolution; all zero (= no trimming) when f == 0.
-  const int f = (level4 || !(flags & HLA_VGG_BWD_SCALE_INVARIANT)) ? 0 : first_row8;   // (the two-pass L2 backward leaves
-                                                                                       //  rounding noise above the support)
-  const int wc = (conf && d_conf) ? 1 : 0;
-  auto ev = [](int v) { return v < 0 ? 0 : (v & ~1); };
-  auto nn = [](int v) { return v < 0 ? 0 : v; };
-  const int n_x21 = f ? 4 * f - wc : 0;                 // H/2
-  const int n_d2a = nn(n_x21 - 1);                      // H/2
-  const int rb_up18 = ev(n_d2a - 1);                    // H/2 rows of the pool_sum launch that produces g_x18
-  const int n_x18 = rb_up18 / 2;                        // H/4   (<= 2f - wc: covers x18's own L2 / conf gradient)
-  const int n_x3p = nn(n_d2a - 1);                      // H/2
-  const int n_d1a = nn(n_x18 - 1);                      // H/4
-  const int rb_up15 = ev(n_d1a - 1);
-  const int n_x15 = rb_up15 / 2;                        // H/8
-  const int n_x8p = nn(n_d1a - 1);                      // H/4
-  const int n_a12 = nn(2 * n_x15 - 1);                  // H/4
-  const int n_a10 = nn(n_a12 - 1);
-  const int n_x8 = nn(n_a10 - 1);                       // H/4
-  const int n_a5 = nn(2 * n_x8 - 1);                    // H/2
-  const int n_x3 = nn(n_a5 - 1);                        // H/2
-  const int n_a0 = nn(2 * n_x3 - 1);                    // H
-  // ... and the L2-norm backward below starts at n_x15 / n_x18 / n_x21 as well: the rows of d_feat[l] above f * 2^l - 2 are neither
-  // read nor written (the caller need not even zero them)
-  const int l2_row0[4] = {n_x15, n_x18, n_x21, 0};
+  // the first row of every gradient map and launch (all zero = no trimming when first_row8 == 0)
+  const VggBwdRows rows = vgg_bwd_rows(c.first_row8, level4, (flags & HLA_VGG_BWD_SCALE_INVARIANT) != 0, with_conf);
+  const int l2_row0[4] = {rows.n[M_X15], rows.n[M_X18], rows.n[M_X21], 0};
+  size_t per[4];
+  for (int l = 0; l < 4; ++l) per[l] = vgg_map_elems(kActMaps[kLevelMap[l]], H, W);
   bool l2_recorded_amax = false;
   for (int l = 0; l < NL; ++l) {
+    const VggMapDef& m = kActMaps[kLevelMap[l]];
     int nblk = (int)(per[l] / 4 / 256 / 8);
     nblk = nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
     double* part = (double*)(bw + bp.dot);
     if (flags & HLA_VGG_BWD_SCALE_INVARIANT) {
-      const int Cl[4] = {256, 128, 64, 64};
-      const size_t skip = (size_t)l2_row0[l] * (W >> (3 - l)) * Cl[l];
+      const size_t skip = (size_t)l2_row0[l] * (W / m.div) * m.C;
       hla_prof_begin(K_ELEMWISE, 0, (double)B * (per[l] - skip) * (4 + sizeof(T)), st);
       // split mode: the finest map's gradient (g_x21 / g_x24) is READ by a convolution, which needs its per-sample maximum; the
       // pass that writes it records it, unless the confidence heads still add into it (then absmax_map below does)
-      unsigned* am = (SPLIT && l == NL - 1 && !(conf && d_conf)) ? GA(level4 ? GA_X24 : GA_X21) : (unsigned*)nullptr;
+      unsigned* am = (SPLIT && l == NL - 1 && !with_conf) ? GA(level4 ? GA_X24 : GA_X21) : (unsigned*)nullptr;
       l2_recorded_amax = l2_recorded_amax || am != nullptr;
-      hipLaunchKernelGGL((l2bwd_apply_kernel<ET, true>), dim3(B * nblk), dim3(256), 0, st, feat[l], d_feat[l], part,
-                         inv_norm + (size_t)l * B, (ET*)l2out[l], per[l], nblk, dynamic ? dynp + dl.seed[l] : (int*)nullptr,
-                         Cl[l], W >> (3 - l), skip, am);
+      hipLaunchKernelGGL((l2bwd_apply_kernel<ET, true>), dim3(B * nblk), dim3(256), 0, st, c.feat[l], c.d_feat[l], part,
+                         c.inv_norm + (size_t)l * B, (ET*)G(l2map[l]), per[l], nblk, dynamic ? dynp + dl.seed[l] : (int*)nullptr,
+                         m.C, W / m.div, skip, am);
     } else {
       hla_prof_begin(K_ELEMWISE, 0, (double)B * per[l] * (16 + sizeof(T)), st);
-      hipLaunchKernelGGL(l2bwd_dot_kernel, dim3(B * nblk), dim3(256), 0, st, feat[l], d_feat[l], part, per[l], nblk);
-      hipLaunchKernelGGL((l2bwd_apply_kernel<ET, false>), dim3(B * nblk), dim3(256), 0, st, feat[l], d_feat[l], part,
-                         inv_norm + (size_t)l * B, (ET*)l2out[l], per[l], nblk);
+      hipLaunchKernelGGL(l2bwd_dot_kernel, dim3(B * nblk), dim3(256), 0, st, c.feat[l], c.d_feat[l], part, per[l], nblk);
+      hipLaunchKernelGGL((l2bwd_apply_kernel<ET, false>), dim3(B * nblk), dim3(256), 0, st, c.feat[l], c.d_feat[l], part,
+                         c.inv_norm + (size_t)l * B, (ET*)G(l2map[l]), per[l], nblk);
     }
     hla_prof_end(st);
   }
@@ -692,22 +643,22 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
   if (dynamic) hipLaunchKernelGGL(bwd_fan_kernel, dim3(1), dim3(1024), 0, st, dynp, dl, H, W);
 
   // ---- confidence heads (only the ground branch with using_weight=1 ever has d_conf): adds into the raw-map gradients
-  if (conf && d_conf) {
-    const ET* acts[4] = {(const ET*)(fw + fp.x15r), (const ET*)(fw + fp.x18r), (const ET*)(fw + fp.x21r), (const ET*)(fw + fp.x24r)};
-    const int Cs[4] = {256, 128, 64, 64}, hs[4] = {H / 8, dH(4), dH(2), dH(1)}, wsz[4] = {W / 8, dW(4), dW(2), dW(1)};
+  if (with_conf) {
     for (int l = 0; l < NL; ++l) {
       if (!d_conf[l]) continue;
+      const VggMapDef& m = kActMaps[kLevelMap[l]];
+      const VggHW g = vgg_map_hw(m, H, W, fold);
       constexpr int EPL = 16 / (int)sizeof(ET);
-      const int ppb = 256 / (Cs[l] / EPL);
-      const size_t npix = (size_t)B * hs[l] * wsz[l];
+      const int ppb = 256 / (m.C / EPL);
+      const size_t npix = (size_t)B * g.h * g.w;
       const int grid = (int)((npix + ppb - 1) / ppb < 1024 ? (npix + ppb - 1) / ppb : 1024);
       float* dz = (float*)(bw + bp.dz);
-      hla_prof_begin(K_ELEMWISE, 4.0 * 9 * Cs[l] * (double)npix, (double)npix * (3 * Cs[l] * sizeof(ET) + 12), st);
+      hla_prof_begin(K_ELEMWISE, 4.0 * 9 * m.C * (double)npix, (double)npix * (3 * m.C * sizeof(ET) + 12), st);
       hipLaunchKernelGGL(conf_dz_kernel, dim3((unsigned)((npix + 255) / 256 < 2048 ? (npix + 255) / 256 : 2048)), dim3(256), 0, st,
                          conf[l], d_conf[l], dz, npix);
-      hipLaunchKernelGGL((conf_bwd_kernel<ET>), dim3(grid), dim3(256), 4 * 9 * Cs[l] * sizeof(float), st, acts[l],
-                         prm->w[13 + l], (const float*)dz, (ET*)l2out[l], (float*)(bw + bp.part), B, hs[l], wsz[l], Cs[l]);
-      const size_t n = (size_t)9 * Cs[l];
+      hipLaunchKernelGGL((conf_bwd_kernel<ET>), dim3(grid), dim3(256), 4 * 9 * m.C * sizeof(float), st, (const ET*)F(kLevelMap[l]),
+                         c.prm->w[13 + l], (const float*)dz, (ET*)G(l2map[l]), (float*)(bw + bp.part), B, g.h, g.w, m.C);
+      const size_t n = (size_t)9 * m.C;
       hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, st, (const float*)(bw + bp.part),
                          gr->dw[13 + l], n, grid, (int)n, 1, 1);
       hla_prof_end(st);
@@ -716,48 +667,51 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
 
   // split mode: the scale of the two gradient maps that convolutions READ but no convolution wrote (at level 3: g_x21; l2_18 /
   // l2_15 are only ever added in an epilogue, in fp32)
-  auto absmax_map = [&](const void* map, size_t per_sample, size_t skip, int slot) {
+  auto absmax_map = [&](int m, size_t skip) {
+    const size_t per_sample = vgg_map_elems(kGradMaps[m].m, H, W);
     int nblk = (int)(per_sample / 4 / 256 / 8);
     nblk = nblk < 1 ? 1 : (nblk > 64 ? 64 : nblk);
     hla_prof_begin(K_ELEMWISE, 0, (double)B * (per_sample - skip) * 4, st);
-    hipLaunchKernelGGL(absmax_map_kernel, dim3(B * nblk), dim3(256), 0, st, (const float*)map, per_sample, skip, nblk, GA(slot));
+    hipLaunchKernelGGL(absmax_map_kernel, dim3(B * nblk), dim3(256), 0, st, (const float*)G(m), per_sample, skip, nblk, GA(kGradMaps[m].ga));
     hla_prof_end(st);
   };
   if (SPLIT && !l2_recorded_amax) {
-    if (level4) absmax_map(G(bp.g_x24), per[3], 0, GA_X24);
-    else absmax_map(G(bp.g_x21), per[2], (size_t)l2_row0[2] * (W / 2) * 64, GA_X21);
+    if (level4) absmax_map(M_X24, 0);
+    else absmax_map(M_X21, (size_t)rows.n[M_X21] * (W / kGradMaps[M_X21].m.div) * kGradMaps[M_X21].m.C);
   }
 
-  // ---- helpers
-  // data gradient of layer l restricted to its input channels [c0, c0+n): a forward conv on the transposed weights
-  // (ga_src / ga_out, split mode: the amax slots of the gradient map it reads and of the one it writes)
+  // ---- the launches of the walk, by their row in kDgrad / kWgrad (vgg_graph.h); rows below DC_N / DW_N have a live-tile list
   bool launch_ok = true;
-  auto dgrad = [&](int l, int c0, int n, const void* gsrc, const unsigned char* unpool, int Hout, int Wout, void* out,
-                   const void* mask, const void* add, bool pool_sum, int row_begin = 0, int src_lo = 0, int add_lo = 0, int dc = -1,
-                   int ga_src = -1, int ga_out = -1, bool fuse_wg0 = false) {
+  auto dgrad = [&](int i) {
+    const VggDgradLaunch& d = kDgrad[i];
+    const bool fuse_wg0 = i == DC_1 && fuse0;
+    const VggHW g = vgg_layer_hw(d.layer, H, W, fold);
     ConvArgs a{};
-    if (fuse_wg0) {      // conv2's data gradient contracted into conv0's weight gradient in its epilogue; `out` receives the partials
-      a.wg0_x = x; a.wg0_x_plane = x_plane ? x_plane : (size_t)H * W; a.wg0_part = (float*)out;
+    if (fuse_wg0) {      // conv2's data gradient contracted into conv0's weight gradient in its epilogue; g_a0 receives the partials
+      a.wg0_x = c.x; a.wg0_x_plane = c.x_plane ? c.x_plane : (size_t)H * W; a.wg0_part = (float*)G(d.out);
     }
-    a.amax1 = GA(ga_src); a.amax_out = GA(ga_out); a.wscale = SPLIT ? wtailT + l : nullptr;
-    a.dyn = (dynamic && dc >= 0) ? dynp : nullptr; a.dyn_desc = dc >= 0 ? dl.conv_desc[dc] : 0;
-    a.src1 = gsrc; a.C1 = kLayers[l].cout; a.unpool_idx = unpool;
-    const int nstage = kLayers[l].cout / KC;
-    a.wpk = (const uint4*)(packedT + packed_offset(l, dtype)) + (size_t)(c0 / 32) * nstage * 18 * 64;
-    a.out_act = fuse_wg0 ? nullptr : out; a.mask_act = mask; a.add_src = add; a.pool_sum = pool_sum ? 1 : 0;
-    a.B = B; a.H = Hout; a.W = Wout; a.Cout = n; a.relu_act = 0;
-    a.row_begin = row_begin > 0 ? row_begin : 0; a.src_row_lo = src_lo > 0 ? src_lo : 0; a.add_row_lo = add_lo > 0 ? add_lo : 0;
-    if (!launch_conv<T, true>(st, a, pool_sum)) launch_ok = false;
+    a.amax1 = GA(kGradMaps[d.src].ga); a.amax_out = GA(fuse_wg0 ? -1 : kGradMaps[d.out].ga); a.wscale = SPLIT ? wtailT + d.layer : nullptr;
+    if (i < DC_N) {
+      a.dyn = dynamic ? dynp : nullptr; a.dyn_desc = dl.conv_desc[i];
+      a.row_begin = rows.dc_row[i]; a.src_row_lo = rows.dc_src_lo[i]; a.add_row_lo = rows.dc_add_lo[i];
+    }
+    a.src1 = G(d.src); a.C1 = kLayers[d.layer].cout; a.unpool_idx = IDX(d.unpool);
+    const int nstage = kLayers[d.layer].cout / KC;
+    a.wpk = (const uint4*)(packedT + packed_offset(d.layer, c.dtype)) + (size_t)(d.c0 / 32) * nstage * 18 * 64;
+    a.out_act = fuse_wg0 ? nullptr : G(d.out); a.mask_act = F(d.mask); a.add_src = G(d.add); a.pool_sum = d.pool_sum;
+    a.B = B; a.H = g.h; a.W = g.w; a.Cout = kGradMaps[d.out].m.C; a.relu_act = 0;
+    if (!launch_conv<T, true>(st, a, d.pool_sum != 0)) launch_ok = false;
   };
-  // (fa1 / fa2 / ga, split mode: the amax slots of its input activation(s) and of the gradient map)
-  auto wgrad = [&](int l, const void* x1, int C1, const void* x2, int C2, int up1, const void* g, const unsigned char* unpool,
-                   int Hout, int Wout, int row_begin = 0, int dw = -1, int fa1 = -1, int fa2 = -1, int ga = -1) {
+  auto wgrad = [&](int i) {
+    const VggWgradLaunch& wl = kWgrad[i];
+    const int l = wl.layer;
+    const VggHW g = vgg_layer_hw(l, H, W, fold);
     WgradArgs a{};
-    a.dyn = (dynamic && dw >= 0) ? dynp : nullptr; a.dyn_desc = dw >= 0 ? dl.wg_desc[dw] : 0;
-    a.x1 = x1; a.x2 = x2; a.C1 = C1; a.C2 = C2; a.up1 = up1; a.g = g; a.g_unpool = unpool;
-    a.B = B; a.H = Hout; a.W = Wout; a.Cout = kLayers[l].cout; a.Cin = kLayers[l].cin;
-    a.row_begin = row_begin > 0 ? row_begin : 0;
-    a.tiles_x = (Wout + 31) / 32; a.tiles_y = (Hout - a.row_begin + WG_TH - 1) / WG_TH; a.ntile = B * a.tiles_x * a.tiles_y;
+    if (i < DW_N) { a.dyn = dynamic ? dynp : nullptr; a.dyn_desc = dl.wg_desc[i]; a.row_begin = rows.dw_row[i]; }
+    a.x1 = F(wl.x1); a.x2 = F(wl.x2); a.C1 = kActMaps[wl.x1].C; a.C2 = wl.x2 >= 0 ? kActMaps[wl.x2].C : 0; a.up1 = wl.x2 >= 0 ? 1 : 0;
+    a.g = G(wl.g); a.g_unpool = IDX(wl.unpool);
+    a.B = B; a.H = g.h; a.W = g.w; a.Cout = kLayers[l].cout; a.Cin = kLayers[l].cin;
+    a.tiles_x = (g.w + 31) / 32; a.tiles_y = (g.h - a.row_begin + WG_TH - 1) / WG_TH; a.ntile = B * a.tiles_x * a.tiles_y;
     // wave-specialised kernels (split and 16-bit, unless the device refused their LDS or the caller asks for the two-phase ones):
     // one 8-wave workgroup per CU -> 256 workgroups are one resident generation; two-phase: two 4-wave workgroups -> 512
     bool ws = false;
@@ -769,12 +723,12 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
     a.KS = wgrad_ksplit(a.Cout, a.Cin, a.ntile, ws ? 256 : 512);
     a.part = (float*)(bw + bp.part);
     a.bpart = (kLayers[l].has_bias && gr->db[l]) ? (float*)(bw + bp.bpart) : nullptr;
-    const double P = (double)B * (Hout - a.row_begin) * Wout;
+    const double P = (double)B * (g.h - a.row_begin) * g.w;
     hla_prof_begin_dyn(K_WGRAD, 2.0 * 9 * a.Cin * a.Cout * P, P * (a.Cin + a.Cout) * sizeof(T), st,
                        a.dyn ? a.dyn + a.dyn_desc : nullptr, a.tiles_x * a.tiles_y);
     const dim3 grid(a.KS, a.Cin / 64, a.Cout / 64), block(ws ? 512 : 256);
-    if constexpr (SPLIT) {
-      const WgradSplitExtra ex{FA(fa1), FA(fa2), GA(ga)};
+    if constexpr (SPLIT) {      // (the amax slots of its input activation(s) and of the gradient map)
+      const WgradSplitExtra ex{FA(wl.x1), FA(wl.x2), GA(kGradMaps[wl.g].ga)};
       if (ws) hipLaunchKernelGGL(wgrad_split_ws_kernel<f16>, grid, block, wgs_ws_lds_bytes(), st, a, ex);
       else hipLaunchKernelGGL(wgrad_split_kernel<f16>, grid, block, wgs_lds_bytes(), st, a, ex);
     } else {
@@ -792,74 +746,39 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
     if (a.bpart)
       hipLaunchKernelGGL(reduce_partials_kernel, dim3((a.Cout + 15) / 16), dim3(256), 0, st, a.bpart, gr->db[l], (size_t)a.Cout, a.KS, a.Cout, 1, 1);
   };
-  const unsigned char* idx3 = (const unsigned char*)(fw + fp.idx3);
-  const unsigned char* idx8 = (const unsigned char*)(fw + fp.idx8);
-  const unsigned char* idx15 = (const unsigned char*)(fw + fp.idx15);
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
-  const int Hd1 = dH(1), Wd1 = dW(1), Hd2 = dH(2), Wd2 = dW(2), Hd4 = dH(4), Wd4 = dW(4);      // the decoder's geometry
-
-  // ---- decoder 3 (VGG.py:153-155, level 4 only; zero-padded to 64 channels, the host slices the weight gradients)
-  if (level4) {
-    dgrad(12, 0, 64, G(bp.g_x24), nullptr, Hd1, Wd1, G(bp.g_d3a), F(fp.d3a), nullptr, false, 0, 0, 0, -1, GA_X24, GA_D3A);
-    wgrad(12, F(fp.d3a), 64, nullptr, 0, 0, G(bp.g_x24), nullptr, Hd1, Wd1, 0, -1, AM_D3A, -1, GA_X24);
-    dgrad(11, 0, 64, G(bp.g_d3a), nullptr, Hd1, Wd1, G(bp.g_x21), F(fp.x21r), G(bp.l2_21), true, 0, 0, 0, -1, GA_D3A, GA_X21);     // up(x21) branch
-    dgrad(11, 64, 64, G(bp.g_d3a), nullptr, Hd1, Wd1, G(bp.g_x2p), F(fp.x2r), nullptr, false, 0, 0, 0, -1, GA_D3A, GA_X2P);         // x2 skip branch
-    wgrad(11, F(fp.x21r), 64, F(fp.x2r), 64, 1, G(bp.g_d3a), nullptr, Hd1, Wd1, 0, -1, AM_X21, AM_X2, GA_D3A);
+  // ---- the walk, from the last layer down: a layer's data gradient(s), then its weight gradient.  (Level 4: conv_dec3 is
+  // zero-padded to 64 channels, the host slices its weight gradients.)
+  for (int l = (level4 ? kAllLayers : kPackedLayers) - 1; l >= 1; --l) {
+    if (l == 1 && level4) {      // the conv2 output also fed conv_dec3: materialise unpool(g_x3) + skip gradient once
+      const size_t n = (size_t)B * H * W * (64 * sizeof(ET) / 16);
+      hla_prof_begin(K_ELEMWISE, 0, (double)B * H * W * 64 * sizeof(ET) * 2.25, st);
+      hipLaunchKernelGGL((unpool_add_kernel<ET>), dim3((unsigned)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535)), dim3(256), 0, st,
+                         (const ET*)G(M_X3), IDX(IDX_3), (const ET*)G(M_X2P), (ET*)G(M_C2), B, H, W);
+      hla_prof_end(st);
+      if (SPLIT) absmax_map(M_C2, 0);
+    }
+    for (int i = 0; i < DC_ALL; ++i)
+      if (kDgrad[i].layer == l && vgg_level_runs(kDgrad[i].level, level4)) dgrad(i);
+    for (int i = 0; i < DW_ALL; ++i)
+      if (kWgrad[i].layer == l && vgg_level_runs(kWgrad[i].level, level4)) wgrad(i);
   }
-  // ---- decoder 2 (VGG.py:148-151)
-  dgrad(10, 0, 64, G(bp.g_x21), nullptr, Hd2, Wd2, G(bp.g_d2a), F(fp.d2a), nullptr, false, n_d2a, n_x21, 0, DC_10, GA_X21, GA_D2A);   // (g_x21 is unwritten above n_x21)
-  wgrad(10, F(fp.d2a), 64, nullptr, 0, 0, G(bp.g_x21), nullptr, Hd2, Wd2, n_x21, DW_10, AM_D2A, -1, GA_X21);
-  dgrad(9, 0, 128, G(bp.g_d2a), nullptr, Hd2, Wd2, G(bp.g_x18), F(fp.x18r), G(bp.l2_18), true, rb_up18, n_d2a, 0, DC_9U, GA_D2A, GA_X18);   // up(x18) branch
-  dgrad(9, 128, 64, G(bp.g_d2a), nullptr, Hd2, Wd2, G(bp.g_x3p), F(fp.x3), nullptr, false, n_x3p, n_d2a, 0, DC_9S, GA_D2A, GA_X3P);          // x3 skip branch
-  wgrad(9, F(fp.x18r), 128, F(fp.x3), 64, 1, G(bp.g_d2a), nullptr, Hd2, Wd2, n_d2a, DW_9, AM_X18, AM_X3, GA_D2A);
-  // ---- decoder 1 (VGG.py:144-146)
-  dgrad(8, 0, 128, G(bp.g_x18), nullptr, Hd4, Wd4, G(bp.g_d1a), F(fp.d1a), nullptr, false, n_d1a, n_x18, 0, DC_8, GA_X18, GA_D1A);
-  wgrad(8, F(fp.d1a), 128, nullptr, 0, 0, G(bp.g_x18), nullptr, Hd4, Wd4, n_x18, DW_8, AM_D1A, -1, GA_X18);
-  dgrad(7, 0, 256, G(bp.g_d1a), nullptr, Hd4, Wd4, G(bp.g_x15), F(fp.x15r), G(bp.l2_15), true, rb_up15, n_d1a, 0, DC_7U, GA_D1A, GA_X15);   // up(x15) branch
-  dgrad(7, 256, 128, G(bp.g_d1a), nullptr, Hd4, Wd4, G(bp.g_x8p), F(fp.x8), nullptr, false, n_x8p, n_d1a, 0, DC_7S, GA_D1A, GA_X8P);        // x8 skip branch
-  wgrad(7, F(fp.x15r), 256, F(fp.x8), 128, 1, G(bp.g_d1a), nullptr, Hd4, Wd4, n_d1a, DW_7, AM_X15, AM_X8, GA_D1A);
-  // ---- encoder block 2 (VGG.py:136-141); conv14 is followed by the pool (no ReLU in between)
-  dgrad(6, 0, 256, G(bp.g_x15), idx15, H4, W4, G(bp.g_a12), F(fp.a12), nullptr, false, n_a12, 2 * n_x15, 0, DC_6, GA_X15, GA_A12);
-  wgrad(6, F(fp.a12), 256, nullptr, 0, 0, G(bp.g_x15), idx15, H4, W4, 2 * n_x15, DW_6, AM_A12, -1, GA_X15);
-  dgrad(5, 0, 256, G(bp.g_a12), nullptr, H4, W4, G(bp.g_a10), F(fp.a10), nullptr, false, n_a10, n_a12, 0, DC_5, GA_A12, GA_A10);
-  wgrad(5, F(fp.a10), 256, nullptr, 0, 0, G(bp.g_a12), nullptr, H4, W4, n_a12, DW_5, AM_A10, -1, GA_A12);
-  dgrad(4, 0, 128, G(bp.g_a10), nullptr, H4, W4, G(bp.g_x8), F(fp.x8), G(bp.g_x8p), false, n_x8, n_a10, n_x8p, DC_4, GA_A10, GA_X8);
-  wgrad(4, F(fp.x8), 128, nullptr, 0, 0, G(bp.g_a10), nullptr, H4, W4, n_a10, DW_4, AM_X8, -1, GA_A10);
-  // ---- encoder block 1
-  dgrad(3, 0, 128, G(bp.g_x8), idx8, H2, W2, G(bp.g_a5), F(fp.a5), nullptr, false, n_a5, 2 * n_x8, 0, DC_3, GA_X8, GA_A5);
-  wgrad(3, F(fp.a5), 128, nullptr, 0, 0, G(bp.g_x8), idx8, H2, W2, 2 * n_x8, DW_3, AM_A5, -1, GA_X8);
-  dgrad(2, 0, 64, G(bp.g_a5), nullptr, H2, W2, G(bp.g_x3), F(fp.x3), G(bp.g_x3p), false, n_x3, n_a5, n_x3p, DC_2, GA_A5, GA_X3);
-  wgrad(2, F(fp.x3), 64, nullptr, 0, 0, G(bp.g_a5), nullptr, H2, W2, n_a5, DW_2, AM_X3, -1, GA_A5);
-  // ---- encoder block 0
-  if (level4) {      // the conv2 output also fed conv_dec3: materialise unpool(g_x3) + skip gradient once
-    const size_t n = (size_t)B * H * W * (64 * sizeof(ET) / 16);
-    hla_prof_begin(K_ELEMWISE, 0, (double)B * H * W * 64 * sizeof(ET) * 2.25, st);
-    hipLaunchKernelGGL((unpool_add_kernel<ET>), dim3((unsigned)((n + 255) / 256 < 65535 ? (n + 255) / 256 : 65535)), dim3(256), 0, st,
-                       (const ET*)G(bp.g_x3), idx3, (const ET*)G(bp.g_x2p), (ET*)G(bp.g_c2), B, H, W);
-    hla_prof_end(st);
-    if (SPLIT) absmax_map(G(bp.g_c2), (size_t)H * W * 64, 0, GA_C2);
-    dgrad(1, 0, 64, G(bp.g_c2), nullptr, H, W, G(bp.g_a0), F(fp.a0), nullptr, false, 0, 0, 0, -1, GA_C2, GA_A0);
-    wgrad(1, F(fp.a0), 64, nullptr, 0, 0, G(bp.g_c2), nullptr, H, W, 0, -1, AM_A0, -1, GA_C2);
-  } else {
-    dgrad(1, 0, 64, G(bp.g_x3), idx3, H, W, G(bp.g_a0), F(fp.a0), nullptr, false, n_a0, 2 * n_x3, 0, DC_1, GA_X3, fuse0 ? -1 : GA_A0, fuse0);
-    wgrad(1, F(fp.a0), 64, nullptr, 0, 0, G(bp.g_x3), idx3, H, W, 2 * n_x3, DW_1, AM_A0, -1, GA_X3);
-  }
+  // ---- conv0's weight gradient
+  const int n_a0 = rows.dw_row[DW_0];
   if (fuse0) {
-    // conv0's weight gradient left the data gradient's epilogue as one [64][32] partial per workgroup, in the place of the map
-    // (8 KB per 8 x 32-pixel tile against the map's 32 / 64 KB): 1024 slabs, then the generic gather (k < 27: dW0, column 27: db0)
-    const int tiles = ((W + 31) / 32) * ((H - (n_a0 > 0 ? n_a0 : 0) + 7) / 8) * B, NS = 1024;
-    const bool dyn1 = dynamic;
+    // it left the data gradient's epilogue as one [64][32] partial per workgroup, in the place of the map (8 KB per 8 x 32-pixel
+    // tile against the map's 32 / 64 KB): 1024 slabs, then the generic gather (k < 27: dW0, column 27: db0)
+    const int tiles = ((W + 31) / 32) * ((H - n_a0 + 7) / 8) * B, NS = 1024;
     float* slab = (float*)(bw + bp.part);
-    hla_prof_begin(K_ELEMWISE, 0, (double)tiles * 8192.0 * (dyn1 ? 0.5 : 1.0), st);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(NS), dim3(256), 0, st, (const float4*)G(bp.g_a0), (float4*)slab, 512, tiles,
-                       dyn1 ? dynp + dl.conv_desc[DC_1] : (const int*)nullptr, B);
+    hla_prof_begin(K_ELEMWISE, 0, (double)tiles * 8192.0 * (dynamic ? 0.5 : 1.0), st);
+    hipLaunchKernelGGL(reduce_rows_kernel, dim3(NS), dim3(256), 0, st, (const float4*)G(M_A0), (float4*)slab, 512, tiles,
+                       dynamic ? dynp + dl.conv_desc[DC_1] : (const int*)nullptr, B);
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((64 * 27 + 15) / 16), dim3(256), 0, st, (const float*)slab, gr->dw[0], (size_t)64 * 27, NS, 64 * 32, 27, 32);
     if (gr->db[0]) hipLaunchKernelGGL(reduce_partials_kernel, dim3(4), dim3(256), 0, st, (const float*)slab + 27, gr->db[0], (size_t)64, NS, 64 * 32, 1, 32);
     hla_prof_end(st);
   } else {
     Wgrad0Args a{};
-    a.x = x; a.x_plane = x_plane ? x_plane : (size_t)H * W; a.g = G(bp.g_a0); a.B = B; a.H = H; a.W = W;
-    a.row_begin = level4 ? 0 : n_a0;
+    a.x = c.x; a.x_plane = c.x_plane ? c.x_plane : (size_t)H * W; a.g = G(M_A0); a.B = B; a.H = H; a.W = W;
+    a.row_begin = n_a0;
     a.dyn = dynamic ? dynp : nullptr; a.dyn_desc = dl.wg_desc[DW_0];
     a.tiles_x = (W + 31) / 32; a.tiles_y = (H - a.row_begin + WG_TH - 1) / WG_TH; a.ntile = B * a.tiles_x * a.tiles_y;
     a.KS = a.ntile < 1024 ? a.ntile : 1024;
@@ -880,11 +799,11 @@ int vgg_backward_t(const float* x, size_t x_plane, const hla_vgg_params* prm, co
 
 #if HLA_TU_DTYPE >= 0
 template void vgg_pack_all_T<TuT>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st);
-template int vgg_backward_t<TuT>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packedT, int dtype, const char* fw, const float* const feat[3], const double* inv_norm, const float* const d_feat[3], const float* const conf[3], const float* const d_conf[3], const hla_vgg_grads* gr, char* bw, const BwdPlan& bp, int B, int H, int W, int flags, int first_row8, hipStream_t st);
+template int vgg_backward_t<TuT>(const VggBwdCall& c);
 #else
 #define HLA_EXTERN_T(T) \
   extern template void vgg_pack_all_T<T>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st); \
-  extern template int vgg_backward_t<T>(const float* x, size_t x_plane, const hla_vgg_params* prm, const char* packedT, int dtype, const char* fw, const float* const feat[3], const double* inv_norm, const float* const d_feat[3], const float* const conf[3], const float* const d_conf[3], const hla_vgg_grads* gr, char* bw, const BwdPlan& bp, int B, int H, int W, int flags, int first_row8, hipStream_t st);
+  extern template int vgg_backward_t<T>(const VggBwdCall& c);
 HLA_EXTERN_T(float) HLA_EXTERN_T(bf16) HLA_EXTERN_T(f16) HLA_EXTERN_T(split32)
 
 extern "C" size_t hla_vgg_bwd_workspace_bytes(int B, int H, int W, int level, int dtype) {
@@ -901,8 +820,6 @@ extern "C" size_t hla_vgg_bwd_workspace_bytes_flags(int B, int H, int W, int lev
 
 // (HLA_F16X3: fp32 storage in the HLA_F32 workspace layout; data and weight gradients on split-fp16 kernels, conv0's weight
 // gradient and the elementwise passes on the fp32 ones)
-static inline int bwd_dtype(int dtype) { return dtype; }
-
 extern "C" size_t hla_vgg_packed_weight_T_bytes(int dtype) {
   return packed_offset(kAllLayers, dtype) + (dtype == HLA_F16X3 ? kPackTailBytes : 0);
 }
@@ -910,11 +827,7 @@ extern "C" size_t hla_vgg_packed_weight_T_bytes(int dtype) {
 extern "C" int hla_vgg_pack_weights_T(const hla_vgg_params* params, void* packed, int dtype, hla_stream_t stream) {
   HLA_REQUIRE(params && packed, "hla_vgg_pack_weights_T: null argument");
   HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_pack_weights_T: bad dtype %d", dtype);
-  dtype = bwd_dtype(dtype);
-  if (dtype == HLA_BF16) vgg_pack_all_T<bf16>(params, (char*)packed, dtype, (hipStream_t)stream);
-  else if (dtype == HLA_F16) vgg_pack_all_T<f16>(params, (char*)packed, dtype, (hipStream_t)stream);
-  else if (dtype == HLA_F16X3) vgg_pack_all_T<split32>(params, (char*)packed, dtype, (hipStream_t)stream);
-  else vgg_pack_all_T<float>(params, (char*)packed, dtype, (hipStream_t)stream);
+  hla_dispatch_dtype(dtype, [&](auto t) { vgg_pack_all_T<typename decltype(t)::type>(params, (char*)packed, dtype, (hipStream_t)stream); });
   HLA_CHECK_HIP(hipGetLastError());
   return HLA_OK;
 }
@@ -927,7 +840,6 @@ extern "C" int hla_vgg_backward(const float* x, size_t x_plane, const hla_vgg_pa
   HLA_REQUIRE(x && params && packed_weights_T && fwd_workspace && feat && inv_norm && d_feat && grads && workspace,
               "hla_vgg_backward: null argument");
   HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_backward: bad dtype %d", dtype);
-  dtype = bwd_dtype(dtype);
   HLA_REQUIRE(level == 3 || level == 4, "hla_vgg_backward: level must be 3 or 4");
   HLA_REQUIRE((size_t)H * W * 64 * 4 < ((size_t)1 << 31), "hla_vgg_backward: image too large (H*W must be below 2^23 pixels)");
   HLA_REQUIRE(x_plane == 0 || x_plane >= (size_t)H * W, "hla_vgg_backward: x_plane (%zu) must be 0 or >= H*W", x_plane);
@@ -944,43 +856,33 @@ extern "C" int hla_vgg_backward(const float* x, size_t x_plane, const hla_vgg_pa
   if (level == 4)
     HLA_REQUIRE(feat[3] && d_feat[3] && params->w[11] && params->w[12] && grads->dw[11] && grads->dw[12],
                 "hla_vgg_backward: level 4 needs feat[3], d_feat[3], the padded conv_dec3 weights and dw[11], dw[12] ([64,128,3,3], [64,64,3,3])");
-  BwdPlan bp;
-  bwd_plan(B, H, W, dtype, &bp, level == 4, (flags & HLA_VGG_BWD_FOLD_DECODER) != 0);
-  if (workspace_bytes < bp.total) {
-    hla_set_error("hla_vgg_backward: workspace %zu < %zu", workspace_bytes, bp.total);
+  VggBwdCall c{x, x_plane, params, (const char*)packed_weights_T, (const char*)fwd_workspace, feat, inv_norm, d_feat, conf, d_conf, grads,
+               (char*)workspace, B, H, W, level, dtype, flags, first_row8, (hipStream_t)stream, {}};
+  bwd_plan(B, H, W, dtype, &c.bp, level == 4, (flags & HLA_VGG_BWD_FOLD_DECODER) != 0);
+  if (workspace_bytes < c.bp.total) {
+    hla_set_error("hla_vgg_backward: workspace %zu < %zu", workspace_bytes, c.bp.total);
     return HLA_ERR_WORKSPACE;
   }
-  if (dtype == HLA_BF16)
-    return vgg_backward_t<bf16>(x, x_plane, params, (const char*)packed_weights_T, dtype, (const char*)fwd_workspace, feat, inv_norm,
-                                d_feat, conf, d_conf, grads, (char*)workspace, bp, B, H, W, flags, first_row8, (hipStream_t)stream);
-  if (dtype == HLA_F16)
-    return vgg_backward_t<f16>(x, x_plane, params, (const char*)packed_weights_T, dtype, (const char*)fwd_workspace, feat, inv_norm,
-                               d_feat, conf, d_conf, grads, (char*)workspace, bp, B, H, W, flags, first_row8, (hipStream_t)stream);
-  if (dtype == HLA_F16X3)
-    return vgg_backward_t<split32>(x, x_plane, params, (const char*)packed_weights_T, dtype, (const char*)fwd_workspace, feat, inv_norm,
-                                   d_feat, conf, d_conf, grads, (char*)workspace, bp, B, H, W, flags, first_row8, (hipStream_t)stream);
-  return vgg_backward_t<float>(x, x_plane, params, (const char*)packed_weights_T, dtype, (const char*)fwd_workspace, feat, inv_norm,
-                               d_feat, conf, d_conf, grads, (char*)workspace, bp, B, H, W, flags, first_row8, (hipStream_t)stream);
+  return hla_dispatch_dtype(dtype, [&](auto t) { return vgg_backward_t<typename decltype(t)::type>(c); });
 }
 extern "C" int hla_vgg_backward_live_tiles(const void* workspace, int B, int H, int W, int level, int dtype, long long* live,
                                            long long* total) {
   HLA_REQUIRE(workspace && live && total, "hla_vgg_backward_live_tiles: null argument");
   HLA_REQUIRE(hla_dtype_ok(dtype), "hla_vgg_backward_live_tiles: bad dtype %d", dtype);
   BwdPlan bp;
-  bwd_plan(B, H, W, bwd_dtype(dtype), &bp, level == 4);
+  bwd_plan(B, H, W, dtype, &bp, level == 4);
   const DynLayout L = dyn_layout(H, W);
   std::vector<int> h(L.total);
   HLA_CHECK_HIP(hipMemcpy(h.data(), (const char*)workspace + bp.dyn, (size_t)L.total * sizeof(int), hipMemcpyDeviceToHost));
   *live = *total = 0;
   if ((h[L.used] & 0xff) != 1) return HLA_OK;
-  const int cdiv[DC_N] = {2, 2, 2, 4, 4, 4, 4, 4, 4, 2, 2, 1}, wdiv[DW_N] = {2, 2, 4, 4, 4, 4, 4, 2, 2, 1, 1};
   for (int i = 0; i < DC_N; ++i) {
     *live += h[L.conv_desc[i]];
-    *total += (long long)((H / cdiv[i] + 7) / 8) * ((W / cdiv[i] + 31) / 32);
+    *total += bwd_tiles(kDgrad[i].layer, H, W, 8);
   }
   for (int i = 0; i < DW_N; ++i) {
     *live += h[L.wg_desc[i]];
-    *total += (long long)((H / wdiv[i] + WG_TH - 1) / WG_TH) * ((W / wdiv[i] + 31) / 32);
+    *total += bwd_tiles(kWgrad[i].layer, H, W, WG_TH);
   }
   return HLA_OK;
 }
