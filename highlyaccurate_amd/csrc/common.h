@@ -24,7 +24,7 @@ bool hla_prof_on();
 #define HLA_CONV_STAMPS 0
 #endif
 #if HLA_CONV_STAMPS
-constexpr int HLA_STAMP_N = 8;
+constexpr int HLA_STAMP_N = 16;
 struct HlaStampCfg { unsigned long long* buf; int want; int counter; unsigned grid_x, grid_y; };
 extern HlaStampCfg g_hla_stamp;      // prof.hip
 #endif

@@ -315,8 +315,12 @@ __device__ __forceinline__ int halo_off(int pix, int hx, int slot) { return pix 
 // un-pooled one; (0, 4) the same; (3, 7) and (1, 6) lose 1-4 %; (3, 6) costs the 32-channel wave tile 20 %)
 constexpr int HALO_TAP0 = 2, HALO_TAP1 = 6;
 // The 16-bit plain kernels fetch a stage's halo tile HBM -> LDS directly (conv3x3_kernel, DMA); the tap at whose weight loads the
-// tile is requested (0 / 1 / 3 measure the same).
+// tile is requested.  (With the compiler-counted ring 0 / 1 / 3 measured the same: the wait for the tile moved with the request.
+// With the hand-counted ring of the forward launches, same-box A/B against tap 1: tap 0 +3 %, 2 +2.5 %, 3 +1.5 %, 6 +5 % per step.)
 constexpr int HLA_CONV_DMA_TAP = 1;
+#ifndef HLA_CONV_ASYNC_RING
+#define HLA_CONV_ASYNC_RING 1
+#endif
 // per-lane byte offsets of a wave's pixel fragments: [kx][kg] -> (x + kx) * PSTR + swizzled slot of (lane half g, k-group kg),
 // relative to the wave's first halo row
 // SHAPE_16x16x32: [kx][p] -> pixel half p of the row (16 p + (lane & 15)), channel slot lane >> 4: a 16-lane group of the
@@ -912,10 +916,56 @@ __device__ __forceinline__ void conv_epilogue_wg0(f32x16 (&acc)[MT][1], const Co
 // offsets into it: the wave's first row, the lane's pixel and the swizzled slot of its k-half).  Weight fragments come from global memory through a ring of
 // WD+1 register sets filled WD taps ahead; `mid(tap)` runs right after the weight loads of each tap (used to
 // issue the next stage's halo loads BEHIND them: VM loads of a wave retire in order).
-template <typename T, int MT, int NT, int WD, int PF = (NT == 1 ? 4 : 3)>
+//
+// ASYNC (the 16-bit forward kernels with the DMA halo loader): the ring's loads are requested and awaited by hand.  The compiler
+// cannot count the tile's buffer_load ... lds (they sit in an asm statement), so the s_waitcnt vmcnt(N) it places in front of a
+// weight fragment's first use is short by the NPIECE tile loads whenever the tile is younger than the fragment: vmcnt retires in
+// issue order, so such a wait also waits for part of the tile, an HBM round trip, within the very tap that requested it.  With
+// the weight loads hidden from the compiler as well, every wait in the stage loop is written out below with the true count
+// (stage_mma).  The loads then have to obey what the compiler no longer enforces: a ring register is never read, copied or
+// reused between its request and the wait that names it (the waits take the fragments as "+v" operands, so every use depends
+// on them; 9 % RS == 0, so no rotation copies fragments that are still in flight across the stage boundary), and nothing is in
+// flight when the stage loop is left (conv3x3_body).  The fragment base is wave-uniform: it lives in scalar registers and a
+// lane adds its 16 bytes.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+template <typename T, int MT, int NT, int WD, int PF = (NT == 1 ? 4 : 3), bool ASYNC = false>
 struct WeightRing {
   static constexpr int RS = WD + 1;
+  static_assert(!ASYNC || 9 % RS == 0, "fragments in flight across the stage boundary must keep their ring slot");
+  static_assert(!ASYNC || NT <= 2, "wait() names 2 * NT fragments");
   uint4 wb[RS][2][NT];
+  u32x4 wa[RS][2][NT];   // ASYNC: the ring (asm operands are plain vectors)
+  const char* ws[NT];    // ASYNC: wave-uniform pointer to this stage's fragments of output tile j
+  unsigned lane16;       // ASYNC: the lane's byte offset inside a fragment
+  __device__ __forceinline__ uint4 frag(int slot, int c, int j) const {
+    if constexpr (ASYNC) return __builtin_bit_cast(uint4, wa[slot][c][j]);
+    else return wb[slot][c][j];
+  }
+  // request the fragments of tap `tapi` of this stage (>= 9: a tap of the next stage) into ring slot `slot`
+  __device__ __forceinline__ void request(int slot, int tapi) {
+#pragma unroll
+    for (int kg = 0; kg < 2; ++kg)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        if constexpr (ASYNC) {
+          const char* p = ws[j] + (tapi * 2 + kg) * 1024;
+          asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(wa[slot][kg][j]) : "v"(lane16), "s"(p));
+        } else {
+          wb[slot][kg][j] = wq[j][(tapi * 2 + kg) * 64];
+        }
+      }
+  }
+  // ASYNC: wait until at most the N youngest vector-memory operations of the wave are in flight (N0 when `alt`: wave-uniform);
+  // slot `slot` is usable behind it.  The branch holds the bare instruction and the fragments are named once, behind the join:
+  // named in both arms they would be two definitions to merge, and the copies of that merge are placed AHEAD of the wait.
+  template <int N, int N0 = N> __device__ __forceinline__ void wait(int slot, bool alt = false) {
+    if (N0 != N && alt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N0));
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N));
+    if constexpr (NT == 2)
+      asm volatile("" : "+v"(wa[slot][0][0]), "+v"(wa[slot][0][1]), "+v"(wa[slot][1][0]), "+v"(wa[slot][1][1]));
+    else
+      asm volatile("" : "+v"(wa[slot][0][0]), "+v"(wa[slot][1][0]));
+  }
   // pixel fragments in flight ahead of the MFMAs (one MFMA per fragment at NT = 1: four reads = 128 matrix-pipe cycles of cover;
   // six, round 2's choice at two workgroups per CU, cost the three-workgroup kernel 27 spilled registers: 804 against 1100 TF)
   static constexpr int PFD = PF;     // default: 4 at NT = 1, 3 at NT = 2 (NT = 2: 2 and 4 measure the same as 3)
@@ -923,6 +973,11 @@ struct WeightRing {
   const uint4* wq[NT];   // per-lane pointer to this stage's fragments of output tile j: [tap][kg][lane]
 
   __device__ __forceinline__ void prime() {
+    if constexpr (ASYNC) {
+#pragma unroll
+      for (int d = 0; d < WD; ++d) request(d, d);
+      return;
+    }
 #pragma unroll
     for (int d = 0; d < WD; ++d)
 #pragma unroll
@@ -932,6 +987,11 @@ struct WeightRing {
   }
   // after a stage the ring holds taps 0..WD-1 of the next stage in slots (9+d) % RS; rotate them to slot d
   __device__ __forceinline__ void next_stage() {
+    if constexpr (ASYNC) {      // (9 % RS == 0: they are in slot d already)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) ws[j] += 18 * 1024;
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < NT; ++j) wq[j] += 18 * 64;
     if (9 % RS != 0) {
@@ -964,17 +1024,47 @@ __device__ __forceinline__ void stagger_priority() {
 
 // SHAPE_16x16x32: the same loop with the fragment index renamed -- pixel fragment (row i, pixel half p), weight fragment [c][j]
 // (cout half c): 2 NT MFMAs of half the length per pixel fragment, so PF reads ahead cover the same matrix time.
-template <typename T, int MT, int NT, int WD, int PF, int SHAPE = SHAPE_32x32x16, typename Mid>
+//
+// DMAN > 0 (ASYNC ring): `mid(HLA_CONV_DMA_TAP)` requests the next stage's tile with DMAN loads when `more`, and the waits are
+// counted here.  A wave's vector-memory queue, in issue order, holds per tap t the 2 NT fragments of tap t + WD and, behind those
+// of tap HLA_CONV_DMA_TAP + WD, the tile.  In front of tap t's MFMAs its own fragments must have landed; younger than they are
+// the fragments of taps t+1 .. t+WD (2 NT WD loads) and, for t = DMA_TAP .. DMA_TAP + WD, the tile (requested after them, and
+// before tap t).  So the wait is vmcnt(2 NT WD + DMAN) on those WD + 1 taps of a stage that has a next one, and vmcnt(2 NT WD)
+// everywhere else: the taps DMA_TAP .. DMA_TAP + WD never wait for the tile.  The first fragments requested BEHIND the tile are
+// those of tap DMA_TAP + WD + 1; their wait (and every later one, vmcnt being in order) cannot pass before the tile has landed.
+#if HLA_CONV_STAMPS
+// Tooling build: cycle sums of one wave over the stages >= 1 that request a tile.  w[k]: the first pixel fragment's MFMA group of
+// tap DMA_TAP + k (k = 0..3; every vmcnt wait of a tap sits in front of or inside that group) and, k = 4, of tap 8 as the control.
+struct StageStamps { bool on; unsigned long long t0, w[5]; };
+#endif
+template <typename T, int MT, int NT, int WD, int PF, int SHAPE = SHAPE_32x32x16, int DMAN = 0, bool ASYNC = false, typename Mid>
 __device__ __forceinline__ void stage_mma(typename AccMap<SHAPE>::Tile (&acc)[MT][NT], const char* cur, const FragOff& fo,
-                                          WeightRing<T, MT, NT, WD, PF>& ring, Mid&& mid) {
+                                          WeightRing<T, MT, NT, WD, PF, ASYNC>& ring, Mid&& mid, bool more = false
+#if HLA_CONV_STAMPS
+                                          , StageStamps* ss = nullptr
+#endif
+                                          ) {
   constexpr int RS = WD + 1;
+  static_assert(ASYNC == (DMAN > 0), "the hand-counted ring belongs to the DMA halo loader");
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
+    if constexpr (ASYNC) {
+      ring.request((tap + WD) % RS, tap + WD);
+    } else {
 #pragma unroll
-    for (int kg = 0; kg < 2; ++kg)
+      for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
-      for (int j = 0; j < NT; ++j) ring.wb[(tap + WD) % RS][kg][j] = ring.wq[j][((tap + WD) * 2 + kg) * 64];
+        for (int j = 0; j < NT; ++j) ring.wb[(tap + WD) % RS][kg][j] = ring.wq[j][((tap + WD) * 2 + kg) * 64];
+    }
     mid(tap);
+#if HLA_CONV_STAMPS
+    const bool stamped = ss && ss->on && ((tap >= HLA_CONV_DMA_TAP && tap <= HLA_CONV_DMA_TAP + 3) || tap == 8);
+    if (stamped) ss->t0 = __builtin_readcyclecounter();
+#endif
+    if constexpr (ASYNC) {
+      if (tap >= HLA_CONV_DMA_TAP && tap <= HLA_CONV_DMA_TAP + WD) ring.template wait<2 * NT * WD, 2 * NT * WD + DMAN>(tap % RS, more);
+      else ring.template wait<2 * NT * WD>(tap % RS);
+    }
     // pixel fragments software-pipelined DEPTH reads ahead of the MFMAs that consume them, through tap boundaries.  (The
     // straightforward "read the fragments of a row, multiply" order leaves every ds_read_b128 one LDS latency -- about 100
     // cycles -- ahead of its first MFMA with only 64 cycles of matrix work queued behind it: the pipe idled ~4 x 50 cycles per
@@ -1000,17 +1090,20 @@ __device__ __forceinline__ void stage_mma(typename AccMap<SHAPE>::Tile (&acc)[MT
 #pragma unroll
         for (int c = 0; c < (kg == 0 ? 2 : 1); ++c)
 #pragma unroll
-          for (int j = 0; j < NT; ++j) mma16<T>(acc[i][j], ring.wb[tap % RS][c][j], ring.pf[slot]);
+          for (int j = 0; j < NT; ++j) mma16<T>(acc[i][j], ring.frag(tap % RS, c, j), ring.pf[slot]);
       } else if constexpr (SHAPE == SHAPE_16x16x32) {
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-          for (int j = 0; j < NT; ++j) mma32<T>(acc[i][j].t[2 * kg + c], ring.wb[tap % RS][c][j], ring.pf[slot]);
+          for (int j = 0; j < NT; ++j) mma32<T>(acc[i][j].t[2 * kg + c], ring.frag(tap % RS, c, j), ring.pf[slot]);
       } else {
 #pragma unroll
-        for (int j = 0; j < NT; ++j) mma16<T>(acc[i][j], ring.wb[tap % RS][kg][j], ring.pf[slot]);
+        for (int j = 0; j < NT; ++j) mma16<T>(acc[i][j], ring.frag(tap % RS, kg, j), ring.pf[slot]);
       }
       __builtin_amdgcn_sched_barrier(0);
+#if HLA_CONV_STAMPS
+      if (f == 0 && stamped) ss->w[tap == 8 && HLA_CONV_DMA_TAP + 3 < 8 ? 4 : tap - HLA_CONV_DMA_TAP] += __builtin_readcyclecounter() - ss->t0;
+#endif
     }
   }
   ring.next_stage();
@@ -1037,9 +1130,12 @@ constexpr int conv3x3_lds_bytes() {      // LDS bytes of conv3x3_body<T, MT, NT,
   constexpr int stg = 32 * (RowStager<float, NT>::PITCH + (sizeof(T) == 2 ? RowStager<T, NT>::PITCH : 0));
   return 2 * buf > 4 * stg ? 2 * buf : 4 * stg;
 }
-template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16, bool XLDS = false>
+// WRA: the weight ring is requested and awaited by hand (WeightRing, ASYNC): the 16-bit forward launches of launch_conv.
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16, bool XLDS = false,
+          bool WRA = false>
 __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, const int nblk) {
   static_assert(WM * WN == 4, "4 waves per block");
+  static_assert(!WRA || (sizeof(T) == 2 && !UNPOOL), "the hand-counted weight ring counts the DMA halo loader's requests");
   static_assert(SHAPE == SHAPE_32x32x16 || (sizeof(T) == 2 && !UNPOOL), "16x16x32: bf16 / f16 forward kernels only");
   using M = AccMap<SHAPE>;
   constexpr int EPL = 16 / sizeof(T), KC = SB / sizeof(T);     // channels per stage: 32 (bf16) / 16 (fp32)
@@ -1284,10 +1380,14 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   // packed weights: [ntile][stage][tap][kg(2)][lane] 16-B fragments
   // (the un-pooling loader carries a piece's argmax bytes next to it: at the three-workgroup register cap that costs the 32-channel
   //  wave tile one fragment of read-ahead -- with four, 7 registers spilled and 3 scratch accesses sat inside the MFMA stream)
-  constexpr int PF = NT == 1 ? (UNPOOL && sizeof(T) == 2 ? 3 : 4) : 3;
-  WeightRing<T, MT, NT, WD, PF> ring;
+  constexpr int PF = NT == 1 ? (UNPOOL && sizeof(T) == 2 ? 3 : 4) : (WRA ? 2 : 3);
+  WeightRing<T, MT, NT, WD, PF, WRA> ring;
 #pragma unroll
-  for (int j = 0; j < NT; ++j) ring.wq[j] = a.wpk + (size_t)(ntg0 + j) * nstage * 18 * 64 + lane;
+  for (int j = 0; j < NT; ++j) {
+    if constexpr (WRA) ring.ws[j] = (const char*)(a.wpk + (size_t)(ntg0 + j) * nstage * 18 * 64);
+    else ring.wq[j] = a.wpk + (size_t)(ntg0 + j) * nstage * 18 * 64 + lane;
+  }
+  if constexpr (WRA) ring.lane16 = lane * 16;
 
   uint4 st[NHALF];
   StageIds ids;
@@ -1295,6 +1395,10 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   if constexpr (DMA) {
     dma_stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (WRA) {     // (the primed fragments have landed with the tile: name them, so that no use is placed above the wait)
+#pragma unroll
+      for (int d = 0; d < WD; ++d) ring.template wait<0>(d);
+    }
   } else {
     uint4 st1[NHALF];        // the prologue has registers to spare: both halves are requested back to back
     StageIds ids1;
@@ -1307,30 +1411,67 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   HLA_STAMP(1);
   stagger_priority();
 
+#if HLA_CONV_STAMPS
+  StageStamps ss = {false, 0, {0, 0, 0, 0, 0}};
+  unsigned long long ss_req = 0, ss_bar = 0, ss_stage = 0, ss_n = 0;
+#endif
   for (int sg = 0; sg < nstage; ++sg) {
     const bool more = sg + 1 < nstage;
     char* nxt = lds + ((sg + 1) & 1) * BUF;
-    stage_mma<T, MT, NT, WD, PF, SHAPE>(acc, lds + (sg & 1) * BUF, fo, ring, [&](int tap) __attribute__((always_inline)) {
+#if HLA_CONV_STAMPS
+    ss.on = a.stamps && sg >= 1 && more;
+    const unsigned long long ts_stage = __builtin_readcyclecounter();
+#endif
+    stage_mma<T, MT, NT, WD, PF, SHAPE, WRA ? NPIECE : 0>(acc, lds + (sg & 1) * BUF, fo, ring, [&](int tap) __attribute__((always_inline)) {
       if constexpr (DMA) {
-        if (tap == HLA_CONV_DMA_TAP && more) dma_stage(sg + 1, (sg + 1) & 1);
+        if (tap == HLA_CONV_DMA_TAP && more) {
+#if HLA_CONV_STAMPS
+          const unsigned long long ts_req = __builtin_readcyclecounter();
+#endif
+          dma_stage(sg + 1, (sg + 1) & 1);
+#if HLA_CONV_STAMPS
+          if (ss.on) ss_req += __builtin_readcyclecounter() - ts_req;
+#endif
+        }
       } else {
         if (tap == HALO_TAP0 && more) load_stage(sg + 1, 0, st, ids);
         if (tap == HALO_TAP1 && more) { write_stage(nxt, sg + 1, 0, st, ids); load_stage(sg + 1, 1, st, ids); }
       }
-    });
+    }, more
+#if HLA_CONV_STAMPS
+    , &ss
+#endif
+    );
+#if HLA_CONV_STAMPS
+    const unsigned long long ts_end = __builtin_readcyclecounter();
+#endif
     if constexpr (DMA) {
       // the next stage's tile has landed when at most the youngest 2 * NT * WD loads -- the weight fragments primed for the next
       // stage, all requested after the tile -- are still in flight
       // (only true while the tile is requested BEFORE the first of those weight loads, which go out at taps 9-WD..8)
       static_assert(!DMA || HLA_CONV_DMA_TAP <= 8 - WD, "the halo DMA must be issued before the next stage's weight fragments");
       if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NT * WD) : "memory");
+      // (hand-counted ring: the compiler does not know of the fragments requested past the last stage, so none of them may still
+      //  be in flight when the epilogue reuses their registers)
+      else if constexpr (WRA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
       if (more) write_stage(nxt, sg + 1, 1, st, ids);
     }
     if (sg == 0) HLA_STAMP(2);      // the first stage's MFMAs issued (+ the next tile awaited / written), before its barrier
     __syncthreads();
     if (sg == 0) HLA_STAMP(3);
+#if HLA_CONV_STAMPS
+    if (ss.on) { const unsigned long long te = __builtin_readcyclecounter(); ss_bar += te - ts_end; ss_stage += te - ts_stage; ++ss_n; }
+#endif
   }
+#if HLA_CONV_STAMPS
+  // stages >= 1 that request a tile, summed per wave: 6 their number, 8 the halo request, 9..12 the first MFMA group of taps
+  // DMA_TAP .. DMA_TAP + 3, 13 that of tap 8, 14 the end-of-stage wait + barrier, 15 the whole stages
+  if (a.stamps && (threadIdx.x & 63) == 0) {
+    unsigned long long* o = a.stamps + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * HLA_STAMP_N;
+    o[6] = ss_n; o[8] = ss_req; o[9] = ss.w[0]; o[10] = ss.w[1]; o[11] = ss.w[2]; o[12] = ss.w[3]; o[13] = ss.w[4]; o[14] = ss_bar; o[15] = ss_stage;
+  }
+#endif
   HLA_STAMP(4);
   // the loop's last barrier guarantees nobody still reads the halo buffers: reuse them as 4 wave-private stagers
   static_assert((LDSB / 4) % 16 == 0, "stager alignment");
@@ -1373,9 +1514,9 @@ __device__ __forceinline__ void conv3x3_body(const ConvArgs& a, const int blk, c
   }
   HLA_STAMP(5);
 }
-template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16>
-__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_kernel(ConvArgs a) {
-  conv3x3_body<T, MT, NT, WM, WN, POOL, WD, UNPOOL, SHAPE>(a, (int)blockIdx.x, (int)gridDim.x);
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, bool UNPOOL = false, int SHAPE = SHAPE_32x32x16, bool WRA = false>
+__global__ __launch_bounds__(256, (NT == 1 || (WRA && MT == 2)) ? 3 : 2) void conv3x3_kernel(ConvArgs a) {
+  conv3x3_body<T, MT, NT, WM, WN, POOL, WD, UNPOOL, SHAPE, false, WRA>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- two-segment launches (inference, vgg.hip: the same layer of the two extractors in ONE grid).  The kernarg holds two
@@ -1421,14 +1562,14 @@ __device__ __forceinline__ void pair_inference_args(ConvArgs& a) {
   a.stamps = nullptr;
 #endif
 }
-template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, int SHAPE>
-__global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv3x3_pair_kernel(PairArgs<ConvArgs> p) {
+template <typename T, int MT, int NT, int WM, int WN, bool POOL, int WD, int SHAPE, bool WRA>
+__global__ __launch_bounds__(256, (NT == 1 || (WRA && MT == 2)) ? 3 : 2) void conv3x3_pair_kernel(PairArgs<ConvArgs> p) {
   const int n0 = p.n0;
   const bool second = (int)blockIdx.x >= n0;      // workgroup-uniform
   ConvArgs a = pair_segment_args<ConvArgs>(second);
   pair_inference_args(a);
-  conv3x3_body<T, MT, NT, WM, WN, POOL, WD, false, SHAPE>(a, second ? (int)blockIdx.x - n0 : (int)blockIdx.x,
-                                                          second ? (int)gridDim.x - n0 : n0);
+  conv3x3_body<T, MT, NT, WM, WN, POOL, WD, false, SHAPE, false, WRA>(a, second ? (int)blockIdx.x - n0 : (int)blockIdx.x,
+                                                                      second ? (int)gridDim.x - n0 : n0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2189,14 +2330,14 @@ static ConvPlan conv_plan(ConvArgs& a, bool pool) {
   return p;
 }
 // one instantiation, as a plain launch or (PAIR) as a two-segment one: segment 0 = a / p, segment 1 = a2 / p2
-template <typename T, int MT, int NT, bool POOL, int WD, bool UNPOOL, int SHAPE, bool PAIR>
+template <typename T, int MT, int NT, bool POOL, int WD, bool UNPOOL, int SHAPE, bool PAIR, bool WRA = false>
 static void conv_dispatch(hipStream_t st, const ConvArgs& a, const ConvPlan& p, const ConvArgs& a2, const ConvPlan& p2) {
   if constexpr (PAIR) {
     static_assert(!UNPOOL, "two-segment launches: forward inference forms only");
     PairArgs<ConvArgs> pa{{a, a2}, p.gx * p.gy};
-    hipLaunchKernelGGL((conv3x3_pair_kernel<T, MT, NT, 2, 2, POOL, WD, SHAPE>), dim3((p.gx + p2.gx) * p.gy), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL((conv3x3_pair_kernel<T, MT, NT, 2, 2, POOL, WD, SHAPE, WRA>), dim3((p.gx + p2.gx) * p.gy), dim3(256), 0, st, pa);
   } else {
-    hipLaunchKernelGGL((conv3x3_kernel<T, MT, NT, 2, 2, POOL, WD, UNPOOL, SHAPE>), dim3(p.gx * p.gy), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((conv3x3_kernel<T, MT, NT, 2, 2, POOL, WD, UNPOOL, SHAPE, WRA>), dim3(p.gx * p.gy), dim3(256), 0, st, a);
   }
 }
 // PAIR: `a2` is the same layer of a second network (same Cout, pooling and kernel instantiation: the caller has checked that both
@@ -2234,31 +2375,37 @@ static bool launch_conv_impl(hipStream_t st, ConvArgs a, ConvArgs a2, bool pool)
   constexpr int S_NT2 = conv_shape<T, BWD>(CONV_CLASS_NT2), S_NT2P = conv_shape<T, BWD>(CONV_CLASS_NT2_POOL),
                 S_NT1 = conv_shape<T, BWD>(CONV_CLASS_NT1);
   constexpr bool UNP = BWD && !PAIR;      // only the backward's translation unit compiles the UNPOOL instantiations
+  // The 16-bit forward launches count their weight ring by hand (WeightRing, ASYNC) and run it two taps ahead in every class:
+  // three slots, so the fragments in flight across a stage boundary keep their slot (HLA_CONV_ASYNC_RING=0: the tooling build
+  // that measures the compiler-counted ring, tools/probes/conv_stamps.py).
+  constexpr bool WRA = HLA_CONV_ASYNC_RING && !BWD && sizeof(T) == 2;
+  constexpr int WD2 = WRA ? 2 : 1;        // ring depth of the 64-channel wave tile
   if (p.small) {      // (never with BWD: conv_plan)
     if constexpr (!BWD) {
       if (big) {
-        if (pool) conv_dispatch<T, 2, 2, true, 1, false, S_NT2P, PAIR>(st, a, p, a2, p2);
-        else conv_dispatch<T, 2, 2, false, 1, false, S_NT2, PAIR>(st, a, p, a2, p2);
+        if (pool) conv_dispatch<T, 2, 2, true, WD2, false, S_NT2P, PAIR, WRA>(st, a, p, a2, p2);
+        else conv_dispatch<T, 2, 2, false, WD2, false, S_NT2, PAIR, WRA>(st, a, p, a2, p2);
       } else {
-        if (pool) conv_dispatch<T, 2, 1, true, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
-        else conv_dispatch<T, 2, 1, false, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
+        if (pool) conv_dispatch<T, 2, 1, true, 2, false, S_NT1, PAIR, WRA>(st, a, p, a2, p2);
+        else conv_dispatch<T, 2, 1, false, 2, false, S_NT1, PAIR, WRA>(st, a, p, a2, p2);
       }
     }
     hla_prof_end(st);
     return true;
   }
-  // Cout >= 128: block = 8x32 pixels x 128 channels, waves 2(M) x 2(N), wave tile 128 px x 64 ch, weights 1 tap ahead
+  // Cout >= 128: block = 8x32 pixels x 128 channels, waves 2(M) x 2(N), wave tile 128 px x 64 ch, weights 1 tap ahead (WD2: 2)
   // Cout == 64 : block = 8x32 pixels x  64 channels, waves 2 x 2,       wave tile 128 px x 32 ch, weights 2 taps ahead
   if (big) {
-    // (weights two taps ahead for this tile as well: spills with the register-staged loader, -1 %; with the LDS-DMA loader it
-    //  fits -- 232 registers -- and measures the same: 4876 / 4871 against 4870 / 4841 pairs/s)
-    if (pool) conv_dispatch<T, 4, 2, true, 1, false, S_NT2P, PAIR>(st, a, p, a2, p2);
-    else if (UNP && a.unpool_idx) conv_dispatch<T, 4, 2, false, 1, UNP, S_NT2, PAIR>(st, a, p, a2, p2);
-    else conv_dispatch<T, 4, 2, false, 1, false, S_NT2, PAIR>(st, a, p, a2, p2);
+    // (weights two taps ahead for this tile as well: spills with the register-staged loader, -1 %; with the LDS-DMA loader and
+    //  the compiler-counted ring it fits -- 232 registers -- and measures the same: 4876 / 4871 against 4870 / 4841 pairs/s,
+    //  because the waits for them wait for the tile all the same.  The hand-counted ring, WD2, is two taps ahead.)
+    if (pool) conv_dispatch<T, 4, 2, true, WD2, false, S_NT2P, PAIR, WRA>(st, a, p, a2, p2);
+    else if (UNP && a.unpool_idx) { if constexpr (UNP) conv_dispatch<T, 4, 2, false, 1, true, S_NT2, PAIR>(st, a, p, a2, p2); }
+    else conv_dispatch<T, 4, 2, false, WD2, false, S_NT2, PAIR, WRA>(st, a, p, a2, p2);
   } else {
-    if (pool) conv_dispatch<T, 4, 1, true, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
-    else if (UNP && a.unpool_idx) conv_dispatch<T, 4, 1, false, 2, UNP, S_NT1, PAIR>(st, a, p, a2, p2);
-    else conv_dispatch<T, 4, 1, false, 2, false, S_NT1, PAIR>(st, a, p, a2, p2);
+    if (pool) conv_dispatch<T, 4, 1, true, 2, false, S_NT1, PAIR, WRA>(st, a, p, a2, p2);
+    else if (UNP && a.unpool_idx) { if constexpr (UNP) conv_dispatch<T, 4, 1, false, 2, true, S_NT1, PAIR>(st, a, p, a2, p2); }
+    else conv_dispatch<T, 4, 1, false, 2, false, S_NT1, PAIR, WRA>(st, a, p, a2, p2);
   }
   hla_prof_end(st);
   return true;

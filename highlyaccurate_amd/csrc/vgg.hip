@@ -287,7 +287,41 @@ int vgg_forward_pair_t(const VggFwdCall c[2]) {
   return launch_ok ? HLA_OK : HLA_ERR_ARG;
 }
 
+// One forward 3x3 convolution of ANY channel counts through launch_conv, outside the network's layer graph (the layer-level tests,
+// tests/test_conv_weight_ring.py: stage counts and kernel classes the fixed layers do not combine).  out = relu([pool](conv(src)))
+// in the activation type; with `raw` + `sumsq` the layer also writes the fp32 map before the ReLU and its sum-of-squares partials
+// -- a feature layer's epilogue, which takes 8-row tiles at any grid size (conv_plan).  No bias.  Two segments: one paired launch.
+struct HlaConvLayerSeg {
+  const void* src;      // NHWC T [B,H,W,Cin]
+  const float* w;       // [Cout,Cin,3,3]
+  void* wpk;            // scratch for the packed weights: Cout * (Cin * 9 * sizeof(T) + 256 * sizeof(T)) bytes (two taps of padding)
+  void* out;            // NHWC T [B,Ho,Wo,Cout]
+  float* raw;           // NHWC fp32 [B,Ho,Wo,Cout] or null
+  double* sumsq;        // with raw: [B, ceil(H/8) * ceil(W/32) * max(1, Cout/128)]
+  int H, W;
+};
+struct HlaConvLayerCall { int B, Cin, Cout, pool, nseg; HlaConvLayerSeg seg[2]; hipStream_t st; };
+template <typename T>
+int vgg_conv_layer_t(const HlaConvLayerCall& c) {
+  ConvArgs a[2] = {};
+  for (int k = 0; k < c.nseg; ++k) {
+    const HlaConvLayerSeg& s = c.seg[k];
+    PackTable tb{};
+    tb.w[0] = s.w; tb.off[0] = 0; tb.cout[0] = c.Cout; tb.cin[0] = c.Cin; tb.first[0] = 0;
+    tb.shape[0] = conv_shape<T, false>(conv_class(c.Cout, c.pool != 0));
+    hipLaunchKernelGGL((pack_weights_multi_kernel<T>), dim3(64, 1), dim3(256), 0, c.st, tb, (char*)s.wpk);
+    a[k].src1 = s.src; a[k].wpk = (const uint4*)s.wpk; a[k].out_act = s.out; a[k].out_raw = s.raw; a[k].sumsq = s.raw ? s.sumsq : nullptr;
+    a[k].C1 = c.Cin; a[k].B = c.B; a[k].H = s.H; a[k].W = s.W; a[k].Cout = c.Cout; a[k].relu_act = 1;
+  }
+  const bool ok = c.nseg == 2 ? launch_conv_pair<T>(c.st, a[0], a[1], c.pool != 0) : launch_conv<T>(c.st, a[0], c.pool != 0);
+  HLA_CHECK_HIP(hipGetLastError());
+  return ok ? HLA_OK : HLA_ERR_ARG;
+}
+
 #if HLA_TU_DTYPE >= 0
+#if HLA_TU_DTYPE == 1 || HLA_TU_DTYPE == 2
+template int vgg_conv_layer_t<TuT>(const HlaConvLayerCall& c);
+#endif
 template void vgg_pack_all<TuT>(const hla_vgg_params* prm, char* packed, int dtype, hipStream_t st);
 template int vgg_forward_t<TuT>(const VggFwdCall& c);
 template int vgg_forward_pair_t<TuT>(const VggFwdCall c[2]);
@@ -302,6 +336,24 @@ template int vgg_fixup_t<TuT>(const VggFwdCall& c);
 HLA_EXTERN_T(float) HLA_EXTERN_T(bf16) HLA_EXTERN_T(f16) HLA_EXTERN_T(split32)
 extern template int vgg_fixup_t<bf16>(const VggFwdCall& c);
 extern template int vgg_fixup_t<f16>(const VggFwdCall& c);
+extern template int vgg_conv_layer_t<bf16>(const HlaConvLayerCall& c);
+extern template int vgg_conv_layer_t<f16>(const HlaConvLayerCall& c);
+
+// The test hook of vgg_conv_layer_t (not part of include/hla.h): seg = HlaConvLayerSeg[nseg], nseg 1 (plain launch) or 2 (paired).
+extern "C" int hla_debug_conv_layer(int dtype, int B, int Cin, int Cout, int pool, const void* seg, int nseg, hla_stream_t stream) {
+  HLA_REQUIRE(seg && (nseg == 1 || nseg == 2), "hla_debug_conv_layer: one or two segments");
+  HLA_REQUIRE(dtype == HLA_BF16 || dtype == HLA_F16, "hla_debug_conv_layer: bf16 / fp16 only");
+  HLA_REQUIRE(B > 0 && Cin >= 32 && Cin % 32 == 0 && (Cout == 64 || (Cout >= 128 && Cout % 128 == 0)),
+              "hla_debug_conv_layer: Cin a multiple of 32, Cout 64 or a multiple of 128 (got %d, %d)", Cin, Cout);
+  HlaConvLayerCall c{B, Cin, Cout, pool, nseg, {}, (hipStream_t)stream};
+  for (int k = 0; k < nseg; ++k) {
+    c.seg[k] = ((const HlaConvLayerSeg*)seg)[k];
+    const HlaConvLayerSeg& s = c.seg[k];
+    HLA_REQUIRE(s.src && s.w && s.wpk && s.out && s.H > 0 && s.W > 0 && (!pool || (s.H % 2 == 0 && s.W % 2 == 0)) && (!s.raw || s.sumsq),
+                "hla_debug_conv_layer: segment %d: null argument, odd size under the pool, or raw without sumsq", k);
+  }
+  return dtype == HLA_BF16 ? vgg_conv_layer_t<bf16>(c) : vgg_conv_layer_t<f16>(c);
+}
 
 extern "C" size_t hla_vgg_packed_weight_bytes(int dtype) {
   return packed_offset(kAllLayers, dtype) + (dtype == HLA_F16X3 ? kPackTailBytes : 0);

@@ -4,7 +4,10 @@ on the short-K layers.  Needs the tooling build:
     HLA_LIB=$PWD/highlyaccurate_amd/libhla_stamps.so HLA_ALLOW_STALE=1 python tools/probes/conv_stamps.py [bf16|fp16x3] > profiles/r06_conv_cycle_table.json
 Stamps (s_memtime = shader-clock cycles, lane 0 of every wave): 0 entry, 1 after the prologue's barrier (first halo tile in LDS),
 2 first stage's MFMAs issued and the next tile awaited / written, 3 after that stage's barrier, 4 after the main loop's last barrier,
-5 after the epilogue.  HW_ID / XCC_ID give the CU: per CU the union of wave lifetimes against their sum is the mean number of
+5 after the epilogue; summed over the stages >= 1 that request a halo tile: 6 their number, 8 the halo request, 9..12 the first
+pixel fragment's MFMA group (with every vmcnt wait of the tap in front of or inside it) of taps DMA_TAP .. DMA_TAP + 3, 13 that of
+tap 8 (far from the request: the control), 14 the end-of-stage wait + barrier, 15 the whole stages ('later_stage_cycles' below, per
+stage; HLA_CONV_ASYNC_RING=0 in the build measures the compiler-counted weight ring).  HW_ID / XCC_ID give the CU: per CU the union of wave lifetimes against their sum is the mean number of
 resident waves; ideal = the wave's MFMA issue cycles (32 per v_mfma_f32_32x32x16)."""
 import ctypes as C, json, sys, os, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -21,7 +24,7 @@ assert hasattr(lib, 'hla_debug_conv_stamps'), 'not a -DHLA_CONV_STAMPS=1 build (
 lib.hla_debug_conv_stamps.argtypes = [C.c_void_p, C.c_int]
 B = 32
 sat, grd = torch.rand(B, 3, 512, 512, device=d), torch.rand(B, 3, 256, 1024, device=d)
-NS = 8
+NS = 16      # HLA_STAMP_N (common.h)
 buf = torch.zeros(64 << 20, dtype=torch.uint8, device=d)
 names = ['conv5', 'conv7+pool', 'conv10', 'conv12', 'conv14+pool', 'dec1.1', 'dec1.3', 'dec2.1', 'dec2.3']
 cin = [64, 128, 128, 256, 256, 384, 128, 192, 64]
@@ -62,6 +65,12 @@ with torch.no_grad():
                'mfma_issue_cycles_per_wave': int(nstage * mf_stage),
                'cycles_mean': {n: int(v.mean()) for n, v in seg.items()}, 'cycles_median': {n: int(np.median(v)) for n, v in seg.items()},
                'simds_seen': int(len(res)), 'resident_waves_per_simd': round(float(np.mean(res)), 2), 'mfma_duty_per_simd': round(float(np.mean(duty)), 3)}
+        if nstage > 2:      # (a tile is requested by stages 1 .. nstage-2)
+            m6 = s[:, 6] > 0
+            per = {n: s[m6, c] / s[m6, 6] for n, c in (('halo_request', 8), ('tap_dma+0_first_group', 9), ('tap_dma+1_first_group', 10),
+                                                       ('tap_dma+2_first_group', 11), ('tap_dma+3_first_group', 12), ('tap8_first_group', 13),
+                                                       ('barrier_wait', 14), ('stage', 15))}
+            row['later_stage_cycles'] = {'mean': {n: int(v.mean()) for n, v in per.items()}, 'median': {n: int(np.median(v)) for n, v in per.items()}}
         row['non_mfma_share_of_life'] = round(1.0 - row['mfma_issue_cycles_per_wave'] / max(1, row['cycles_mean']['life']), 3)
         rows.append(row)
         print(json.dumps(row), file=sys.stderr)

@@ -31,7 +31,7 @@ for k in ords:
     gx, gy = C.c_uint(0), C.c_uint(0)
     lib.hla_debug_conv_stamps_grid(C.byref(gx), C.byref(gy))
     nw = gx.value * gy.value * 4
-    s = buf[: nw * 8 * 8].cpu().numpy().view(np.uint64).reshape(nw, 8).astype(np.int64)
+    s = buf[: nw * 16 * 8].cpu().numpy().view(np.uint64).reshape(nw, 16).astype(np.int64)      # HLA_STAMP_N words per wave
     s = s[s[:, 5] > 0]
     seg = {'prologue': s[:, 1] - s[:, 0], 'stage0_issue': s[:, 2] - s[:, 1], 'stage0_barrier_wait': s[:, 3] - s[:, 2],
            'later_stages': s[:, 4] - s[:, 3], 'epilogue': s[:, 5] - s[:, 4], 'life': s[:, 5] - s[:, 0]}
