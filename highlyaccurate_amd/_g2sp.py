@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import _lib, utils
-from ._s2gp import _poses_arg, eligible_cost, loss_from_trace, loss_func, raise_like_reference  # noqa: F401
+from ._s2gp import _poses_arg, eligible_cost, loss_from_trace, loss_func, raise_like_reference, score_loss_tail  # noqa: F401
 from .VGG import VGGUnet, VGGUnet_G2S, vgg_backward_nhwc, vgg_forward_nhwc
 
 
@@ -42,6 +42,7 @@ class LM_G2SP(nn.Module):
         self.last_trace = None
         self.last_normal_eq = None
         self.keep_normal_eq = False
+        self.last_score_loss = None  # score_loss: costs [B,K+1] and sums [B,K+1,8] per scored level of the last call (entry 0: the true pose)
 
     def _structs(self, sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm):
         dev = sat_feats[0].device
@@ -163,6 +164,104 @@ class LM_G2SP(nn.Module):
         _lib.check(rc, 'hla_g2s_pose_score')
         return cost, sums
 
+    @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
+    def score_poses_bwd(self, sat_feats, grd_feats, grd_confs, camera_k, ori_hw, poses, level, sums, d_cost, sat_inv_norm=None,
+                        grd_inv_norm=None):
+        """Backward of ``score_poses`` (``hla_g2s_pose_score_bwd``, include/hla.h): the same map arguments, ``sums`` [B,K,8] of
+        the forward and ``d_cost`` [B,K] -> (d_sat [B,A,A,C], d_grd [B,h,w,C], d_conf [B,h,w] or None) of level ``level``, fp32
+        NHWC, with respect to the L2-normalised maps -- what ``vgg_backward_nhwc(..., scale_invariant=True)`` takes.  All three
+        are written by the call; poses get no gradient.  d_sat is bitwise reproducible, d_grd and d_conf (fp32 atomics) are not."""
+        B, L = sat_feats[0].shape[0], len(sat_feats)
+        p = _poses_arg(poses, B)
+        if not 0 <= int(level) < L:
+            raise ValueError(f'level must be in [0, {L}), got {level}')
+        _lib.require_gpu(sat_feats[0], 'sat_feats')
+        lib = _lib.load()
+        dev = sat_feats[0].device
+        l = int(level)
+        cfg, lv, Kc = self._structs(sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm)
+        p = p.to(dev).contiguous()
+        K = p.shape[1]
+        if tuple(sums.shape) != (B, K, 8) or sums.dtype != torch.float64 or tuple(d_cost.shape) != (B, K):
+            raise ValueError(f'expected sums [B,K,8] fp64 and d_cost [B,K] with B = {B}, K = {K}, got {tuple(sums.shape)} '
+                             f'{sums.dtype} and {tuple(d_cost.shape)}')
+        sums, dc = sums.to(dev).contiguous(), d_cost.to(dev).float().contiguous()
+        one = C.byref(lv[l])
+        d_sat, d_grd = torch.empty_like(sat_feats[l], dtype=torch.float32), torch.empty_like(grd_feats[l], dtype=torch.float32)
+        d_conf = torch.empty_like(grd_confs[l]) if cfg.using_weight else None
+        gr = _lib.S2GLevelGrad()
+        gr.d_sat_feat, gr.d_grd_feat, gr.d_grd_conf = d_sat.data_ptr(), d_grd.data_ptr(), d_conf.data_ptr() if d_conf is not None else 0
+        nbytes = lib.hla_g2s_pose_score_bwd_workspace_bytes(C.byref(cfg), one, B, K)
+        if nbytes == 0:
+            _lib.check(-1, 'hla_g2s_pose_score_bwd_workspace_bytes')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))
+        rc = lib.hla_g2s_pose_score_bwd(C.byref(cfg), one, C.byref(gr), _lib.ptr(Kc), oh, ow, _lib.ptr(p), K, _lib.ptr(sums),
+                                        _lib.ptr(dc), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
+        _lib.check(rc, 'hla_g2s_pose_score_bwd')
+        return d_sat, d_grd, d_conf
+
+    def _score_checks(self, what, sat_map, grd_img_left):
+        if getattr(self.args, 'dropout', 0):
+            raise NotImplementedError(f'{what} with args.dropout: a pose is scored on every pixel')
+        if self.proj == 'nn' and self.using_weight:
+            raise NotImplementedError('using_weight with proj=nn')
+        _lib.require_gpu(sat_map, 'sat_map')
+        _lib.require_gpu(grd_img_left, 'grd_img')
+        if sat_map.dim() != 4 or grd_img_left.dim() != 4 or sat_map.shape[1] != 3 or grd_img_left.shape[1] != 3:
+            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W], got {tuple(sat_map.shape)} and '
+                             f'{tuple(grd_img_left.shape)}')
+        self._check_images(sat_map, grd_img_left)
+        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img_left), ('parameters', self.damping))
+
+    @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
+    def score_candidates(self, sat_map, grd_img_left, left_camera_k, poses, levels=None):
+        """The matching term at ``poses`` ([K,3] or [B,K,3], normalised units) on the maps of the two images, differentiable with
+        respect to both extractors' parameters (not the poses): -> (costs, sums), a list of [B,K] fp32 costs and a list of
+        [B,K,8] fp64 sums, one entry per level in ``levels`` (default: every level).  Under autograd it is ONE autograd.Function:
+        both extractors with their activations saved, ``hla_g2s_pose_score`` per scored level; its backward runs
+        ``hla_g2s_pose_score_bwd`` per scored level and ``hla_vgg_backward`` for both extractors.  ``sums`` carry no gradient.
+        Without grad it is the inference extractors plus ``score_poses``."""
+        self._score_checks('score_candidates', sat_map, grd_img_left)
+        B = sat_map.shape[0]
+        cand = _poses_arg(poses, B).to(sat_map.device).contiguous()
+        lvls = tuple(range(self.level)) if levels is None else tuple(int(l) for l in levels)
+        if not lvls or len(set(lvls)) != len(lvls) or not all(0 <= l < self.level for l in lvls):
+            raise ValueError(f'levels must be distinct indices in [0, {self.level}), got {levels}')
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            names = [n for n, _ in self.named_parameters()]
+            params = [p for _, p in self.named_parameters()]
+            out = _G2sScoreFn.apply(self, names, sat_map, grd_img_left, left_camera_k, cand, lvls, *params)
+            n = len(lvls)
+            return list(out[:n]), list(out[n:])
+        with torch.no_grad():
+            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
+            grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_img_left, want_conf=bool(self.using_weight),
+                                                             defer_norm=True)
+            res = [self.score_poses(sat_feats, grd_feats, grd_confs, left_camera_k, grd_img_left.shape[-2:], cand, l, sat_inv,
+                                    grd_inv) for l in lvls]
+        return [r[0] for r in res], [r[1] for r in res]
+
+    def score_loss(self, sat_map, grd_img_left, left_camera_k, candidates, gt_shift_u, gt_shift_v, gt_heading, levels=None,
+                   min_in_view=0.5):
+        """Metric learning on the surface ``forward_search`` ranks with, ``LM_S2GP.score_loss`` in this direction (an extension,
+        in the form of the reference's triplet_loss, models_kitti.py:579-595): the pose list of every sample is the true pose
+        (gt_shift_u, gt_shift_v, gt_heading: [B] or [B,1], normalised units) followed by ``candidates`` ([K,3] or [B,K,3]); per
+        scored level (``levels``, default all)
+            loss_l = sum_b sum_k log(1 + exp(10 (cost[b, true] - cost[b, k]))) / (B K)
+        over the candidates that keep at least ``min_in_view`` of the sample's best pixel count in view (``eligible_cost``'s rule
+        over the K + 1 entries; the others contribute exactly zero), summed over the levels: a scalar that back-propagates into
+        both extractors through HIP kernels (``score_candidates``).  ``last_score_loss`` keeps the costs [B,K+1] and sums
+        [B,K+1,8] per level."""
+        self._score_checks('score_loss', sat_map, grd_img_left)
+        B, dev = sat_map.shape[0], sat_map.device
+        cand = _poses_arg(candidates, B, 'candidates').to(dev)
+        gt = torch.stack([torch.as_tensor(g, dtype=torch.float32).detach().to(dev).reshape(B)
+                          for g in (gt_shift_u, gt_shift_v, gt_heading)], dim=1)
+        poses = torch.cat([gt[:, None, :], cand], dim=1).contiguous()             # entry 0: the ground truth
+        costs, sums = self.score_candidates(sat_map, grd_img_left, left_camera_k, poses, levels)
+        return score_loss_tail(self, costs, sums, min_in_view)
+
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def forward_search(self, sat_map, grd_img_left, left_camera_k, candidates, top_m=1, score_level=0, min_in_view=0.5):
         """A pose search in front of the LM loop, the composition of ``S2GPBase._search`` in this direction: extract the features
@@ -280,4 +379,61 @@ class _G2sFn(torch.autograd.Function):
             if sync:
                 sync.finish(sync.start({'damping': grads['damping']}))
         ctx.state = None            # release the saved workspaces now, not when the loss tensor dies
+        return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)
+
+
+class _G2sScoreFn(torch.autograd.Function):
+    """``LM_G2SP.score_candidates`` under autograd.  forward: the costs [B,K] of every scored level, then their sums [B,K,8]
+    (non-differentiable); backward: parameter gradients of both extractors from HIP kernels."""
+
+    @staticmethod
+    def forward(ctx, model, names, sat_map, grd_img, camera_k, poses, levels, *params):
+        want_conf = bool(model.using_weight)
+        sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True,
+                                                     save_for_backward=True)
+        grd_feats, grd_confs, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=want_conf, defer_norm=True,
+                                                             save_for_backward=True)
+        if grd_confs is None:
+            grd_confs = [None] * len(grd_feats)
+        hw = tuple(grd_img.shape[-2:])
+        res = [model.score_poses(sat_feats, grd_feats, grd_confs, camera_k, hw, poses, l, sat_inv, grd_inv) for l in levels]
+        costs, sums = tuple(r[0] for r in res), tuple(r[1] for r in res)
+        ctx.model, ctx.names, ctx.levels = model, names, levels
+        ctx.state = (sat_feats, grd_feats, grd_confs, camera_k, hw, poses, sums, sat_inv, grd_inv, cs, cg)
+        ctx.mark_non_differentiable(*sums)
+        ctx.set_materialize_grads(False)
+        return costs + sums
+
+    @staticmethod
+    def backward(ctx, *d_out):
+        model = ctx.model
+        if ctx.state is None:
+            raise RuntimeError('backward through the same score_candidates call twice: the saved activations are released after '
+                               'the first backward; retain_graph is not supported by the HIP backward')
+        sat_feats, grd_feats, grd_confs, camera_k, hw, poses, sums, sat_inv, grd_inv, cs, cg = ctx.state
+        use_w = bool(model.using_weight) and all(c is not None for c in grd_confs)
+        d_sat, d_grd, d_conf = [None] * len(sat_feats), [None] * len(sat_feats), [None] * len(sat_feats)
+        for n, l in enumerate(ctx.levels):
+            if d_out[n] is None:            # this level's cost was not used downstream
+                continue
+            d_sat[l], d_grd[l], d_conf[l] = model.score_poses_bwd(sat_feats, grd_feats, grd_confs, camera_k, hw, poses, l, sums[n],
+                                                                  d_out[n], sat_inv, grd_inv)
+        for l in range(len(sat_feats)):     # an unscored level takes no part: zeros
+            if d_sat[l] is None:
+                d_sat[l], d_grd[l] = torch.zeros_like(sat_feats[l]), torch.zeros_like(grd_feats[l])
+            if use_w and d_conf[l] is None:
+                d_conf[l] = torch.zeros_like(grd_confs[l])
+        # the cost renormalises both maps: every d_map is orthogonal to its map (HLA_VGG_BWD_SCALE_INVARIANT, include/hla.h)
+        sync = getattr(model, 'grad_sync', None)
+        g_sat, flat_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, scale_invariant=True, flat=True)
+        h1 = sync.start({'SatFeatureNet.' + k: v for k, v in g_sat.items()}, flat_sat) if sync else None
+        g_grd, flat_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
+                                            scale_invariant=True, flat=True)
+        h2 = sync.start({'GrdFeatureNet.' + k: v for k, v in g_grd.items()}, flat_grd) if sync else None
+        if sync:
+            sync.finish(h1)
+            sync.finish(h2)
+        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
+        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
+        ctx.state = None                    # release the saved workspaces now
         return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)

@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 class HlaError(RuntimeError):
@@ -182,6 +182,11 @@ def load() -> C.CDLL:
     lib.hla_g2s_pose_score_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, i]
     lib.hla_g2s_pose_score.restype = i
     lib.hla_g2s_pose_score.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), vp, i, i, vp, i, vp, vp, vp, sz, i, vp]
+    lib.hla_g2s_pose_score_bwd_workspace_bytes.restype = sz
+    lib.hla_g2s_pose_score_bwd_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, i]
+    lib.hla_g2s_pose_score_bwd.restype = i
+    lib.hla_g2s_pose_score_bwd.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), C.POINTER(S2GLevelGrad), vp, i, i, vp, i,
+                                           vp, vp, vp, sz, i, vp]
     lib.hla_g2s_bwd_workspace_bytes.restype = sz
     lib.hla_g2s_bwd_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i]
     lib.hla_g2s_lm_solve_bwd.restype = i

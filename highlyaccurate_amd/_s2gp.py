@@ -704,17 +704,7 @@ class S2GPBase(nn.Module):
         gt = torch.stack([torch.as_tensor(g, dtype=torch.float32).detach().to(dev).reshape(B) for g in gt_pose], dim=1)
         poses = torch.cat([gt[:, None, :], cand], dim=1).contiguous()             # entry 0: the ground truth
         costs, sums = self.score_candidates(sat_map, grd_img, poses, levels, extra)
-        K = cand.shape[1]
-        loss = 0
-        for cost, s in zip(costs, sums):
-            # eligible_cost's in-view rule over the K + 1 entries; an ineligible negative contributes exactly zero
-            in_view = s[..., 6]
-            ok = (in_view >= float(min_in_view) * in_view.max(dim=1, keepdim=True).values)[:, 1:]
-            # models_kitti.py:592, 1622: log(1 + exp(10 (pos - neg))), averaged; cost <= 4 keeps the exponent below 40
-            t = torch.log(1 + torch.exp(10.0 * (cost[:, :1] - cost[:, 1:])))
-            loss = loss + torch.where(ok, t, torch.zeros_like(t)).sum() / (B * K)     # models_kitti.py:595: summed over the levels
-        self.last_score_loss = dict(costs=[c.detach() for c in costs], sums=sums)
-        return loss
+        return score_loss_tail(self, costs, sums, min_in_view)
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def _search(self, sat_map, grd_img, extra, candidates, top_m, score_level, min_in_view, level_first):
@@ -874,6 +864,22 @@ def eligible_cost(cost, sums, min_in_view):
     none = ~ok.any(dim=1)
     out[:, 0] = torch.where(none, torch.zeros_like(cost[:, 0]), out[:, 0])
     return out
+
+
+def score_loss_tail(model, costs, sums, min_in_view):
+    """The loss of ``score_loss`` in both directions, from the costs [B,K+1] and sums [B,K+1,8] of the scored levels (entry 0:
+    the true pose); ``model.last_score_loss`` keeps them."""
+    loss = 0
+    for cost, s in zip(costs, sums):
+        B, K = cost.shape[0], cost.shape[1] - 1
+        # eligible_cost's in-view rule over the K + 1 entries; an ineligible negative contributes exactly zero
+        in_view = s[..., 6]
+        ok = (in_view >= float(min_in_view) * in_view.max(dim=1, keepdim=True).values)[:, 1:]
+        # models_kitti.py:592, 1622: log(1 + exp(10 (pos - neg))), averaged; cost <= 4 keeps the exponent below 40
+        t = torch.log(1 + torch.exp(10.0 * (cost[:, :1] - cost[:, 1:])))
+        loss = loss + torch.where(ok, t, torch.zeros_like(t)).sum() / (B * K)     # models_kitti.py:595: summed over the levels
+    model.last_score_loss = dict(costs=[c.detach() for c in costs], sums=sums)
+    return loss
 
 
 def _poses_arg(poses, B: int, name: str = 'poses'):

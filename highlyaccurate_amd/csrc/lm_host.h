@@ -81,7 +81,7 @@ static inline LmSolveCfg lm_solve_cfg_of(const hla_s2g_config* cfg) {
 }
 
 // hla_s2g_level -> the dimension fields an argument struct shares with its kin (AccumArgs, RepairLevel, BwdAccumArgs, PsArgs;
-// G2sAccumArgs, G2sBwdAccumArgs, GpsArgs)
+// G2sAccumArgs, G2sBwdAccumArgs, GpsArgs, GpsbArgs)
 template <class Args>
 static inline void lm_fill_s2g_dims(Args& a, const hla_s2g_level& v, const LmTiling& t) {
   a.A = v.A; a.h = v.h; a.w = v.w; a.row0 = v.row0; a.npix = t.npix; a.TP = t.TP; a.nt = t.nt;

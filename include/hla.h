@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 31
+#define HLA_ABI_VERSION 32
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -554,6 +554,32 @@ int hla_s2g_lm_solve_bwd(const hla_s2g_config* cfg, const hla_s2g_level* levels,
 size_t hla_s2g_pose_score_bwd_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K);
 int hla_s2g_pose_score_bwd(const hla_s2g_config* cfg, const hla_s2g_level* level, const hla_s2g_level_grad* grad,
                            const float* R_FL, const float* T_FL, const float* poses, int K, const double* sums,
+                           const float* d_cost, void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
+
+/* Backward of hla_g2s_pose_score (no reference function; what autograd gives for the cost formula of hla_g2s_pose_score -- the
+ * ground -> satellite counterpart of the surface the reference trains by metric learning with triplet_loss,
+ * models_kitti.py:579-595).  Given d(loss)/d(cost) it writes d(loss)/d(the level's maps); poses get no gradient.
+ *   cfg, level, camera_k, ori_h, ori_w, poses, K   the forward's (fp32 maps, grd_row_skip 0, depth NULL, ford 0); also cfg->keep
+ *                                                  NULL and cfg->deterministic 0
+ *   sums   [B,K,8] fp64   the forward's output;   d_cost [B,K] fp32
+ *   grad   d_sat_feat [B,A,A,C], d_grd_feat [B,h,w,C] and, iff cfg->using_weight, d_grd_conf [B,h,w]: fp32 NHWC, all OVERWRITTEN
+ *          (the call clears what it accumulates into; without using_weight d_grd_conf is not touched).  Gradients are taken
+ *          w.r.t. the L2-NORMALISED maps (inv_norm x stored map), hla_g2s_lm_solve_bwd's convention: hla_vgg_backward with
+ *          HLA_VGG_BWD_SCALE_INVARIANT consumes them as they are
+ * With f, s, w as in the forward, N = sums[0], S = sums[1], a = sums[3], e = sums[4], c = sums[5], nf = max(sqrt N, 1e-6),
+ * ns = max(sqrt S, 1e-6), per satellite pixel IN VIEW (the forward's decision, bit for bit) and per channel:
+ *   d cost/d f = 2 w f/nf^2 - 2 a f/nf^4 - 2 w s/(nf ns) + 2 c f/(nf^3 ns)     (to the four ground taps, clamped-corner weights)
+ *   d cost/d s = 2 w s/ns^2 - 2 e s/ns^4 - 2 w f/(nf ns) + 2 c s/(ns^3 nf)     (on the satellite pixel itself)
+ *   d cost/d w = sum_channels (f/nf - s/ns)^2                                  (to the same four taps of grd_conf)
+ * where a clamped norm is a constant (its second and fourth term are absent), and without weights the first two terms, which
+ * cancel identically, are not formed.  A pixel out of view gets nothing for that hypothesis; sums[7] does not enter.  The
+ * per-(sample, hypothesis) scalars are formed in fp64 from `sums` and rounded once.  d_sat_feat is summed over k in ascending
+ * order in registers and every element is stored once: the same bits from run to run and whatever B is.  d_grd_feat and
+ * d_grd_conf are summed with fp32 atomics: NOT bitwise reproducible.  A hypothesis with d_cost == 0 or sums[6] == 0 costs no map
+ * traffic.  hla_g2s_pose_score_bwd_workspace_bytes returns 0 and sets the last error on bad arguments. */
+size_t hla_g2s_pose_score_bwd_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* level, int B, int K);
+int hla_g2s_pose_score_bwd(const hla_s2g_config* cfg, const hla_s2g_level* level, const hla_s2g_level_grad* grad,
+                           const float* camera_k, int ori_h, int ori_w, const float* poses, int K, const double* sums,
                            const float* d_cost, void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
 
 /* Backward of hla_g2s_lm_solve (autograd through the same reference lines).  grads[l]: d_sat_feat [B,A,A,C] and
