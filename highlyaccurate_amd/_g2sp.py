@@ -42,6 +42,7 @@ class LM_G2SP(nn.Module):
         self.last_trace = None
         self.last_normal_eq = None
         self.keep_normal_eq = False
+        self.last_corr = None        # corr: the correlation surface [B,Ny,Nx] fp32 of every level of the last call (an extension)
         self.last_score_loss = None  # score_loss: costs [B,K+1] and sums [B,K+1,8] per scored level of the last call (entry 0: the true pose)
 
     def _structs(self, sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm):
@@ -295,6 +296,18 @@ class LM_G2SP(nn.Module):
             pose = finals.gather(1, best[:, None, None].expand(-1, 1, 3))[:, 0]
         self.last_search = dict(cost=cost, sums=sums, start_index=start_index, traces=traces, final_cost=final_cost, best=best)
         return pose[:, 1], pose[:, 0], pose[:, 2]
+
+    def corr(self, sat_map, grd_img_left, left_camera_k, gt_shift_u=None, gt_shift_v=None, gt_heading=None, mode='train',
+             file_name=None, gt_depth=None):
+        """models_kitti.py:501-577, the reference's signature: the dense translation search.  Per level the ground map is projected
+        at the zero pose, centre-cropped by the shift ranges, normalised and correlated with the satellite map at every shift
+        (``_g2s_corr``; ``hla_g2s_corr``, include/hla.h).  mode='train' -> the triplet loss (579-595) summed over the levels, a
+        scalar that back-propagates into both extractors; any other mode -> (pred_u [B], pred_v [B]), the argmin shift of the
+        LAST level in metres, computed without autograd.  ``self.last_corr`` keeps corr [B,Ny,Nx] of every level.  The
+        correlation reads fp32 maps in every precision mode; gt_heading, file_name and gt_depth are ignored as in the reference;
+        proj='nn' raises NotImplementedError."""
+        from . import _g2s_corr
+        return _g2s_corr.corr(self, sat_map, grd_img_left, left_camera_k, gt_shift_u, gt_shift_v, mode)
 
     def _check_images(self, sat_map, grd_img_left):
         if sat_map.dim() != 4 or grd_img_left.dim() != 4 or sat_map.shape[0] != grd_img_left.shape[0] \

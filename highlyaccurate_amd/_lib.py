@@ -227,6 +227,16 @@ def load() -> C.CDLL:
     lib.hla_orien_triplet_loss.argtypes = [vp, vp, ll, dbl, dbl, vp, i, i, i, vp]
     lib.hla_orien_triplet_loss_bwd.restype = i
     lib.hla_orien_triplet_loss_bwd.argtypes = [vp, vp, ll, dbl, dbl, vp, vp, i, i, vp]
+    lib.hla_g2s_corr_workspace_bytes.restype = sz
+    lib.hla_g2s_corr_workspace_bytes.argtypes = [i, i, i, i, i]
+    lib.hla_g2s_corr.restype = i
+    lib.hla_g2s_corr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+    lib.hla_g2s_corr_bwd.restype = i
+    lib.hla_g2s_corr_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+    lib.hla_g2s_corr_triplet_loss.restype = i
+    lib.hla_g2s_corr_triplet_loss.argtypes = [vp, vp, ll, vp, ll, dbl, dbl, dbl, vp, i, i, i, i, vp]
+    lib.hla_g2s_corr_triplet_loss_bwd.restype = i
+    lib.hla_g2s_corr_triplet_loss_bwd.argtypes = [vp, vp, ll, vp, ll, dbl, dbl, dbl, vp, vp, i, i, i, vp]
     lib.hla_prof_enable.restype = i
     lib.hla_prof_enable.argtypes = [i]
     lib.hla_prof_kernel_name.restype = C.c_char_p

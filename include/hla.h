@@ -686,11 +686,57 @@ int hla_orien_triplet_loss_bwd(const float* corr, const float* gt_heading, long 
                                double degree_per_pixel, const float* g_loss, float* d_corr, int B, int S, hla_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * LM_G2SP.corr  (models_kitti.py:501-577) and triplet_loss (579-595): the dense translation search
+ * ------------------------------------------------------------------------- */
+/* One level of corr behind the projection.  The caller samples the centre crop of the ground map projected at the zero pose
+ * (project_grd_to_map, 163-287; TF.center_crop to crop_H x crop_W, 546-548) with hla_grid_sample from the raw ground map, and
+ * takes d_g2s back through hla_orien_window_bwd.
+ *   sat           [B,A,A,C] NHWC fp32;  sat_inv_norm [B] fp64 or NULL: sat is multiplied by it (HLA_VGG_DEFER_NORM); s below
+ *   g2s           [B,Hc,Wc,C] NHWC fp32, the sampled crop before F.normalize;  g2s_inv_norm [B] fp64 or NULL likewise (sampling
+ *                 is linear).  With f = g2s_inv_norm * g2s:  g = f / max(||f||_2, 1e-12) per sample (F.normalize, 549)
+ *   Ny = A - Hc + 1, Nx = A - Wc + 1   the shifts (the reference's conv2d output)
+ *   dot   [B,Ny,Nx] fp64 out   sum_{y<Hc,x<Wc,c} g[b,y,x,c] s[b,y+dy,x+dx,c]      (the grouped conv2d, 551-552)
+ *   E     [B,Ny,Nx] fp64 out   sum_{y<Hc,x<Wc,c} s[b,y+dy,x+dx,c]^2               (avg_pool2d, divisor_override=1, and the channel sum, 554-555)
+ *   gnorm [B]       fp64 out   ||f||_2
+ *   corr  [B,Ny,Nx] fp32 out   2 - 2 dot / max(sqrt(E), 1e-6)                     (556-557), rounded once
+ * The contraction runs on the fp32-input MFMA; no fp32 accumulator collects more than 4096 products before it is added to an
+ * fp64 sum, and the partial sums of different workgroups are stored and added in fp64 in a fixed order: the result does not
+ * depend on B, on the grid or on the run.  C in {16, 64, 128, 256}; 1 <= Hc, Wc <= A <= 16384; B <= 65535.
+ * workspace: hla_g2s_corr_workspace_bytes (serves both calls; 0 with hla_last_error set for sizes that are refused). */
+size_t hla_g2s_corr_workspace_bytes(int B, int A, int Hc, int Wc, int C);
+int hla_g2s_corr(const float* sat, const float* g2s, const double* sat_inv_norm, const double* g2s_inv_norm, double* dot, double* E,
+                 double* gnorm, float* corr, void* workspace, size_t workspace_bytes, int B, int A, int Hc, int Wc, int C,
+                 hla_stream_t stream);
+/* Backward (what autograd derives from 549-557): d_corr [B,Ny,Nx] fp32 and the forward's dot, E, gnorm.  With D = max(sqrt(E), 1e-6),
+ * ddot = -2 d_corr / D and beta = d_corr dot / D^3 where sqrt(E) > 1e-6, else 0 (no gradient flows through a clamped E):
+ *   d_sat [B,A,A,C]    w.r.t. s:  sum_{dy,dx} ddot[dy,dx] g[r-dy,x-dx,c] + 2 s[r,x,c] Bsum[r,x],  Bsum the sum of beta over the shifts
+ *                      whose window covers (r,x)
+ *   d_g2s [B,Hc,Wc,C]  w.r.t. f:  (d_g - g (g . d_g)) / ||f||,  d_g[y,x,c] = sum_{dy,dx} ddot[dy,dx] s[y+dy,x+dx,c]; zero through the
+ *                      norm where ||f|| is clamped
+ * Both are WRITTEN (no zero fill by the caller), in gather form with fp64 sums: no atomics, bitwise reproducible. */
+int hla_g2s_corr_bwd(const float* sat, const float* g2s, const double* sat_inv_norm, const double* g2s_inv_norm, const double* dot,
+                     const double* E, const double* gnorm, const float* d_corr, float* d_sat, float* d_g2s, void* workspace,
+                     size_t workspace_bytes, int B, int A, int Hc, int Wc, int C, hla_stream_t stream);
+/* triplet_loss of one level (579-595): sum_{b,dy,dx} log(1 + exp(10 (corr[b,h_b,w_b] - corr[b,dy,dx]))) / (B (Ny Nx - 1)) with
+ *   w_b = round(Nx/2 + gt_shift_u[b] * shift_range_lon / meters_per_pixel),  h_b = round(Ny/2 - gt_shift_v[b] * shift_range_lat / meters_per_pixel)
+ * (587-588: fp32 like the reference's tensors, Nx/2 a true division, half to even).  h in [-Ny,Ny) and w in [-Nx,Nx) wrap like a
+ * Python index; outside, where the reference raises, the loss is NaN.  meters_per_pixel is the level's
+ * utils.get_meter_per_pixel() * 2^(3-level).  loss[0] (fp32) is written, or added to when accumulate != 0 (the sum over the levels,
+ * 595).  Element b of gt_shift_u at gt_shift_u[b * gt_u_stride], of gt_shift_v likewise. */
+int hla_g2s_corr_triplet_loss(const float* corr, const float* gt_shift_u, long long gt_u_stride, const float* gt_shift_v,
+                              long long gt_v_stride, double shift_range_lat, double shift_range_lon, double meters_per_pixel,
+                              float* loss, int accumulate, int B, int Ny, int Nx, hla_stream_t stream);
+/* d_corr [B,Ny,Nx] fp32 (written) = g_loss[0] * d(loss of this level)/d(corr) */
+int hla_g2s_corr_triplet_loss_bwd(const float* corr, const float* gt_shift_u, long long gt_u_stride, const float* gt_shift_v,
+                                  long long gt_v_stride, double shift_range_lat, double shift_range_lon, double meters_per_pixel,
+                                  const float* g_loss, float* d_corr, int B, int Ny, int Nx, hla_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Measurement hooks (no reference counterpart; used by bench.py for the roofline numbers).
  * When enabled, every kernel launch of the entry points above is bracketed by two hipEvents
  * on its own stream; hla_prof_fetch synchronises them and returns one record per launch.
  * ------------------------------------------------------------------------- */
-#define HLA_PROF_NKERNELS 18 /* (17 before lm_repair_loop got an id of its own: a caller that sizes a table by it recompiles) */
+#define HLA_PROF_NKERNELS 20 /* (17 before lm_repair_loop got an id of its own, 18 before hla_g2s_corr's two: a caller that sizes a table by it recompiles) */
 typedef struct hla_prof_record {
   int kernel_id;  /* index for hla_prof_kernel_name */
   float ms;       /* event-to-event duration on the launch stream */
