@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib, utils
-from .VGG import vgg_backward_nhwc, vgg_forward_nhwc
+from ._autograd import extract_saved, extractor_grads, grad_params, take_state
 
 CHANNELS = (16, 64, 128, 256)
 
@@ -197,8 +197,7 @@ class _G2sCorrFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, names, sat_map, grd_img, camera_k, gt_u, gt_v, *params):
-        sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True, save_for_backward=True)
-        grd_feats, _, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=False, defer_norm=True, save_for_backward=True)
+        sat_feats, sat_inv, grd_feats, _, grd_inv, cs, cg = extract_saved(model, sat_map, grd_img, False)
         lv = levels_forward(model, sat_feats, sat_inv, grd_feats, grd_inv, camera_k, tuple(grd_img.shape[-2:]))
         loss = _loss_of(model, lv, gt_u, gt_v, sat_map.device)
         model.last_corr = [c.detach() for c, *_ in lv]
@@ -210,9 +209,7 @@ class _G2sCorrFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss):
         model = ctx.model
-        if ctx.state is None:
-            raise RuntimeError('backward through the same corr forward twice: the saved activations are released after the first')
-        sat_feats, sat_inv, grd_feats, grd_inv, cs, cg, lv = ctx.state
+        sat_feats, sat_inv, grd_feats, grd_inv, cs, cg, lv = take_state(ctx, 'corr forward')
         g = g_loss.float().reshape(1).contiguous()
         d_sat, d_grd = [], []
         for l, (corr, mpp, g2s, grid, saved) in enumerate(lv):
@@ -220,17 +217,7 @@ class _G2sCorrFn(torch.autograd.Function):
             ds, dg = corr_backward(sat_feats[l], g2s, sat_inv[l], grd_inv[l], saved, d_corr)
             d_sat.append(ds)
             d_grd.append(sample_crop_bwd(grd_feats[l], grid, dg))
-        sync = getattr(model, 'grad_sync', None)
-        g_sat, flat_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, flat=True)
-        h1 = sync.start({'SatFeatureNet.' + k: v for k, v in g_sat.items()}, flat_sat) if sync else None
-        g_grd, flat_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, flat=True)
-        h2 = sync.start({'GrdFeatureNet.' + k: v for k, v in g_grd.items()}, flat_grd) if sync else None
-        if sync:
-            sync.finish(h1)
-            sync.finish(h2)
-        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
-        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
-        ctx.state = None
+        grads = extractor_grads(model, cs, cg, d_sat, d_grd)
         return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)
 
 
@@ -239,12 +226,7 @@ def corr(model, sat_map, grd_img, camera_k, gt_shift_u, gt_shift_v, mode):
     if model.proj == 'nn':
         # the reference would run the geometric projection on the FOLDED maps of VGGUnet_G2S: defined, plainly unintended
         raise NotImplementedError("corr with proj='nn': the reference projects the folded ground maps geometrically there; refused")
-    _lib.require_gpu(sat_map, 'corr sat_map')
-    _lib.require_gpu(grd_img, 'corr grd_img_left')
     model._check_images(sat_map, grd_img)
-    if sat_map.shape[1] != 3 or grd_img.shape[1] != 3:
-        raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W], got {tuple(sat_map.shape)} and {tuple(grd_img.shape)}')
-    _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', model.damping))
     dev = sat_map.device
     ori_hw = tuple(grd_img.shape[-2:])
     train = mode == 'train'
@@ -252,13 +234,11 @@ def corr(model, sat_map, grd_img, camera_k, gt_shift_u, gt_shift_v, mode):
         if gt_shift_u is None or gt_shift_v is None:
             raise ValueError("corr(mode='train') needs gt_shift_u and gt_shift_v")
         gt_u, gt_v = _gt_column(gt_shift_u, dev), _gt_column(gt_shift_v, dev)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters()):
-            names = [k for k, _ in model.named_parameters()]
-            params = [p for _, p in model.named_parameters()]
-            return _G2sCorrFn.apply(model, names, sat_map, grd_img, camera_k, gt_u, gt_v, *params)
+        under = grad_params(model)
+        if under:
+            return _G2sCorrFn.apply(model, under[0], sat_map, grd_img, camera_k, gt_u, gt_v, *under[1])
     with torch.no_grad():
-        sat_feats, _, sat_inv = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
-        grd_feats, _, grd_inv = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=False, defer_norm=True)
+        sat_feats, sat_inv, grd_feats, _, grd_inv = model._features(sat_map, grd_img, False)
         lv = levels_forward(model, sat_feats, sat_inv, grd_feats, grd_inv, camera_k, ori_hw)
         model.last_corr = [c for c, *_ in lv]
         if train:

@@ -12,9 +12,11 @@ import ctypes as C
 import torch
 from torch import nn
 
-from . import _lib, utils
-from ._s2gp import _poses_arg, eligible_cost, loss_from_trace, loss_func, raise_like_reference, score_loss_tail  # noqa: F401
-from .VGG import VGGUnet, VGGUnet_G2S, vgg_backward_nhwc, vgg_forward_nhwc
+from . import _lib, _pose, utils
+from ._autograd import extract_saved, extractor_grads, grad_params, take_state
+from ._pose import _poses_arg
+from ._s2gp import loss_from_trace, raise_like_reference
+from .VGG import VGGUnet, VGGUnet_G2S, vgg_forward_nhwc
 
 
 class LM_G2SP(nn.Module):
@@ -135,6 +137,12 @@ class LM_G2SP(nn.Module):
         _lib.check(rc, 'hla_g2s_lm_solve_bwd')
         return d_sat, d_grd, d_conf, d_lambda
 
+    def _score_structs(self, sat_feats, grd_feats, grd_confs, camera_k, ori_hw, sat_inv_norm, grd_inv_norm):
+        """``_pose.score_poses``' structs: (cfg, lv, (camera_k, ori_h, ori_w)), what ``hla_g2s_pose_score[_bwd]`` take."""
+        cfg, lv, Kc = self._structs(sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm)
+        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))      # (the in-plane warp reads neither)
+        return cfg, lv, (Kc, oh, ow)
+
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def score_poses(self, sat_feats, grd_feats, grd_confs, camera_k, ori_hw, poses, level, sat_inv_norm=None, grd_inv_norm=None):
         """The matching term of this direction at given poses, on feature maps extracted once (``hla_g2s_pose_score``,
@@ -142,28 +150,8 @@ class LM_G2SP(nn.Module):
         [B,K,3], (shift_u, shift_v, heading) in normalised units; ``level`` indexes the lists.  Returns (cost [B,K] fp32, sums
         [B,K,8] fp64): over the satellite pixels whose projection is in view sum f^2, sum s^2, sum f s, the same three weighted,
         their number, and sum s^2 over all pixels; cost = sum w (f/||f|| - s/||s||)^2 over the overlap, +inf with nothing in view."""
-        B, L = sat_feats[0].shape[0], len(sat_feats)
-        p = _poses_arg(poses, B)
-        if not 0 <= int(level) < L:
-            raise ValueError(f'level must be in [0, {L}), got {level}')
-        _lib.require_gpu(sat_feats[0], 'sat_feats')
-        lib = _lib.load()
-        dev = sat_feats[0].device
-        cfg, lv, Kc = self._structs(sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm)
-        p = p.to(dev).contiguous()
-        K = p.shape[1]
-        one = C.byref(lv[int(level)])
-        cost = torch.empty(B, K, device=dev, dtype=torch.float32)
-        sums = torch.empty(B, K, 8, device=dev, dtype=torch.float64)
-        nbytes = lib.hla_g2s_pose_score_workspace_bytes(C.byref(cfg), one, B, K)
-        if nbytes == 0:
-            _lib.check(-1, 'hla_g2s_pose_score_workspace_bytes')
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))
-        rc = lib.hla_g2s_pose_score(C.byref(cfg), one, _lib.ptr(Kc), oh, ow, _lib.ptr(p), K, _lib.ptr(sums), _lib.ptr(cost),
-                                    _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
-        _lib.check(rc, 'hla_g2s_pose_score')
-        return cost, sums
+        structs = lambda: self._score_structs(sat_feats, grd_feats, grd_confs, camera_k, ori_hw, sat_inv_norm, grd_inv_norm)
+        return _pose.score_poses('hla_g2s_pose_score', structs, sat_feats, poses, level)
 
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def score_poses_bwd(self, sat_feats, grd_feats, grd_confs, camera_k, ori_hw, poses, level, sums, d_cost, sat_inv_norm=None,
@@ -172,48 +160,21 @@ class LM_G2SP(nn.Module):
         the forward and ``d_cost`` [B,K] -> (d_sat [B,A,A,C], d_grd [B,h,w,C], d_conf [B,h,w] or None) of level ``level``, fp32
         NHWC, with respect to the L2-normalised maps -- what ``vgg_backward_nhwc(..., scale_invariant=True)`` takes.  All three
         are written by the call; poses get no gradient.  d_sat is bitwise reproducible, d_grd and d_conf (fp32 atomics) are not."""
-        B, L = sat_feats[0].shape[0], len(sat_feats)
-        p = _poses_arg(poses, B)
-        if not 0 <= int(level) < L:
-            raise ValueError(f'level must be in [0, {L}), got {level}')
-        _lib.require_gpu(sat_feats[0], 'sat_feats')
-        lib = _lib.load()
-        dev = sat_feats[0].device
-        l = int(level)
-        cfg, lv, Kc = self._structs(sat_feats, grd_feats, grd_confs, camera_k, sat_inv_norm, grd_inv_norm)
-        p = p.to(dev).contiguous()
-        K = p.shape[1]
-        if tuple(sums.shape) != (B, K, 8) or sums.dtype != torch.float64 or tuple(d_cost.shape) != (B, K):
-            raise ValueError(f'expected sums [B,K,8] fp64 and d_cost [B,K] with B = {B}, K = {K}, got {tuple(sums.shape)} '
-                             f'{sums.dtype} and {tuple(d_cost.shape)}')
-        sums, dc = sums.to(dev).contiguous(), d_cost.to(dev).float().contiguous()
-        one = C.byref(lv[l])
-        d_sat, d_grd = torch.empty_like(sat_feats[l], dtype=torch.float32), torch.empty_like(grd_feats[l], dtype=torch.float32)
-        d_conf = torch.empty_like(grd_confs[l]) if cfg.using_weight else None
-        gr = _lib.S2GLevelGrad()
-        gr.d_sat_feat, gr.d_grd_feat, gr.d_grd_conf = d_sat.data_ptr(), d_grd.data_ptr(), d_conf.data_ptr() if d_conf is not None else 0
-        nbytes = lib.hla_g2s_pose_score_bwd_workspace_bytes(C.byref(cfg), one, B, K)
-        if nbytes == 0:
-            _lib.check(-1, 'hla_g2s_pose_score_bwd_workspace_bytes')
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        oh, ow = (0, 0) if self.proj == 'nn' else (int(ori_hw[0]), int(ori_hw[1]))
-        rc = lib.hla_g2s_pose_score_bwd(C.byref(cfg), one, C.byref(gr), _lib.ptr(Kc), oh, ow, _lib.ptr(p), K, _lib.ptr(sums),
-                                        _lib.ptr(dc), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
-        _lib.check(rc, 'hla_g2s_pose_score_bwd')
-        return d_sat, d_grd, d_conf
+        structs = lambda: self._score_structs(sat_feats, grd_feats, grd_confs, camera_k, ori_hw, sat_inv_norm, grd_inv_norm)
+        return _pose.score_poses_bwd('hla_g2s_pose_score_bwd', structs, sat_feats, grd_feats, grd_confs, poses, level, sums, d_cost)
+
+    def _features(self, sat_map, grd_img_left, want_conf):
+        """Both extractors of the inference path, normalisation deferred: (sat_feats, sat_inv, grd_feats, grd_confs, grd_inv)."""
+        sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
+        grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_img_left, want_conf=want_conf, defer_norm=True)
+        return sat_feats, sat_inv, grd_feats, grd_confs, grd_inv
 
     def _score_checks(self, what, sat_map, grd_img_left):
         if getattr(self.args, 'dropout', 0):
             raise NotImplementedError(f'{what} with args.dropout: a pose is scored on every pixel')
         if self.proj == 'nn' and self.using_weight:
             raise NotImplementedError('using_weight with proj=nn')
-        _lib.require_gpu(sat_map, 'sat_map')
-        _lib.require_gpu(grd_img_left, 'grd_img')
-        if sat_map.dim() != 4 or grd_img_left.dim() != 4 or sat_map.shape[1] != 3 or grd_img_left.shape[1] != 3:
-            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W], got {tuple(sat_map.shape)} and '
-                             f'{tuple(grd_img_left.shape)}')
         self._check_images(sat_map, grd_img_left)
-        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img_left), ('parameters', self.damping))
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def score_candidates(self, sat_map, grd_img_left, left_camera_k, poses, levels=None):
@@ -224,21 +185,14 @@ class LM_G2SP(nn.Module):
         ``hla_g2s_pose_score_bwd`` per scored level and ``hla_vgg_backward`` for both extractors.  ``sums`` carry no gradient.
         Without grad it is the inference extractors plus ``score_poses``."""
         self._score_checks('score_candidates', sat_map, grd_img_left)
-        B = sat_map.shape[0]
-        cand = _poses_arg(poses, B).to(sat_map.device).contiguous()
-        lvls = tuple(range(self.level)) if levels is None else tuple(int(l) for l in levels)
-        if not lvls or len(set(lvls)) != len(lvls) or not all(0 <= l < self.level for l in lvls):
-            raise ValueError(f'levels must be distinct indices in [0, {self.level}), got {levels}')
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            names = [n for n, _ in self.named_parameters()]
-            params = [p for _, p in self.named_parameters()]
-            out = _G2sScoreFn.apply(self, names, sat_map, grd_img_left, left_camera_k, cand, lvls, *params)
-            n = len(lvls)
-            return list(out[:n]), list(out[n:])
+        cand = _poses_arg(poses, sat_map.shape[0]).to(sat_map.device).contiguous()
+        lvls = _pose.levels_arg(levels, self.level)
+        under = grad_params(self)
+        if under:
+            out = _G2sScoreFn.apply(self, under[0], sat_map, grd_img_left, left_camera_k, cand, lvls, *under[1])
+            return list(out[:len(lvls)]), list(out[len(lvls):])
         with torch.no_grad():
-            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
-            grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_img_left, want_conf=bool(self.using_weight),
-                                                             defer_norm=True)
+            sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img_left, bool(self.using_weight))
             res = [self.score_poses(sat_feats, grd_feats, grd_confs, left_camera_k, grd_img_left.shape[-2:], cand, l, sat_inv,
                                     grd_inv) for l in lvls]
         return [r[0] for r in res], [r[1] for r in res]
@@ -255,13 +209,9 @@ class LM_G2SP(nn.Module):
         both extractors through HIP kernels (``score_candidates``).  ``last_score_loss`` keeps the costs [B,K+1] and sums
         [B,K+1,8] per level."""
         self._score_checks('score_loss', sat_map, grd_img_left)
-        B, dev = sat_map.shape[0], sat_map.device
-        cand = _poses_arg(candidates, B, 'candidates').to(dev)
-        gt = torch.stack([torch.as_tensor(g, dtype=torch.float32).detach().to(dev).reshape(B)
-                          for g in (gt_shift_u, gt_shift_v, gt_heading)], dim=1)
-        poses = torch.cat([gt[:, None, :], cand], dim=1).contiguous()             # entry 0: the ground truth
+        poses = _pose.true_pose_first((gt_shift_u, gt_shift_v, gt_heading), candidates, sat_map.shape[0], sat_map.device)
         costs, sums = self.score_candidates(sat_map, grd_img_left, left_camera_k, poses, levels)
-        return score_loss_tail(self, costs, sums, min_in_view)
+        return _pose.score_loss_tail(self, costs, sums, min_in_view)
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def forward_search(self, sat_map, grd_img_left, left_camera_k, candidates, top_m=1, score_level=0, min_in_view=0.5):
@@ -270,31 +220,15 @@ class LM_G2SP(nn.Module):
         eligible ones (``eligible_cost``), keep the final pose that scores best at the finest level.  No autograd, no host sync,
         no random numbers.  -> (shift_lat[B], shift_lon[B], theta[B]) like ``forward(mode='test')``; ``last_search`` keeps cost,
         sums, start_index [B,top_m], traces [B,top_m,N_iters,L,3], final_cost [B,top_m] and best [B]."""
-        _lib.require_gpu(sat_map, 'sat_map')
-        _lib.require_gpu(grd_img_left, 'grd_img')
         self._check_images(sat_map, grd_img_left)
-        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img_left), ('parameters', self.damping))
-        B, M = sat_map.shape[0], int(top_m)
-        cand = _poses_arg(candidates, B, 'candidates').to(sat_map.device)
-        if not 1 <= M <= cand.shape[1]:
-            raise ValueError(f'top_m must be in [1, {cand.shape[1]}] (the number of candidates), got {top_m}')
+        cand, M = _pose.search_candidates(candidates, top_m, sat_map)
         with torch.no_grad():
-            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
-            grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_img_left, want_conf=bool(self.using_weight),
-                                                             defer_norm=True)
+            sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img_left, bool(self.using_weight))
             hw = grd_img_left.shape[-2:]
             score = lambda poses, level: self.score_poses(sat_feats, grd_feats, grd_confs, left_camera_k, hw, poses, level,
                                                           sat_inv, grd_inv)
-            cost, sums = score(cand, score_level)
-            start_index = torch.topk(eligible_cost(cost, sums, min_in_view), M, dim=1, largest=False, sorted=True).indices
-            starts = cand.gather(1, start_index[:, :, None].expand(-1, -1, 3))
-            traces = torch.stack([self.lm_solve(sat_feats, grd_feats, grd_confs, left_camera_k, hw, starts[:, m].contiguous(),
-                                                sat_inv, grd_inv) for m in range(M)], dim=1)
-            finals = traces[:, :, -1, -1, :].contiguous()
-            final_cost, _ = score(finals, len(sat_feats) - 1)
-            best = final_cost.argmin(dim=1)
-            pose = finals.gather(1, best[:, None, None].expand(-1, 1, 3))[:, 0]
-        self.last_search = dict(cost=cost, sums=sums, start_index=start_index, traces=traces, final_cost=final_cost, best=best)
+            solve = lambda p0: self.lm_solve(sat_feats, grd_feats, grd_confs, left_camera_k, hw, p0, sat_inv, grd_inv)
+            pose = _pose.search(self, cand, M, score, solve, score_level, len(sat_feats) - 1, min_in_view)
         return pose[:, 1], pose[:, 0], pose[:, 2]
 
     def corr(self, sat_map, grd_img_left, left_camera_k, gt_shift_u=None, gt_shift_v=None, gt_heading=None, mode='train',
@@ -309,11 +243,8 @@ class LM_G2SP(nn.Module):
         from . import _g2s_corr
         return _g2s_corr.corr(self, sat_map, grd_img_left, left_camera_k, gt_shift_u, gt_shift_v, mode)
 
-    def _check_images(self, sat_map, grd_img_left):
-        if sat_map.dim() != 4 or grd_img_left.dim() != 4 or sat_map.shape[0] != grd_img_left.shape[0] \
-                or sat_map.shape[2] != sat_map.shape[3]:
-            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W], got {tuple(sat_map.shape)} and '
-                             f'{tuple(grd_img_left.shape)}')
+    def _check_images(self, sat_map, grd_img_left, gpu=True):
+        _lib.image_pair(sat_map, grd_img_left, self.damping, gpu)
         if self.proj == 'nn':
             A, (H, W) = sat_map.shape[-1], grd_img_left.shape[-2:]
             if 2 * H != A or W != 2 * A:
@@ -326,16 +257,14 @@ class LM_G2SP(nn.Module):
                 mode='train', file_name=None, gt_depth=None, init_pose=None):
         """mode='test' -> (shift_lat[B], shift_lon[B], theta[B]) (models_kitti.py:498-499);
         mode='train' -> the 14-tuple (486-496); under autograd its loss back-propagates through the HIP backward (_G2sFn)."""
-        self._check_images(sat_map, grd_img_left)
+        self._check_images(sat_map, grd_img_left, gpu=False)
         want_conf = bool(self.using_weight) or mode == 'train'
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            names = [n for n, _ in self.named_parameters()]
-            params = [p for _, p in self.named_parameters()]
-            out = _G2sFn.apply(self, names, sat_map, grd_img_left, left_camera_k, want_conf, init_pose, *params)
+        under = grad_params(self)
+        if under:
+            out = _G2sFn.apply(self, under[0], sat_map, grd_img_left, left_camera_k, want_conf, init_pose, *under[1])
             trace, grd_confs = out[0], (list(out[1:]) if want_conf else [None] * self.level)
         else:
-            sat_feats, _, sat_inv = vgg_forward_nhwc(self.SatFeatureNet, sat_map, want_conf=False, defer_norm=True)
-            grd_feats, grd_confs, grd_inv = vgg_forward_nhwc(self.GrdFeatureNet, grd_img_left, want_conf=want_conf, defer_norm=True)
+            sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img_left, want_conf)
             trace = self.lm_solve(sat_feats, grd_feats, grd_confs, left_camera_k, grd_img_left.shape[-2:], init_pose, sat_inv,
                                   grd_inv)
         shift_lons, shift_lats, thetas = trace[..., 0], trace[..., 1], trace[..., 2]        # models_kitti.py:470-472
@@ -352,10 +281,7 @@ class _G2sFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, names, sat_map, grd_img, camera_k, want_conf, init_pose, *params):
-        sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True,
-                                                     save_for_backward=True)
-        grd_feats, grd_confs, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=want_conf,
-                                                             defer_norm=True, save_for_backward=True)
+        sat_feats, sat_inv, grd_feats, grd_confs, grd_inv, cs, cg = extract_saved(model, sat_map, grd_img, want_conf)
         trace = model.lm_solve(sat_feats, grd_feats, grd_confs, camera_k, grd_img.shape[-2:], init_pose, sat_inv, grd_inv,
                                keep_normal_eq=True)
         ctx.model, ctx.names, ctx.init_pose = model, names, init_pose
@@ -369,29 +295,16 @@ class _G2sFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_trace, *unused):
         model = ctx.model
-        if ctx.state is None:
-            raise RuntimeError('backward through the same forward twice: the saved activations are released after the first '
-                               'backward; retain_graph is not supported by the HIP backward')
-        sat_feats, grd_feats, grd_confs, camera_k, ori_hw, trace, neq, sat_inv, grd_inv, cs, cg = ctx.state
+        sat_feats, grd_feats, grd_confs, camera_k, ori_hw, trace, neq, sat_inv, grd_inv, cs, cg = take_state(ctx)
         d_sat, d_grd, d_conf, d_lam = model.lm_backward(sat_feats, grd_feats, grd_confs, camera_k, ori_hw, trace, neq, d_trace,
                                                         ctx.init_pose, sat_inv, grd_inv)
-        sync = getattr(model, 'grad_sync', None)
-        g_sat, flat_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, flat=True)
-        h1 = sync.start({'SatFeatureNet.' + k: v for k, v in g_sat.items()}, flat_sat) if sync else None
         use_w = model.using_weight and all(c is not None for c in d_conf)
-        g_grd, flat_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
-                                            flat=True)
-        h2 = sync.start({'GrdFeatureNet.' + k: v for k, v in g_grd.items()}, flat_grd) if sync else None
-        if sync:
-            sync.finish(h1)
-            sync.finish(h2)
-        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
-        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
+        grads = extractor_grads(model, cs, cg, d_sat, d_grd, grd_confs if use_w else None, d_conf if use_w else None)
         if getattr(model.args, 'train_damping', 0):            # lambda is the parameter itself (models_kitti.py:357-358)
             grads['damping'] = d_lam.view(1, 3).float()
+            sync = getattr(model, 'grad_sync', None)
             if sync:
                 sync.finish(sync.start({'damping': grads['damping']}))
-        ctx.state = None            # release the saved workspaces now, not when the loss tensor dies
         return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)
 
 
@@ -401,13 +314,7 @@ class _G2sScoreFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, names, sat_map, grd_img, camera_k, poses, levels, *params):
-        want_conf = bool(model.using_weight)
-        sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True,
-                                                     save_for_backward=True)
-        grd_feats, grd_confs, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=want_conf, defer_norm=True,
-                                                             save_for_backward=True)
-        if grd_confs is None:
-            grd_confs = [None] * len(grd_feats)
+        sat_feats, sat_inv, grd_feats, grd_confs, grd_inv, cs, cg = extract_saved(model, sat_map, grd_img, bool(model.using_weight))
         hw = tuple(grd_img.shape[-2:])
         res = [model.score_poses(sat_feats, grd_feats, grd_confs, camera_k, hw, poses, l, sat_inv, grd_inv) for l in levels]
         costs, sums = tuple(r[0] for r in res), tuple(r[1] for r in res)
@@ -420,33 +327,10 @@ class _G2sScoreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *d_out):
         model = ctx.model
-        if ctx.state is None:
-            raise RuntimeError('backward through the same score_candidates call twice: the saved activations are released after '
-                               'the first backward; retain_graph is not supported by the HIP backward')
-        sat_feats, grd_feats, grd_confs, camera_k, hw, poses, sums, sat_inv, grd_inv, cs, cg = ctx.state
-        use_w = bool(model.using_weight) and all(c is not None for c in grd_confs)
-        d_sat, d_grd, d_conf = [None] * len(sat_feats), [None] * len(sat_feats), [None] * len(sat_feats)
-        for n, l in enumerate(ctx.levels):
-            if d_out[n] is None:            # this level's cost was not used downstream
-                continue
-            d_sat[l], d_grd[l], d_conf[l] = model.score_poses_bwd(sat_feats, grd_feats, grd_confs, camera_k, hw, poses, l, sums[n],
-                                                                  d_out[n], sat_inv, grd_inv)
-        for l in range(len(sat_feats)):     # an unscored level takes no part: zeros
-            if d_sat[l] is None:
-                d_sat[l], d_grd[l] = torch.zeros_like(sat_feats[l]), torch.zeros_like(grd_feats[l])
-            if use_w and d_conf[l] is None:
-                d_conf[l] = torch.zeros_like(grd_confs[l])
+        sat_feats, grd_feats, grd_confs, camera_k, hw, poses, sums, sat_inv, grd_inv, cs, cg = take_state(ctx, 'score_candidates call')
+        bwd = lambda n, l: model.score_poses_bwd(sat_feats, grd_feats, grd_confs, camera_k, hw, poses, l, sums[n], d_out[n],
+                                                 sat_inv, grd_inv)
+        d_sat, d_grd, d_conf = _pose.score_level_grads(model, bwd, ctx.levels, d_out, sat_feats, grd_feats, grd_confs)
         # the cost renormalises both maps: every d_map is orthogonal to its map (HLA_VGG_BWD_SCALE_INVARIANT, include/hla.h)
-        sync = getattr(model, 'grad_sync', None)
-        g_sat, flat_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, scale_invariant=True, flat=True)
-        h1 = sync.start({'SatFeatureNet.' + k: v for k, v in g_sat.items()}, flat_sat) if sync else None
-        g_grd, flat_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
-                                            scale_invariant=True, flat=True)
-        h2 = sync.start({'GrdFeatureNet.' + k: v for k, v in g_grd.items()}, flat_grd) if sync else None
-        if sync:
-            sync.finish(h1)
-            sync.finish(h2)
-        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
-        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
-        ctx.state = None                    # release the saved workspaces now
+        grads = extractor_grads(model, cs, cg, d_sat, d_grd, grd_confs if d_conf else None, d_conf, scale_invariant=True)
         return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)

@@ -318,6 +318,19 @@ def require_gpu(t: torch.Tensor, name: str) -> None:
         raise HlaError(f'{name} must live on the HIP device (got {t.device}); highlyaccurate_amd has no CPU path')
 
 
+def image_pair(sat_map, grd_img, param, gpu: bool = True) -> None:
+    """The image check of the models' entry points: sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, on the device of the
+    model (``param``: one of its parameters).  ``gpu=False`` where the extractors' own ``require_gpu`` is the first to speak."""
+    if gpu:
+        require_gpu(sat_map, 'sat_map')
+        require_gpu(grd_img, 'grd_img')
+    if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
+            or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
+        raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
+                         f'and {tuple(grd_img.shape)}')
+    same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', param))
+
+
 def ptr(t) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 

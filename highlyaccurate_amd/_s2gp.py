@@ -12,8 +12,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, utils
-from .VGG import VGGUnet, vgg_forward_nhwc, vgg_forward_pair_nhwc, vgg_backward_nhwc, vgg_fixup_nhwc, promised_cols
+from . import _lib, _pose, utils
+from ._autograd import _side_stream, extract_saved, extractor_grads, grad_params, take_state
+from ._pose import _poses_arg, eligible_cost, pose_grid  # noqa: F401  (the models, drivers and tests import these names here)
+from .VGG import VGGUnet, vgg_forward_nhwc, vgg_forward_pair_nhwc, vgg_fixup_nhwc, promised_cols
 
 KITTI_K = [[582.9802, 0.0, 496.2420], [0.0, 482.7076, 125.0034], [0.0, 0.0, 1.0]]      # models_kitti.py:657-660
 FORD_K_FL = [945.391406, 0.0, 855.502825, 0.0, 945.668274, 566.372868, 0.0, 0.0, 1.0]   # models_ford.py:116
@@ -592,33 +594,19 @@ class S2GPBase(nn.Module):
                                'from its last step to an earlier one; the result is not valid (run without args.deterministic_backward)')
         return d_sat, d_grd, d_conf, d_lambda[:3]
 
+    def _score_structs(self, sat_feats, grd_feats, grd_confs, grd_hw, extra, sat_inv_norm, grd_inv_norm):
+        """``_pose.score_poses``' structs: (cfg, lv, (R_FL, T_FL)), what ``hla_s2g_pose_score[_bwd]`` take."""
+        cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, 0, sat_inv_norm, grd_inv_norm)
+        return cfg, lv, (R_FL, T_FL)
+
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def score_poses(self, sat_feats, grd_feats, grd_confs, grd_hw, poses, level, extra=None, sat_inv_norm=None, grd_inv_norm=None):
         """The LM objective at given poses, on feature maps extracted once (``hla_s2g_pose_score``, include/hla.h): low-level like
         ``lm_solve``, with the same map arguments.  ``poses`` [K,3] (shared by the samples) or [B,K,3], (shift_u, shift_v, theta)
         in normalised units; ``level`` indexes the lists.  Returns (cost [B,K] fp32, sums [B,K,8] fp64): sum s^2, sum g^2,
         sum s g, the same three weighted, pixels in view, pixels with the ground mask."""
-        B, L = sat_feats[0].shape[0], len(sat_feats)
-        p = _poses_arg(poses, B)
-        if not 0 <= int(level) < L:
-            raise ValueError(f'level must be in [0, {L}), got {level}')
-        _lib.require_gpu(sat_feats[0], 'sat_feats')
-        lib = _lib.load()
-        dev = sat_feats[0].device
-        cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, 0, sat_inv_norm, grd_inv_norm)
-        p = p.to(dev).contiguous()
-        K = p.shape[1]
-        one = C.byref(lv[int(level)])
-        cost = torch.empty(B, K, device=dev, dtype=torch.float32)
-        sums = torch.empty(B, K, 8, device=dev, dtype=torch.float64)
-        nbytes = lib.hla_s2g_pose_score_workspace_bytes(C.byref(cfg), one, B, K)
-        if nbytes == 0:
-            _lib.check(-1, 'hla_s2g_pose_score_workspace_bytes')
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        rc = lib.hla_s2g_pose_score(C.byref(cfg), one, _lib.ptr(R_FL), _lib.ptr(T_FL), _lib.ptr(p), K, _lib.ptr(sums), _lib.ptr(cost),
-                                    _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
-        _lib.check(rc, 'hla_s2g_pose_score')
-        return cost, sums
+        structs = lambda: self._score_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, sat_inv_norm, grd_inv_norm)
+        return _pose.score_poses('hla_s2g_pose_score', structs, sat_feats, poses, level)
 
     @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
     def score_poses_bwd(self, sat_feats, grd_feats, grd_confs, grd_hw, poses, level, sums, d_cost, extra=None, sat_inv_norm=None,
@@ -628,34 +616,8 @@ class S2GPBase(nn.Module):
         level ``level``, fp32 NHWC, with respect to the L2-normalised maps -- what ``vgg_backward_nhwc(..., scale_invariant=True)``
         takes.  All three are written by the call (ground rows above row0 are zero); poses get no gradient.  d_grd and d_conf are
         bitwise reproducible, d_sat (fp32 atomics) is not."""
-        B, L = sat_feats[0].shape[0], len(sat_feats)
-        p = _poses_arg(poses, B)
-        if not 0 <= int(level) < L:
-            raise ValueError(f'level must be in [0, {L}), got {level}')
-        _lib.require_gpu(sat_feats[0], 'sat_feats')
-        lib = _lib.load()
-        dev = sat_feats[0].device
-        l = int(level)
-        cfg, lv, R_FL, T_FL = self._lm_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, 0, sat_inv_norm, grd_inv_norm)
-        p = p.to(dev).contiguous()
-        K = p.shape[1]
-        if tuple(sums.shape) != (B, K, 8) or sums.dtype != torch.float64 or tuple(d_cost.shape) != (B, K):
-            raise ValueError(f'expected sums [B,K,8] fp64 and d_cost [B,K] with B = {B}, K = {K}, got {tuple(sums.shape)} '
-                             f'{sums.dtype} and {tuple(d_cost.shape)}')
-        sums, dc = sums.to(dev).contiguous(), d_cost.to(dev).float().contiguous()
-        one = C.byref(lv[l])
-        d_sat, d_grd = torch.empty_like(sat_feats[l], dtype=torch.float32), torch.empty_like(grd_feats[l], dtype=torch.float32)
-        d_conf = torch.empty_like(grd_confs[l]) if cfg.using_weight else None
-        gr = _lib.S2GLevelGrad()
-        gr.d_sat_feat, gr.d_grd_feat, gr.d_grd_conf = d_sat.data_ptr(), d_grd.data_ptr(), d_conf.data_ptr() if d_conf is not None else 0
-        nbytes = lib.hla_s2g_pose_score_bwd_workspace_bytes(C.byref(cfg), one, B, K)
-        if nbytes == 0:
-            _lib.check(-1, 'hla_s2g_pose_score_bwd_workspace_bytes')
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        rc = lib.hla_s2g_pose_score_bwd(C.byref(cfg), one, C.byref(gr), _lib.ptr(R_FL), _lib.ptr(T_FL), _lib.ptr(p), K, _lib.ptr(sums),
-                                        _lib.ptr(dc), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
-        _lib.check(rc, 'hla_s2g_pose_score_bwd')
-        return d_sat, d_grd, d_conf
+        structs = lambda: self._score_structs(sat_feats, grd_feats, grd_confs, grd_hw, extra, sat_inv_norm, grd_inv_norm)
+        return _pose.score_poses_bwd('hla_s2g_pose_score_bwd', structs, sat_feats, grd_feats, grd_confs, poses, level, sums, d_cost)
 
     def _score_checks(self, what, sat_map, grd_img):
         if getattr(self.args, 'dropout', 0):
@@ -663,13 +625,7 @@ class S2GPBase(nn.Module):
                                       'half -- their objectives differ')
         if self.level != 3:
             raise NotImplementedError(f'{what} is built for args.level = 3 (x15, x18, x21), got level {self.level}')
-        _lib.require_gpu(sat_map, 'sat_map')
-        _lib.require_gpu(grd_img, 'grd_img')
-        if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
-                or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
-            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
-                             f'and {tuple(grd_img.shape)}')
-        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
+        _lib.image_pair(sat_map, grd_img, self.damping)
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def score_candidates(self, sat_map, grd_img, poses, levels=None, extra=None):
@@ -680,17 +636,12 @@ class S2GPBase(nn.Module):
         ``hla_s2g_pose_score_bwd`` per scored level and ``hla_vgg_backward`` for both extractors.  ``sums`` carry no gradient.
         Without grad it is the inference extractors plus ``score_poses``.  ``extra``: the Ford dict (R_FL, T_FL, side_m)."""
         self._score_checks('score_candidates', sat_map, grd_img)
-        B = sat_map.shape[0]
-        cand = _poses_arg(poses, B).to(sat_map.device).contiguous()
-        lvls = tuple(range(self.level)) if levels is None else tuple(int(l) for l in levels)
-        if not lvls or len(set(lvls)) != len(lvls) or not all(0 <= l < self.level for l in lvls):
-            raise ValueError(f'levels must be distinct indices in [0, {self.level}), got {levels}')
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            names = [n for n, _ in self.named_parameters()]
-            params = [p for _, p in self.named_parameters()]
-            out = _ScoreFn.apply(self, names, sat_map, grd_img, cand, lvls, extra, *params)
-            n = len(lvls)
-            return list(out[:n]), list(out[n:])
+        cand = _poses_arg(poses, sat_map.shape[0]).to(sat_map.device).contiguous()
+        lvls = _pose.levels_arg(levels, self.level)
+        under = grad_params(self)
+        if under:
+            out = _ScoreFn.apply(self, under[0], sat_map, grd_img, cand, lvls, extra, *under[1])
+            return list(out[:len(lvls)]), list(out[len(lvls):])
         with torch.no_grad():
             sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, bool(self.using_weight), False)
             res = [self.score_poses(sat_feats, grd_feats, grd_confs, grd_img.shape[-2:], cand, l, extra, sat_inv, grd_inv) for l in lvls]
@@ -699,12 +650,9 @@ class S2GPBase(nn.Module):
     def _score_loss(self, sat_map, grd_img, extra, candidates, gt_pose, levels, min_in_view):
         """``score_loss`` of both models.  gt_pose: (shift_u, shift_v, heading), each [B] or [B,1], normalised units."""
         self._score_checks('score_loss', sat_map, grd_img)
-        B, dev = sat_map.shape[0], sat_map.device
-        cand = _poses_arg(candidates, B, 'candidates').to(dev)
-        gt = torch.stack([torch.as_tensor(g, dtype=torch.float32).detach().to(dev).reshape(B) for g in gt_pose], dim=1)
-        poses = torch.cat([gt[:, None, :], cand], dim=1).contiguous()             # entry 0: the ground truth
+        poses = _pose.true_pose_first(gt_pose, candidates, sat_map.shape[0], sat_map.device)
         costs, sums = self.score_candidates(sat_map, grd_img, poses, levels, extra)
-        return score_loss_tail(self, costs, sums, min_in_view)
+        return _pose.score_loss_tail(self, costs, sums, min_in_view)
 
     @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
     def _search(self, sat_map, grd_img, extra, candidates, top_m, score_level, min_in_view, level_first):
@@ -713,32 +661,14 @@ class S2GPBase(nn.Module):
         if getattr(self.args, 'dropout', 0):
             raise NotImplementedError('forward_search with args.dropout: a pose is scored on every pixel, the dropout loop on a '
                                       'random half -- their objectives differ')
-        _lib.require_gpu(sat_map, 'sat_map')
-        _lib.require_gpu(grd_img, 'grd_img')
-        if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
-                or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
-            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
-                             f'and {tuple(grd_img.shape)}')
-        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
-        B, M = sat_map.shape[0], int(top_m)
-        cand = _poses_arg(candidates, B, 'candidates').to(sat_map.device)
-        if not 1 <= M <= cand.shape[1]:
-            raise ValueError(f'top_m must be in [1, {cand.shape[1]}] (the number of candidates), got {top_m}')
+        _lib.image_pair(sat_map, grd_img, self.damping)
+        cand, M = _pose.search_candidates(candidates, top_m, sat_map)
         with torch.no_grad():
             sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_img, bool(self.using_weight), False)
             hw = grd_img.shape[-2:]
             score = lambda poses, level: self.score_poses(sat_feats, grd_feats, grd_confs, hw, poses, level, extra, sat_inv, grd_inv)
-            cost, sums = score(cand, score_level)
-            start_index = torch.topk(eligible_cost(cost, sums, min_in_view), M, dim=1, largest=False, sorted=True).indices
-            starts = cand.gather(1, start_index[:, :, None].expand(-1, -1, 3))
-            traces = torch.stack([self.lm_solve(sat_feats, grd_feats, grd_confs, hw, extra, level_first, starts[:, m].contiguous(),
-                                                sat_inv, grd_inv) for m in range(M)], dim=1)
-            finals = traces[:, :, -1, -1, :].contiguous()
-            final_cost, _ = score(finals, len(sat_feats) - 1)
-            best = final_cost.argmin(dim=1)
-            pose = finals.gather(1, best[:, None, None].expand(-1, 1, 3))[:, 0]
-        self.last_search = dict(cost=cost, sums=sums, start_index=start_index, traces=traces, final_cost=final_cost, best=best)
-        return pose
+            solve = lambda p0: self.lm_solve(sat_feats, grd_feats, grd_confs, hw, extra, level_first, p0, sat_inv, grd_inv)
+            return _pose.search(self, cand, M, score, solve, score_level, len(sat_feats) - 1, min_in_view)
 
     def _features(self, sat_map, grd_img, want_conf, return_confs, sat_c32=0, col_state=None):
         """Both extractors of the inference path: (sat_feats, sat_inv, grd_feats, grd_confs, grd_inv), normalisation deferred.
@@ -803,20 +733,15 @@ class S2GPBase(nn.Module):
         Under autograd (training) the same kernels run inside one autograd.Function whose backward is the HIP
         backward pass (hla_s2g_lm_solve_bwd + hla_vgg_backward for both extractors).
         ``gt_depth`` [B,dH,dW] or None: ``lm_solve``'s depth map; it gets no gradient."""
-        if sat_map.dim() != 4 or grd_img.dim() != 4 or sat_map.shape[0] != grd_img.shape[0] or sat_map.shape[1] != 3 \
-                or grd_img.shape[1] != 3 or sat_map.shape[2] != sat_map.shape[3]:
-            raise ValueError(f'expected sat_map [B,3,A,A] and grd_img [B,3,H,W] with one B, got {tuple(sat_map.shape)} '
-                             f'and {tuple(grd_img.shape)}')
-        _lib.same_device(('sat_map', sat_map), ('grd_img', grd_img), ('parameters', self.damping))
+        _lib.image_pair(sat_map, grd_img, self.damping, gpu=False)
         gt_depth = self._depth_arg(gt_depth, sat_map.shape[0], sat_map.device)      # (checked before the extractors run)
         if self.polar and self.ford and level_first:
             # models_ford.py:935-950: the level-first loop has no proj branch and reads the bottom half of the polar table
             raise NotImplementedError("LM_S2GP_Ford(proj='polar') with level_first=1: the reference's level-first loop reads only "
                                       "the bottom half of the polar maps (it has no proj branch); that combination is not built")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            names = [n for n, _ in self.named_parameters()]
-            params = [p for _, p in self.named_parameters()]
-            out = _LocaliseFn.apply(self, names, sat_map, grd_img, want_conf, extra, level_first, init_pose, gt_depth, *params)
+        under = grad_params(self)
+        if under:
+            out = _LocaliseFn.apply(self, under[0], sat_map, grd_img, want_conf, extra, level_first, init_pose, gt_depth, *under[1])
             return out[0], list(out[1:]) if want_conf else [None] * self.level
         # (the two dense extractor passes on two streams measured 2 % slower than back to back: DESIGN.md 3.1)
         # args.sat_reach_crop (DESIGN.md 3.5): the satellite extractor skips the columns the configured pose range cannot reach;
@@ -835,61 +760,6 @@ class S2GPBase(nn.Module):
         if self.keep_features:
             self.last_features = (sat_feats, sat_inv, grd_feats, grd_inv)
         return trace, grd_confs
-
-
-def pose_grid(n_u: int, n_v: int, n_theta: int, span=(1., 1., 1.)):
-    """Candidate poses for ``forward_search``: a centred lattice over [-span, span] per component, in the normalised units of the
-    pose (1 = shift_range / rotation_range), [n_u * n_v * n_theta, 3] fp32 (shift_u, shift_v, theta).  The counts are odd so that
-    the zero pose is on the lattice; it is candidate 0, the others follow with shift_u outermost and theta innermost."""
-    axes = []
-    for name, n, s in zip(('n_u', 'n_v', 'n_theta'), (n_u, n_v, n_theta), span):
-        if int(n) != n or n < 1 or n % 2 == 0:
-            raise ValueError(f'{name} must be a positive odd count (the lattice is centred on the zero pose), got {n}')
-        half = (int(n) - 1) // 2
-        axes.append(torch.tensor([float(s) * i / half if half else 0.0 for i in range(-half, half + 1)], dtype=torch.float32))
-    grid = torch.cartesian_prod(*axes).reshape(-1, 3)
-    zero = (len(axes[0]) // 2 * len(axes[1]) + len(axes[1]) // 2) * len(axes[2]) + len(axes[2]) // 2
-    order = [zero] + [i for i in range(grid.shape[0]) if i != zero]
-    return grid[order].contiguous()
-
-
-def eligible_cost(cost, sums, min_in_view):
-    """The ranking rule of ``forward_search``: a candidate is eligible when its pixels in view (``sums[..., 6]``) reach
-    ``min_in_view`` times the sample's maximum over its candidates; the others get +inf.  (A pose with nothing in view scores 1,
-    below the ~2 of a mismatch, and would otherwise win.)  A sample without any eligible candidate keeps candidate 0.
-    cost [B,K], sums [B,K,8] -> [B,K] in cost's dtype."""
-    in_view = sums[..., 6]
-    ok = in_view >= float(min_in_view) * in_view.max(dim=1, keepdim=True).values
-    out = torch.where(ok, cost, torch.full_like(cost, float('inf')))
-    none = ~ok.any(dim=1)
-    out[:, 0] = torch.where(none, torch.zeros_like(cost[:, 0]), out[:, 0])
-    return out
-
-
-def score_loss_tail(model, costs, sums, min_in_view):
-    """The loss of ``score_loss`` in both directions, from the costs [B,K+1] and sums [B,K+1,8] of the scored levels (entry 0:
-    the true pose); ``model.last_score_loss`` keeps them."""
-    loss = 0
-    for cost, s in zip(costs, sums):
-        B, K = cost.shape[0], cost.shape[1] - 1
-        # eligible_cost's in-view rule over the K + 1 entries; an ineligible negative contributes exactly zero
-        in_view = s[..., 6]
-        ok = (in_view >= float(min_in_view) * in_view.max(dim=1, keepdim=True).values)[:, 1:]
-        # models_kitti.py:592, 1622: log(1 + exp(10 (pos - neg))), averaged; cost <= 4 keeps the exponent below 40
-        t = torch.log(1 + torch.exp(10.0 * (cost[:, :1] - cost[:, 1:])))
-        loss = loss + torch.where(ok, t, torch.zeros_like(t)).sum() / (B * K)     # models_kitti.py:595: summed over the levels
-    model.last_score_loss = dict(costs=[c.detach() for c in costs], sums=sums)
-    return loss
-
-
-def _poses_arg(poses, B: int, name: str = 'poses'):
-    """[K,3] (shared) or [B,K,3] -> [B,K,3] fp32, K >= 1."""
-    p = torch.as_tensor(poses, dtype=torch.float32)
-    if p.dim() == 2 and p.shape[1] == 3 and p.shape[0] >= 1:
-        return p[None].expand(B, -1, -1)
-    if p.dim() == 3 and p.shape[0] == B and p.shape[2] == 3 and p.shape[1] >= 1:
-        return p
-    raise ValueError(f'{name} must be [K,3] or [B,K,3] with B = {B} and K >= 1, got {tuple(p.shape)}')
 
 
 def draw_reinit(n_steps: int, B: int, device):
@@ -934,18 +804,6 @@ def raise_like_reference(trace, in_view, level_first, gn_norm2=None):
     if k_s < steps:
         raise RuntimeError(f'linalg.inv: the normal matrix of LM step {k_s} is singular '
                            '(use_hessian / zero damping / Gauss-Newton with no Jacobian support in one pose component)')
-
-
-_SIDE_STREAMS = {}
-
-
-def _side_stream(device) -> 'torch.cuda.Stream':
-    """One extra stream per device, kept OUTSIDE the modules (a Stream inside a module's __dict__ would break pickling / deepcopy)."""
-    idx = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-    st = _SIDE_STREAMS.get(idx)
-    if st is None:
-        st = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=idx)
-    return st
 
 
 def sat_reach(tables, sizes, mpp, shift_range_lat, shift_range_lon, rotation_range, n: int = 5):
@@ -1068,15 +926,9 @@ class _LocaliseFn(torch.autograd.Function):
     def backward(ctx, d_trace, *unused):
         model = ctx.model
         _phase('loss')
-        if ctx.state is None:
-            raise RuntimeError('backward through the same forward twice: the saved activations (GBs at B = 32) are released after '
-                               'the first backward; retain_graph is not supported by the HIP backward')
-        sat_feats, grd_feats, grd_confs, grd_hw, trace, neq, sat_inv, grd_inv, cs, cg, keep = ctx.state
+        sat_feats, grd_feats, grd_confs, grd_hw, trace, neq, sat_inv, grd_inv, cs, cg, keep = take_state(ctx)
         if d_trace is None:         # (only the confidence maps were used downstream: they are non-differentiable outputs)
             d_trace = torch.zeros_like(trace)
-        # LM_update renormalises both maps, so d_feat is orthogonal to feat: HLA_VGG_BWD_SCALE_INVARIANT (include/hla.h)
-        inv = getattr(model.args, 'Optimizer', 'LM') == 'LM'
-        trim = bool(getattr(model.args, 'bwd_trim', 1))
         # the ground maps' gradient lives in rows h_l/2.. (all the LM loop reads): the backward skips the rows above its support
         f8 = _bwd_first_row8(model, grd_hw, grd_feats[-1].shape[1])       # (grd_feats[-1]: the H/2 map)
         d_sat, d_grd, d_conf, d_lam = model.lm_backward(sat_feats, grd_feats, grd_confs, grd_hw, trace, neq, d_trace, ctx.extra,
@@ -1088,59 +940,30 @@ class _LocaliseFn(torch.autograd.Function):
             d_sat, d_grd = [zf(cs)] + list(d_sat), [zf(cg)] + list(d_grd)
             if grd_confs is not None and all(c is not None for c in d_conf):
                 grd_confs, d_conf = [ctx.conf0] + list(grd_confs), [torch.zeros_like(ctx.conf0)] + list(d_conf)
-        sync = getattr(model, 'grad_sync', None)        # optional: overlap the sat-branch all-reduce with the grd backward
+        a = model.args
+        use_w = model.using_weight and all(c is not None for c in d_conf)
         # LM_update renormalises both projected maps (models_kitti.py:982-990), so the loss does not depend on the per-sample
         # scale of either extractor's output: d_feat is orthogonal to feat and the L2_norm backward needs no (x . dy) pass
-        # (model.bwd_stats = {}: diagnostics, filled with the satellite branch's live / total backward tiles; costs a device sync)
-        # The two extractors' backward passes are independent.  After the data-dependent trimming the satellite branch's launches
-        # are sparse (0.42 of the tiles: many of them fill the chip for a round or two only), so it runs on a side stream next to
-        # the ground branch's: 24.78 -> 24.43 ms per step (same-box A/B, four alternating pairs, the faster one every time).  (The
-        # same split of the two FORWARD passes, both dense, measured 2 % slower.)  Not with a gradient all-reduce installed: there
-        # the satellite bucket is already in flight under the ground branch's backward.  args.bwd_two_streams = 0 switches it off.
-        # Memory: the satellite branch's backward workspace and gradient buffer then come from the side stream's pool of the
-        # caching allocator, so the freed block cannot be reused for the ground branch's workspace on the main stream: peak
-        # training memory is one backward workspace higher (GB-class at B = 32 in fp32) for that 1.4 %.
-        two = bool(getattr(model.args, 'bwd_two_streams', 1)) and sync is None
-        tp = int(getattr(model.args, 'wgrad_two_phase', 0))       # (A/B and tests: bit 0 HLA_VGG_BWD_WGRAD_TWO_PHASE, bit 1 ..._WGRAD0_UNFUSED)
-        if two:
-            cur = torch.cuda.current_stream()
-            side = _side_stream(d_sat[0].device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                g_sat, flat_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, scale_invariant=inv, flat=True, dense=not trim,
-                                                    stats=getattr(model, 'bwd_stats', None), wgrad_two_phase=tp)
-            for t in d_sat:
-                t.record_stream(side)
-        else:
-            g_sat, flat_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, scale_invariant=inv, flat=True, dense=not trim,
-                                                stats=getattr(model, 'bwd_stats', None), wgrad_two_phase=tp)
-        h1 = sync.start({'SatFeatureNet.' + k: v for k, v in g_sat.items()}, flat_sat) if sync else None
-        use_w = model.using_weight and all(c is not None for c in d_conf)
-        g_grd, flat_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
-                                            scale_invariant=inv, first_row8=f8, flat=True, dense=not trim, wgrad_two_phase=tp)
-        h2 = sync.start({'GrdFeatureNet.' + k: v for k, v in g_grd.items()}, flat_grd) if sync else None
-        if two:
-            torch.cuda.current_stream().wait_stream(side)
-            for t in [flat_sat] + list(g_sat.values()):       # allocated on the side stream, consumed (optimizer) on this one
-                t.record_stream(torch.cuda.current_stream())
-        if sync:
-            sync.finish(h1)
-            sync.finish(h2)
-        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
-        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
-        if getattr(model.args, 'train_damping', 0):
+        # (HLA_VGG_BWD_SCALE_INVARIANT, include/hla.h).  model.bwd_stats = {}: diagnostics, filled with the satellite branch's
+        # live / total backward tiles; costs a device sync.  args.wgrad_two_phase: A/B and tests (bit 0
+        # HLA_VGG_BWD_WGRAD_TWO_PHASE, bit 1 ..._WGRAD0_UNFUSED).  args.bwd_two_streams = 0 keeps both branches on one stream.
+        grads = extractor_grads(model, cs, cg, d_sat, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
+                                scale_invariant=getattr(a, 'Optimizer', 'LM') == 'LM', first_row8=f8,
+                                dense=not bool(getattr(a, 'bwd_trim', 1)), wgrad_two_phase=int(getattr(a, 'wgrad_two_phase', 0)),
+                                stats=getattr(model, 'bwd_stats', None), two_streams=bool(getattr(a, 'bwd_two_streams', 1)))
+        if getattr(a, 'train_damping', 0):
             d = model.damping.detach().double()
             sg = torch.sigmoid(d)
             lam = 10.0 ** (-6 + sg * 11.0)
             dlam_dd = lam * np.log(10.0) * 11.0 * sg * (1 - sg)
             if d.dim() == 0:
-                n = 2 if model.args.rotation_range == 0 else 1
+                n = 2 if a.rotation_range == 0 else 1
                 grads['damping'] = (d_lam[:n].sum() * dlam_dd).float()
             else:
                 grads['damping'] = (d_lam.view(1, 3) * dlam_dd).float()
+            sync = getattr(model, 'grad_sync', None)
             if sync:
                 sync.finish(sync.start({'damping': grads['damping']}))
-        ctx.state = None            # release the saved workspaces now, not when the loss tensor dies
         _phase('vgg_bwd')
         return (None,) * 9 + tuple(grads.get(n) for n in ctx.names)
 
@@ -1151,13 +974,7 @@ class _ScoreFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, names, sat_map, grd_img, poses, levels, extra, *params):
-        want_conf = bool(model.using_weight)
-        sat_feats, _, sat_inv, cs = vgg_forward_nhwc(model.SatFeatureNet, sat_map, want_conf=False, defer_norm=True,
-                                                     save_for_backward=True)
-        grd_feats, grd_confs, grd_inv, cg = vgg_forward_nhwc(model.GrdFeatureNet, grd_img, want_conf=want_conf, defer_norm=True,
-                                                             save_for_backward=True)
-        if grd_confs is None:
-            grd_confs = [None] * len(grd_feats)
+        sat_feats, sat_inv, grd_feats, grd_confs, grd_inv, cs, cg = extract_saved(model, sat_map, grd_img, bool(model.using_weight))
         hw = tuple(grd_img.shape[-2:])
         res = [model.score_poses(sat_feats, grd_feats, grd_confs, hw, poses, l, extra, sat_inv, grd_inv) for l in levels]
         costs, sums = tuple(r[0] for r in res), tuple(r[1] for r in res)
@@ -1170,33 +987,15 @@ class _ScoreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *d_out):
         model = ctx.model
-        if ctx.state is None:
-            raise RuntimeError('backward through the same score_candidates call twice: the saved activations are released after '
-                               'the first backward; retain_graph is not supported by the HIP backward')
-        sat_feats, grd_feats, grd_confs, hw, poses, sums, sat_inv, grd_inv, cs, cg = ctx.state
-        use_w = bool(model.using_weight) and all(c is not None for c in grd_confs)
-        d_sat, d_grd, d_conf = [None] * len(sat_feats), [None] * len(sat_feats), [None] * len(sat_feats)
-        for n, l in enumerate(ctx.levels):
-            if d_out[n] is None:            # this level's cost was not used downstream
-                continue
-            d_sat[l], d_grd[l], d_conf[l] = model.score_poses_bwd(sat_feats, grd_feats, grd_confs, hw, poses, l, sums[n], d_out[n],
-                                                                  ctx.extra, sat_inv, grd_inv)
-        for l in range(len(sat_feats)):     # an unscored level takes no part: zeros
-            if d_sat[l] is None:
-                d_sat[l], d_grd[l] = torch.zeros_like(sat_feats[l]), torch.zeros_like(grd_feats[l])
-            if use_w and d_conf[l] is None:
-                d_conf[l] = torch.zeros_like(grd_confs[l])
+        sat_feats, grd_feats, grd_confs, hw, poses, sums, sat_inv, grd_inv, cs, cg = take_state(ctx, 'score_candidates call')
+        bwd = lambda n, l: model.score_poses_bwd(sat_feats, grd_feats, grd_confs, hw, poses, l, sums[n], d_out[n], ctx.extra,
+                                                 sat_inv, grd_inv)
+        d_sat, d_grd, d_conf = _pose.score_level_grads(model, bwd, ctx.levels, d_out, sat_feats, grd_feats, grd_confs)
         # the cost renormalises both maps: every d_map is orthogonal to its map (HLA_VGG_BWD_SCALE_INVARIANT, include/hla.h), and
         # the ground maps' gradient lives in the rows the score reads (row0..: the backward skips the rows above its support)
-        trim = bool(getattr(model.args, 'bwd_trim', 1))
         f8 = 0 if model.polar else _bwd_first_row8(model, hw, grd_feats[-1].shape[1])
-        tp = int(getattr(model.args, 'wgrad_two_phase', 0))
-        g_sat = vgg_backward_nhwc(model.SatFeatureNet, cs, d_sat, scale_invariant=True, dense=not trim, wgrad_two_phase=tp)
-        g_grd = vgg_backward_nhwc(model.GrdFeatureNet, cg, d_grd, grd_confs if use_w else None, d_conf if use_w else None,
-                                  scale_invariant=True, first_row8=f8, dense=not trim, wgrad_two_phase=tp)
-        grads = {'SatFeatureNet.' + k: v for k, v in g_sat.items()}
-        grads.update({'GrdFeatureNet.' + k: v for k, v in g_grd.items()})
-        ctx.state = None                    # release the saved workspaces now
+        grads = extractor_grads(model, cs, cg, d_sat, d_grd, grd_confs if d_conf else None, d_conf, scale_invariant=True,
+                                first_row8=f8, dense=not bool(getattr(model.args, 'bwd_trim', 1)),
+                                wgrad_two_phase=int(getattr(model.args, 'wgrad_two_phase', 0)))
         return (None,) * 7 + tuple(grads.get(n) for n in ctx.names)
-
 
