@@ -21,7 +21,7 @@ HLA_VGG_BWD_DENSE = 2
 HLA_VGG_BWD_WGRAD_TWO_PHASE = 4
 HLA_VGG_BWD_WGRAD0_UNFUSED = 8
 HLA_VGG_BWD_FOLD_DECODER = 16
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 
 class HlaError(RuntimeError):
@@ -194,6 +194,10 @@ def load() -> C.CDLL:
                                          vp, vp, vp, vp, sz, i, vp]
     lib.hla_s2g_lm_solve.restype = i
     lib.hla_s2g_lm_solve.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), vp, vp, vp, vp, vp, vp, vp, sz, i, vp]
+    lib.hla_s2g_views_workspace_bytes.restype = sz
+    lib.hla_s2g_views_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, i]
+    lib.hla_s2g_lm_solve_views.restype = i
+    lib.hla_s2g_lm_solve_views.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, vp]
     lib.hla_s2g_pose_score_workspace_bytes.restype = sz
     lib.hla_s2g_pose_score_workspace_bytes.argtypes = [C.POINTER(S2GConfig), C.POINTER(S2GLevel), i, i]
     lib.hla_s2g_pose_score.restype = i

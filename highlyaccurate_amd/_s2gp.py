@@ -290,6 +290,8 @@ class S2GPBase(nn.Module):
         self.last_reach_flag = None  # int32 [B] of the last localise that ran with args.sat_reach_crop in effect (1: recomputed), else None
         self.last_search = None      # forward_search: cost, sums, start_index, traces, final_cost, best of the last call
         self.last_score_loss = None  # score_loss: costs [B,K+1] and sums [B,K+1,8] per scored level of the last call (entry 0: the true pose)
+        self._view_tables = {}
+        self.last_views = None       # lm_solve_views: dict(trace, normal_eq [steps,B,16], view_sums [steps,B,V,16]) of the last call
 
     # -- geometry tables ---------------------------------------------------------------------
     def xyz_tables(self, grd_H: int, grd_W: int, device):
@@ -508,6 +510,84 @@ class S2GPBase(nn.Module):
         self.last_trace, self.last_normal_eq = trace.detach(), neq
         return trace
 
+    def view_tables(self, grd_H: int, grd_W: int, camera_k, device):
+        """Per level, the V ground-plane tables of ``forward_views`` back to back, [V,h,w,3]: ``ground_plane_table`` with view v's
+        ``camera_k[v]`` (given for a 256x1024 image, the convention of ``ford_K_network_input``), sized like ``xyz_tables``;
+        proj='polar': V copies of the polar table (it has no intrinsics).  Cached per (size, matrices, device)."""
+        K = torch.as_tensor(camera_k, dtype=torch.float32).cpu().reshape(-1, 3, 3)
+        key = (grd_H, grd_W, K.numpy().tobytes(), str(device))
+        if key not in self._view_tables:
+            hw = [(grd_H / 2 ** (3 - l), grd_W / 2 ** (3 - l)) for l in range(4)]
+            self._view_tables[key] = [torch.stack([polar_plane_table(h, w) if self.polar else ground_plane_table(k.tolist(), h, w, 256, 1024)
+                                                   for k in K]).contiguous().to(device) for h, w in hw]
+        return self._view_tables[key][1:3] if self.level == 2 else self._view_tables[key]
+
+    @_lib.on_device(lambda self, sat_feats, *a, **k: sat_feats[0])
+    def lm_solve_views(self, sat_feats, grd_feats, grd_confs, grd_hw, V, R, T, side_m, tables=None, level_first=0, init_pose=None,
+                       sat_inv_norm=None, grd_inv_norm=None):
+        """The LM loop over V views of one body pose (``hla_s2g_lm_solve_views``, include/hla.h): the analogue of ``lm_solve``
+        for the Ford chain.  One step is the reference's LM_update on the UNION of the views' pixels: every view's normal-equation
+        sums are formed at the common pose with that view's table and (R_v, T_v), added in view order, and solved once.
+        sat_feats[l] [B,A,A,C]; grd_feats[l] [B*V,h',w,C] and grd_confs[l] [B*V,h',w] with view v of sample b at index b*V+v;
+        R [B,V,3,3], T [B,V,3] camera -> body; ``tables[l]`` [V,h,w,3] (default: this model's ground-plane table for every view);
+        sat_inv_norm[l] [B], grd_inv_norm[l] [B*V] fp64 with raw maps.  The re-initialisation draws are ``draw_reinit(steps, B)``:
+        the RNG consumption of ``forward`` with batch B.  A view that lies outside the satellite map still contributes the
+        norm of its ground features, as out-of-map pixels of a single view do.  Inference only: no backward exists.
+        Returns the trace [B,N_iters,L,3]; ``last_views`` keeps dict(trace, normal_eq, view_sums)."""
+        if not self.ford:
+            raise NotImplementedError('lm_solve_views: the Ford chain only (the KITTI chain has no camera extrinsics)')
+        if getattr(self.args, 'dropout', 0):
+            raise NotImplementedError('lm_solve_views with args.dropout: the dropout loop is not built for several views')
+        lib = _lib.load()
+        dev = sat_feats[0].device
+        B, L, V = sat_feats[0].shape[0], len(sat_feats), int(V)
+        if tables is None:
+            tables = [t[None].expand(V, -1, -1, -1).contiguous() for t in self.xyz_tables(grd_hw[0], grd_hw[1], dev)]
+        R = R.to(dev).float().contiguous()
+        T = T.to(dev).float().contiguous()
+        if tuple(R.shape) != (B, V, 3, 3) or tuple(T.shape) != (B, V, 3):
+            raise ValueError(f'R must be [B,V,3,3] and T [B,V,3] with B = {B}, V = {V}, got {tuple(R.shape)} and {tuple(T.shape)}')
+        cfg = self._config(L, level_first)
+        lv = (_lib.S2GLevel * L)()
+        for l in range(L):
+            s, g, tab = sat_feats[l], grd_feats[l], tables[l]
+            A, w, Cn = s.shape[1], g.shape[2], g.shape[3]
+            h = tab.shape[1]
+            row0 = 0 if self.polar else h // 2
+            skip = h - g.shape[1]
+            if not (s.shape[2] == A and s.shape[3] == Cn and tuple(tab.shape) == (V, h, w, 3) and tab.dtype == torch.float32
+                    and tab.is_contiguous() and tab.device == dev and 0 <= skip <= row0 and g.shape[0] == B * V
+                    and s.is_contiguous() and g.is_contiguous() and s.dtype == g.dtype and s.dtype in _FEAT_DTYPES):
+                raise ValueError(f'level {l}: inconsistent maps sat {tuple(s.shape)} / grd {tuple(g.shape)} / tables {tuple(tab.shape)} '
+                                 f'for B = {B}, V = {V} and a {tuple(grd_hw)} ground image')
+            lv[l].sat_feat, lv[l].grd_feat, lv[l].feat_dtype = s.data_ptr(), g.data_ptr(), _FEAT_DTYPES[s.dtype]
+            lv[l].grd_conf = grd_confs[l].data_ptr() if (self.using_weight and grd_confs[l] is not None) else 0
+            lv[l].xyz = tab.data_ptr()
+            lv[l].sat_inv_norm = sat_inv_norm[l].data_ptr() if sat_inv_norm is not None else 0
+            lv[l].grd_inv_norm = grd_inv_norm[l].data_ptr() if grd_inv_norm is not None else 0
+            lv[l].A, lv[l].h, lv[l].w, lv[l].C, lv[l].row0, lv[l].grd_row_skip = A, h, w, Cn, row0, skip
+            lv[l].meter_per_pixel = float(side_m) / A               # models_ford.py:230
+            lv[l].centre = float(A // 2)                            # models_ford.py:231
+        steps = L * self.N_iters
+        rand_uv = self._draw_reinit(steps, B, dev)
+        trace = torch.empty(B, self.N_iters, L, 3, device=dev, dtype=torch.float32)
+        neq = torch.empty(steps, B, 16, device=dev, dtype=torch.float64)
+        sums = torch.empty(steps, B, V, 16, device=dev, dtype=torch.float64)
+        nbytes = lib.hla_s2g_views_workspace_bytes(C.byref(cfg), lv, B, V)
+        if nbytes == 0:
+            raise _lib.HlaError(f'hla_s2g_views_workspace_bytes: {lib.hla_last_error().decode()}')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        p0 = init_pose.to(dev).float().contiguous() if init_pose is not None else None
+        rc = lib.hla_s2g_lm_solve_views(C.byref(cfg), lv, V, _lib.ptr(R), _lib.ptr(T), _lib.ptr(p0), _lib.ptr(rand_uv), _lib.ptr(trace),
+                                        _lib.ptr(neq), _lib.ptr(sums), _lib.ptr(ws), nbytes, B, _lib.stream_ptr())
+        _lib.check(rc, 'hla_s2g_lm_solve_views')
+        # the reference's singular-matrix error under the flags that can cause it, as in lm_solve (costs a host sync there only)
+        risky = cfg.optimizer == 3 or (cfg.optimizer == 0 and (cfg.use_hessian or min(cfg.damping[i] for i in range(3)) <= 0.0))
+        if risky:
+            raise_like_reference(trace, None, level_first, gn_norm2=neq[:, :, 0] if cfg.optimizer == 3 else None)
+        self.last_views = dict(trace=trace, normal_eq=neq, view_sums=sums)
+        return trace
+
     def lm_grad_buffers(self, sat_feats, grd_feats, grd_confs, row0s, row_skips, grd_first_row8=0, overwrite=True, deterministic=False):
         """The buffers ``hla_s2g_lm_solve_bwd`` accumulates into, cleared where they have to be by ONE launch (``hla_zero_fill``) on
         the current stream: (d_sat[l], d_grd[l], d_conf[l] or None, d_lambda[4]).
@@ -670,9 +750,10 @@ class S2GPBase(nn.Module):
             solve = lambda p0: self.lm_solve(sat_feats, grd_feats, grd_confs, hw, extra, level_first, p0, sat_inv, grd_inv)
             return _pose.search(self, cand, M, score, solve, score_level, len(sat_feats) - 1, min_in_view)
 
-    def _features(self, sat_map, grd_img, want_conf, return_confs, sat_c32=0, col_state=None):
+    def _features(self, sat_map, grd_img, want_conf, return_confs, sat_c32=0, col_state=None, pair=True):
         """Both extractors of the inference path: (sat_feats, sat_inv, grd_feats, grd_confs, grd_inv), normalisation deferred.
-        ``sat_c32`` / ``col_state``: the satellite extractor's first_col32 and the dict that receives its fix-up state."""
+        ``sat_c32`` / ``col_state``: the satellite extractor's first_col32 and the dict that receives its fix-up state.
+        ``pair`` = False: never the paired launches (``forward_views``: the two batches differ in size)."""
         # Reduced-precision inference modes: the LM loop reads fp16 feature maps (written saturating by the three feature
         # layers' epilogues; also in bf16 mode: bf16's 8 significand bits moved the worst golden seed's pose 23x, fp16's 11
         # move it 1.6x).  With the gather loop written on channel PAIRS (lm_solve.hip) the accumulate kernels are VALU-bound on
@@ -696,7 +777,7 @@ class S2GPBase(nn.Module):
         f8 = f8 if f8 >= 4 else 0
         # A batch that fills the chip: the two extractors are the same ten launches on two images, and each of them runs for both
         # as ONE launch (args.pair_extractor_launches, default 1; the library falls back to the two forwards where it cannot pair)
-        if (not small and not want_conf and self.level != 4 and bool(getattr(self.args, 'pair_extractor_launches', 1))
+        if (pair and not small and not want_conf and self.level != 4 and bool(getattr(self.args, 'pair_extractor_launches', 1))
                 and self.GrdFeatureNet.precision == self.SatFeatureNet.precision):
             (sat_feats, sat_inv), (grd_feats, grd_inv), _ = vgg_forward_pair_nhwc(
                 (self.SatFeatureNet, self.GrdFeatureNet), (sat_map, grd_in), first_row8=(0, f8), feat16=f16,

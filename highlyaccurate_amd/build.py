@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libhla.so')
 # (source, HLA_TU_DTYPE): the conv-heavy files are compiled once per dtype (kernels) plus once as the dispatcher (-1)
-SOURCES = [('capi.hip', -1), ('prof.hip', -1), ('lm_solve.hip', -1), ('lm_backward.hip', -1), ('lm_g2s.hip', -1),
+SOURCES = [('capi.hip', -1), ('prof.hip', -1), ('lm_solve.hip', -1), ('lm_views.hip', -1), ('lm_backward.hip', -1), ('lm_g2s.hip', -1),
            ('grid_sample.hip', -1), ('sat_tile.hip', -1), ('pose_loss.hip', -1), ('fill.hip', -1), ('orien_corr.hip', -1), ('pose_score.hip', -1),
            ('g2s_pose_score.hip', -1), ('g2s_corr.hip', -1)] + \
           [(f, d) for f in ('vgg.hip', 'vgg_backward.hip') for d in (0, 1, 2, 3, -1)]

@@ -1,5 +1,5 @@
-// The per-tile part of the forward LM accumulate kernels (csrc/lm_solve.hip), as TEXT: lm_accum includes it once, lm_repair_loop
-// once per channel count.  One tile of one sample, by 256 threads: pixel set-up into pp[], the gather loop, the wave and block
+// The per-tile part of the forward LM accumulate kernels, as TEXT: lm_accum (csrc/lm_solve.hip) includes it once, lm_repair_loop
+// once per channel count, lmv_accum (csrc/lm_views.hip) once.  One tile of one sample, by 256 threads: pixel set-up into pp[], the gather loop, the wave and block
 // reductions and the tile's 14 published partials (row `tile` of the sample's rows of a.part).
 //
 // Why not a __forceinline__ function: the gather's sums are written as a * b + c * d and -ffp-contract=fast lets the backend fuse
@@ -15,6 +15,9 @@
 //   PixParam pp[FWD_MAX_TP]; float red[4][14]; double redd[14]      shared arrays of these 256 threads
 //   LM_TILE_COEF            expression: const double* to the sample's COEF_N projection coefficients
 //   LM_TILE_BEFORE_PUBLISH  statement(s) between the last barrier and the publication (lm_accum: waves 1-3 leave)
+// Everything the fragment indexes by b -- a.sat, a.grd, a.conf, a.part, the depth map of a.pts, a.reach_flag -- it indexes by the
+// SAME b.  A kernel whose arrays do not share one index (lmv_accum: ground map per view, satellite map per sample, table per
+// view) hands the fragment copies of those pointers moved to its elements and b = 0, and leaves this text alone.
 // The barriers are __syncthreads(): in lm_accum the 256 threads are the workgroup; in lm_repair_loop four such groups share one
 // and walk their tiles in lockstep.  Declares p0, np, cf, lane, wave, ... : include it inside a block of its own.
 // An inactive group is kept from every memory access by np = 0 ALONE: both pixel loops run `< np`, the address arithmetic in
@@ -22,7 +25,7 @@
 // Not pinned (left to -ffp-contract=fast, held by tests/test_lm_repair_launch.py): the per-pixel sums b1, b2, Q, U3, V3 -- written
 // as fmaf they no longer vectorise, none of the 32 choices keeps lm_accum's instruction stream -- and the fp64 publication sums.
 #if !defined(LM_TILE_COEF) || !defined(LM_TILE_BEFORE_PUBLISH)
-#error "lm_tile_body.h is a text fragment of lm_accum / lm_repair_loop (csrc/lm_solve.hip): define LM_TILE_COEF and LM_TILE_BEFORE_PUBLISH"
+#error "lm_tile_body.h is a text fragment of lm_accum / lm_repair_loop / lmv_accum: define LM_TILE_COEF and LM_TILE_BEFORE_PUBLISH"
 #endif
   const int p0 = tile * a.TP;
   const int np = active ? min(a.TP, a.npix - p0) : 0;

@@ -4,7 +4,8 @@ from __future__ import annotations
 
 import torch
 
-from ._s2gp import S2GPBase, loss_func, loss_from_trace, pose_grid  # noqa: F401
+from . import _lib
+from ._s2gp import S2GPBase, ford_K_network_input, loss_func, loss_from_trace, pose_grid  # noqa: F401
 
 
 class LM_S2GP_Ford(S2GPBase):
@@ -49,3 +50,44 @@ class LM_S2GP_Ford(S2GPBase):
         back-propagates into both extractors.  ``last_score_loss`` keeps the costs and sums."""
         extra = dict(R_FL=R_FL, T_FL=T_FL, side_m=float(satmap_sidelength_meters))
         return self._score_loss(sat_map, grd_img_left, extra, candidates, (gt_shiftu, gt_shiftv, gt_heading), levels, min_in_view)
+
+    @_lib.on_device(lambda self, sat_map, *a, **k: sat_map)
+    def forward_views(self, sat_map, grd_imgs, satmap_sidelength_meters, R, T, camera_k=None, level_first=0, init_pose=None):
+        """Multi-view localisation: ONE LM loop over V ground images per satellite tile -- several calibrated cameras, or earlier
+        frames carried forward by odometry -- each with its own rigid transform to the one body pose being solved for.
+        sat_map [B,3,A,A]; grd_imgs [B,V,3,H,W], one size for all views; R [B,V,3,3], T [B,V,3] camera v -> body (what
+        ``forward`` takes as R_FL, T_FL); camera_k [V,3,3] in the convention of ``ford_K_network_input()`` (given for a 256x1024
+        image), default: that matrix for every view.  GrdFeatureNet is shared by all views, so the weights of a single-view
+        training apply.  One step is the reference's LM_update on the union of the views' pixels (``lm_solve_views``); V = 1 is
+        ``forward(mode='test')``, with the same RNG consumption.  A view outside the satellite map still contributes the norm of
+        its ground features.  Returns the tuple of ``forward(mode='test')``: (shift_u[B], shift_v[B], theta[B]).
+        Inference only: it runs under no_grad, its outputs carry no gradient, and NO BACKWARD EXISTS (there is no mode='train')."""
+        if getattr(self.args, 'dropout', 0):
+            raise NotImplementedError('forward_views with args.dropout: the dropout loop is not built for several views')
+        if getattr(self.args, 'estimate_depth', 0):
+            raise NotImplementedError('forward_views with args.estimate_depth: depth lifting is not built for several views')
+        if self.polar and level_first:
+            raise NotImplementedError("LM_S2GP_Ford(proj='polar') with level_first=1: the reference's level-first loop reads only "
+                                      "the bottom half of the polar maps (it has no proj branch); that combination is not built")
+        _lib.require_gpu(sat_map, 'sat_map')
+        _lib.require_gpu(grd_imgs, 'grd_imgs')
+        if sat_map.dim() != 4 or grd_imgs.dim() != 5 or sat_map.shape[0] != grd_imgs.shape[0] or sat_map.shape[1] != 3 \
+                or grd_imgs.shape[2] != 3 or sat_map.shape[2] != sat_map.shape[3] or grd_imgs.shape[1] < 1:
+            raise ValueError(f'expected sat_map [B,3,A,A] and grd_imgs [B,V,3,H,W] with one B, got {tuple(sat_map.shape)} '
+                             f'and {tuple(grd_imgs.shape)}')
+        _lib.same_device(('sat_map', sat_map), ('grd_imgs', grd_imgs), ('parameters', self.damping))
+        B, V, _, H, W = grd_imgs.shape
+        if V > 8:
+            raise ValueError(f'forward_views: at most 8 views, got {V}')
+        K = torch.as_tensor(ford_K_network_input() if camera_k is None else camera_k, dtype=torch.float32).cpu()
+        K = K.reshape(1, 3, 3).expand(V, 3, 3) if K.numel() == 9 else K
+        if tuple(K.shape) != (V, 3, 3):
+            raise ValueError(f'camera_k must be [V,3,3] with V = {V}, got {tuple(K.shape)}')
+        with torch.no_grad():
+            tables = self.view_tables(H, W, K, sat_map.device)
+            sat_feats, sat_inv, grd_feats, grd_confs, grd_inv = self._features(sat_map, grd_imgs.reshape(B * V, 3, H, W),
+                                                                               bool(self.using_weight), False, pair=False)
+            trace = self.lm_solve_views(sat_feats, grd_feats, grd_confs, (H, W), V, R, T, float(satmap_sidelength_meters), tables,
+                                        level_first, init_pose, sat_inv, grd_inv)
+        self.last_trace = trace
+        return trace[:, -1, -1, 0], trace[:, -1, -1, 1], trace[:, -1, -1, 2]

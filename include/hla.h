@@ -63,7 +63,7 @@ const char* hla_last_error(void);
  * with its own struct sizes (ctypes structs are positional: a mismatch corrupts silently).  highlyaccurate_amd/_lib.py
  * does both at load time, and rebuilds or refuses a binary whose hla_source_hash() is not the hash of the sources
  * next to it (the library is git-ignored but shipped prebuilt). */
-#define HLA_ABI_VERSION 32
+#define HLA_ABI_VERSION 33
 int hla_abi_version(void);
 const char* hla_source_hash(void); /* sha256 (hex) of the csrc sources, this header and the compiler flags at build time */
 typedef enum hla_struct_id {
@@ -425,6 +425,43 @@ int hla_s2g_lm_solve(const hla_s2g_config* cfg, const hla_s2g_level* levels, con
                      double* normal_eq, void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Multi-view localisation (no reference function; the reference's drivers carry --stereo / --sequence, which no model reads):
+ * ONE LM loop over V ground images per satellite tile, each with its own rigid transform (R_v, T_v) from its camera to the ONE
+ * body pose being solved for -- several calibrated cameras, or earlier frames carried forward by odometry.  Ford chain only
+ * (models_ford.py:173-264 takes the extrinsics), inference only: there is no backward.
+ *
+ * One step is the reference's LM_update (models_ford.py:384-466) applied to the UNION of the views' pixels.  View v of sample b
+ * produces the 14 sums of normal_eq at the common pose, de-normalised as hla_s2g_lm_solve does it (sat_inv_norm[b] for s and J,
+ * grd_inv_norm[b*V+v] for g); the V vectors are added in fp64 in view order, ((0 + s_0) + s_1) + ..., and the step is solved from
+ * the total, so both norms and their 1e-6 clamps apply to the total.  Damping, use_hessian, GN's ng := 1, the +-2.5
+ * re-initialisation rule with the caller's draws and dof are those of hla_s2g_lm_solve.  (Per-view normalisation,
+ * sum_v H_v / ||s_v||^2, is NOT what this computes.)  Hence: V = 1 is hla_s2g_lm_solve's step; a duplicated view changes nothing
+ * beyond fp64 rounding; permuting the views changes only the fp64 addition order; a view whose table has no point with z > 0
+ * contributes fourteen exact zeros (the result is bit for bit that of the call without it); a view that is merely OUTSIDE the
+ * satellite map still contributes its ||g||^2, as out-of-map pixels of a single view do.
+ *
+ * levels   per level, for this entry point:
+ *            sat_feat [B,A,A,C]; sat_inv_norm [B] or NULL
+ *            grd_feat [B*V, h-grd_row_skip, w, C]: view v of sample b is index b*V+v; grd_conf [B*V, h-grd_row_skip, w] likewise
+ *            grd_inv_norm [B*V] or NULL
+ *            xyz      V tables back to back, [V,h,w,3]: the cameras may differ in intrinsics (one image size for all views)
+ *            row0, grd_row_skip, meter_per_pixel, centre, feat_dtype, A, h, w, C: as in hla_s2g_lm_solve; all depth fields NULL / 0
+ * cfg      ford = 1; optimizer 0 (LM) or 3 (GN, iteration-first only); using_weight, use_hessian, level_first, dof, damping and the
+ *          ranges as in hla_s2g_lm_solve.  Refused with HLA_ERR_ARG and no launch: ford = 0, keep != NULL, a depth field,
+ *          reach_mode != 0, count_in_view != 0, optimizer 1 / 2, proj != 0, V outside 1..8 (a cap: Ford carries seven cameras)
+ * R, T     [B,V,3,3], [B,V,3] fp32: camera v -> body
+ * pose0    [B,3] or NULL;  rand_uv [n_steps,2,B]: per SAMPLE, as in hla_s2g_lm_solve;  trace [B,n_iters,n_levels,3] out
+ * normal_eq [n_steps,B,16] fp64 out or NULL: the TOTAL sums, slots 14 / 15 zero
+ * view_sums [n_steps,B,V,16] fp64 out or NULL: each view's de-normalised sums, slots 14 / 15 zero
+ * Two launches per step plus one init launch, all on `stream` (no internal stream: also while `stream` is being captured).  The
+ * results of sample b do not depend, bit for bit, on B, on its batch mates or on repeats.
+ * hla_s2g_views_workspace_bytes returns 0 and sets the last error on bad sizes. */
+size_t hla_s2g_views_workspace_bytes(const hla_s2g_config* cfg, const hla_s2g_level* levels, int B, int V);
+int hla_s2g_lm_solve_views(const hla_s2g_config* cfg, const hla_s2g_level* levels, int V, const float* R, const float* T,
+                           const float* pose0, const float* rand_uv, float* trace, double* normal_eq, double* view_sums,
+                           void* workspace, size_t workspace_bytes, int B, hla_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Pose scoring (no reference function: the objective of LM_update, models_kitti.py:982-996 / models_ford.py:414-430, read back
  * at given poses).  For ONE level, B samples and K candidate poses per sample, without Jacobians.  Over the pixels of rows
  * row0..h-1 of the level's ground map, for sample b and hypothesis k:
@@ -736,7 +773,7 @@ int hla_g2s_corr_triplet_loss_bwd(const float* corr, const float* gt_shift_u, lo
  * When enabled, every kernel launch of the entry points above is bracketed by two hipEvents
  * on its own stream; hla_prof_fetch synchronises them and returns one record per launch.
  * ------------------------------------------------------------------------- */
-#define HLA_PROF_NKERNELS 20 /* (17 before lm_repair_loop got an id of its own, 18 before hla_g2s_corr's two: a caller that sizes a table by it recompiles) */
+#define HLA_PROF_NKERNELS 22 /* (17 before lm_repair_loop got an id of its own, 18 before hla_g2s_corr's two, 20 before hla_s2g_lm_solve_views' two: a caller that sizes a table by it recompiles) */
 typedef struct hla_prof_record {
   int kernel_id;  /* index for hla_prof_kernel_name */
   float ms;       /* event-to-event duration on the launch stream */
